@@ -1,6 +1,7 @@
 """Benchmark: KMC particle-updates/s of the HIP engine (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--evolve E]
+                    [--dump-outputs DIR] [--full]
 
 Ranks.  One process per GPU, each an independent replica trajectory (key =
 (seed, rank)) — SURVEY.md §8(e) "replicas only" — with one RCCL all-reduce of
@@ -12,19 +13,28 @@ processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* on 127.0.0.1), and exits
 with the first failing rank's code.  Every rank checks the world size and that
 its device is distinct from the others'.
 
-Window.  After the keyed placement: W warm-up steps, a timed K-step window
-from the fresh placement (ms_per_step_fresh), E untimed evolution steps
-toward the bond-rich steady state the reference simulates for 2e7 steps, W
-warm-up steps with every kernel bracketed (per-kernel breakdown, dominant
-kernel), then THE timed window of exactly K steps (barrier + device sync on
-both sides, max over ranks) that `value` and `ms_per_step` report.
+Window.  A plain run does only what the headline figure needs: the keyed
+placement, W + K + E untimed steps toward the bond-rich steady state the
+reference simulates for 2e7 steps, W warm-up steps, then THE timed window of
+exactly K steps (barrier + device sync on both sides, max over ranks) that
+`value` and `ms_per_step` report.  --dump-outputs DIR then writes what that
+window returned to its caller (dump_outputs below).
+
+--full adds every other measurement, around the same timed steps of the same
+trajectory: the first W + K steps become W warm-up steps and a timed K-step
+window from the fresh placement (ms_per_step_fresh), the warm-up before the
+timed window brackets every kernel (per-kernel breakdown, dominant kernel),
+the timed window brackets the dominant kernel in every 8th step (roofline),
+and the CPU baseline runs afterwards.  --no-fresh-window, --no-cpu-baseline
+and --profile select among these.
 
 Rank 0 prints ONE JSON line:
   value        particle-updates/s over all ranks = N_gpus · particles · K / t
-  roofline     the dominant kernel's algorithmic HBM bytes per launch ÷ its
+  ms_per_step  milliseconds per step of the timed window
+  roofline     (--full) the dominant kernel's algorithmic HBM bytes per launch ÷ its
                average duration (HIP events on the engine's stream over the
                timed region); peak 8 TB/s (MI355X HBM3E)
-  cpu_baseline the keyed CPU oracle, one pinned core, on a bounded sample of
+  cpu_baseline (--full) the keyed CPU oracle, one pinned core, on a bounded sample of
                the same state (rank 0 at N = 1 only), plus an ensemble of one
                oracle per core and the C1 link to the unmodified reference
 """
@@ -126,9 +136,15 @@ def parse(argv):
     ap.add_argument("--evolve", type=int, default=None,
                     help="untimed steps before the timed window (default: the workload's, C3 20000)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the fresh-placement window, the per-kernel breakdown and roofline, "
+                         "and the CPU baseline (a plain run only times the K steps)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed window, write what it returned as DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-baseline-steps", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fresh-window", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fresh-window", action="store_true",
+                    help="skip the first W + K steps (with --full: the fresh-placement window)")
     ap.add_argument("--save-state", default="", help="write the exact state after the evolution (KMCSTAT1)")
     ap.add_argument("--load-state", default="",
                     help="start from an exact state file instead of placement + fresh window + evolution "
@@ -136,7 +152,10 @@ def parse(argv):
     ap.add_argument("--profile", action="store_true", help="print the per-kernel breakdown to stderr")
     ap.add_argument("--launcher-check", action="store_true",
                     help="ranks rendezvous over gloo and report who they are; no GPU work (launcher test)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.profile and not args.full:
+        ap.error("--profile prints the per-kernel breakdown, which only a --full run measures")
+    return args
 
 
 # ---------------------------------------------------------------- launcher
@@ -319,11 +338,15 @@ def run_rank(args, rank: int, world: int, local: int):
 
     # fresh placement window (bonds ~0: the early transient)
     fresh_ms = None
-    if not args.no_fresh_window:
+    if not args.no_fresh_window and args.full:
         if args.warmup:
             sim.step(args.warmup)
         dt_f, _ = timed(args.steps)
         fresh_ms = max_over_ranks(dt_f)[0] / args.steps * 1e3
+    elif not args.no_fresh_window:
+        # a plain run takes the same steps untimed, so that its timed window
+        # is the same stretch of the trajectory as a --full run's
+        sim.step(args.warmup + args.steps)
     # evolution toward the steady state (untimed)
     t0 = time.perf_counter()
     chunk = 5000
@@ -339,18 +362,22 @@ def run_rank(args, rank: int, world: int, local: int):
     if args.save_state:
         sim.save_state(args.save_state)
 
-    # warm-up with every kernel bracketed: find the dominant kernel
-    sim.set_timing(engine.kernel_names())
+    # --full: warm-up with every kernel bracketed, to find the dominant kernel
+    if args.full:
+        sim.set_timing(engine.kernel_names())
     if args.warmup:
         sim.step(args.warmup)
-    kt = sim.kernel_times()
+    kt = sim.kernel_times() if args.full else {}
     dom = max(kt, key=lambda k: kt[k][0]) if kt else "k_propose"
     breakdown = {k: round(v[0] / max(v[1], 1), 4) for k, v in sorted(kt.items(), key=lambda x: -x[1][0])}
-    # timed region: only the dominant kernel is bracketed, in every 8th step
+    # timed region: --full brackets only the dominant kernel, in every 8th step
     # (an event pair adds a few microseconds of queue time to its step)
-    sim.set_timing([dom, *[k for k in DETAIL_KERNELS if k != dom]], every=TIMING_EVERY)
+    if args.full:
+        sim.set_timing([dom, *[k for k in DETAIL_KERNELS if k != dom]], every=TIMING_EVERY)
     dt_local, (sums, maxima, cluster) = timed(args.steps)
     dt, per_rank = max_over_ranks(dt_local)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_obs["obs"], sums, maxima, cluster, sim.get_state())
 
     # what the all-reduce did: at N = 1 the reduced series must equal this
     # rank's own observables (the same RCCL call the N-GPU run makes)
@@ -361,7 +388,7 @@ def run_rank(args, rank: int, world: int, local: int):
     if world == 1:
         reduce_info["equals_local"] = bool((sums == own_s).all() and (maxima == own_m).all())
 
-    ktimed = sim.kernel_times()
+    ktimed = sim.kernel_times() if args.full else {}
     total_ms, launches = ktimed.get(dom, (0.0, 0))
     avg_s = total_ms / 1e3 / max(launches, 1)
     detail = {}
@@ -394,7 +421,7 @@ def run_rank(args, rank: int, world: int, local: int):
     ms_per_step = dt / args.steps * 1e3
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         steps = args.cpu_baseline_steps or w["cpu_sample_steps"]
         cpu = cpu_baseline(args.workload, args.seed, sim, steps, w.get("cpu_ensemble_max", MAX_CPU_WORKERS))
 
@@ -404,6 +431,27 @@ def run_rank(args, rank: int, world: int, local: int):
 
     if rank == 0:
         rate = world * n * args.steps / dt
+        # a plain run reports the whole step against the HBM peak; the
+        # per-kernel figures need the event brackets of a --full run
+        roofline = {
+            "bound": "hbm",
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "step_bytes": step_b,
+            "step_frac": step_b / (ms_per_step / 1e3) / 1e9 / HBM_PEAK_GBS,
+        }
+        if args.full:
+            roofline.update({
+                "kernel": dom,
+                "achieved": achieved,
+                "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                "traffic": traffic,
+                "traffic_source": TRAFFIC_JSON if traffic is not None else None,
+                "kernels": list(PROPOSE_PHASE) if dom == "k_propose" else [kernel_trace_name(dom)],
+                "bytes_per_launch": kb,
+                "avg_launch_ms": avg_s * 1e3,
+                "by_kernel": detail,
+            })
         line = {
             "metric": METRIC,
             "value": None if shared else rate,
@@ -411,6 +459,7 @@ def run_rank(args, rank: int, world: int, local: int):
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_per_step,
             "steps_per_s": args.steps / dt,
             "higher_is_better": True,
@@ -437,22 +486,7 @@ def run_rank(args, rank: int, world: int, local: int):
                 "max_complex_ensemble": int(maxima[-1, 0]),
                 "mean_cluster_size_ensemble": float(cluster[-1]),
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": dom,
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                "traffic": traffic,
-                "traffic_source": TRAFFIC_JSON if traffic is not None else None,
-                "kernels": list(PROPOSE_PHASE) if dom == "k_propose" else [kernel_trace_name(dom)],
-                "bytes_per_launch": kb,
-                "avg_launch_ms": avg_s * 1e3,
-                "step_bytes": step_b,
-                "step_frac": step_b / (ms_per_step / 1e3) / 1e9 / HBM_PEAK_GBS,
-                "by_kernel": detail,
-            },
+            "roofline": roofline,
             "cpu_baseline": cpu,
             "ensemble_reduce": reduce_info,
             "library": library,
@@ -464,6 +498,40 @@ def run_rank(args, rank: int, world: int, local: int):
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     sim.close()
     dist.destroy_process_group()
+
+
+# ---------------------------------------------------------------- outputs
+DUMP_MAX_ROWS = 100000  # of the timed window's per-step records (the last ones)
+DUMP_SAMPLE = 20000  # proteins of each kind whose final state is written
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path: str, obs, sums, maxima, cluster, state) -> None:
+    """What the timed window handed its caller, as float64 .npy files (about
+    30 MB at most): the per-step records sim.step returned and their ensemble
+    reduction (the last DUMP_MAX_ROWS steps), and the state the window left
+    the simulation in, for a fixed seeded sample of DUMP_SAMPLE receptors and
+    ligands (all of them where there are fewer).  The trajectory is keyed by
+    (seed, rank), so equal arguments give equal files from run to run."""
+    os.makedirs(path, exist_ok=True)
+    rows = slice(max(0, len(obs) - DUMP_MAX_ROWS), None)
+    fields = [f for f in obs.dtype.names if f != "reserved"]
+    out = {
+        "obs": np.stack([obs[f].astype(np.float64) for f in fields], axis=1)[rows],
+        "ensemble_sums": sums.astype(np.float64)[rows],
+        "ensemble_maxima": maxima.astype(np.float64)[rows],
+        "ensemble_cluster_size": np.asarray(cluster, dtype=np.float64)[rows],
+        "state_counters": np.append(state.counters.astype(np.float64), float(state.step)),
+    }
+    rng = np.random.default_rng(DUMP_SEED)
+    for kind, pos, ints in (("receptors", state.ra, state.a_int), ("ligands", state.rb, state.b_int)):
+        n = pos.shape[1]
+        ids = np.sort(rng.choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+        out[f"state_{kind}_ids"] = ids.astype(np.float64)
+        out[f"state_{kind}_beads"] = np.ascontiguousarray(pos[:, ids].T)
+        out[f"state_{kind}_ints"] = ints[:, ids].T.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------- CPU baseline

@@ -27,7 +27,7 @@ def test_bench_two_ranks_shared_device_equals_oracle_replicas():
     env["KMC_BENCH_SHARED_DEVICE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--workload", "C1",
                         "--steps", str(STEPS), "--warmup", str(WARMUP), "--evolve", str(EVOLVE),
-                        "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=280)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=280)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [x for x in r.stdout.splitlines() if x.strip()]
     assert len(lines) == 1, r.stdout

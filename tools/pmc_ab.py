@@ -87,7 +87,7 @@ def main():
                 label, env = variant_env(spec)
                 t0 = time.time()
                 rc = run(bench + ["--load-state", state, "--steps", str(a.steps), "--warmup", "30",
-                                  "--no-cpu-baseline", "--profile"], env, f"{out}/{label}_{r}.json",
+                                  "--full", "--no-cpu-baseline", "--profile"], env, f"{out}/{label}_{r}.json",
                          f"{out}/{label}_{r}.err", 200)
                 if rc != 0:
                     sys.exit(f"{label} round {r} failed ({rc})")
