@@ -163,6 +163,71 @@ const char* kmc_kernel_name(int32_t id);
  * the current state). */
 int kmc_get_clusters(kmc_sim* s, int32_t* row_len, int32_t* members);
 
+/* Structure analysis of the CURRENT state — what kmc_get_state would return —
+ * computed on the device.  The calls work on any handle that
+ * has a state, straight after kmc_set_state / kmc_load_* included (no step
+ * needed, unlike kmc_get_clusters); they launch nothing inside kmc_step, read
+ * no step-internal table and leave the state, the step counter and
+ * kmc_get_clusters' validity untouched.  KMC_ERR_ARG for a null / out-of-range
+ * argument, a handle without state and a decomposed (kmc_dd_set_state) handle;
+ * KMC_ERR_STATE when a bond link leaves [0, n_a + n_b] or the links do not
+ * form finite chains (the device loops are bounded, they cannot hang).
+ *
+ * The bond graph: vertices are the n_a + n_b proteins; a receptor's edges are
+ * res_nei[.][2] (its ligand) and res_nei[.][3] (its cis partner), a ligand's
+ * res_nei[.][2..4] — the links the reference's BFS follows (main.cpp:543-551),
+ * but started from every protein, so receptor-only cis dimers are components
+ * too.
+ *   kmc_components       label[i-1] = the smallest reference index (1-based)
+ *                        in protein i's component; label may be NULL (the
+ *                        links are only checked).
+ *   kmc_oligomer_census  hist[r * (max_l+1) + l] = components with r receptors
+ *                        and l ligands, counts above max_r / max_l clamped
+ *                        into the last row / column, so the bins sum to
+ *                        n_components; hist may be NULL; at most
+ *                        KMC_CENSUS_MAX_BINS bins on the device.  A "complex"
+ *                        is the reference's cluster: at least one ligand and
+ *                        more than one protein (tot_cluster_num,
+ *                        tot_proteins_in_cluster of the NEXT step's record,
+ *                        whose BFS starts from this state, main.cpp:514-562).
+ *   kmc_pair_counts      lateral pair-distance histogram for g(r), species
+ *                        pair `which`.  A protein's position is (x, y) of its
+ *                        bead [1][1]; for a pair,
+ *                          dx = xi - xj; dx = dx - box_x * round(dx / box_x)
+ *                        (round half away from zero; the same in y),
+ *                          d2 = dx*dx + dy*dy        (no fused multiply-add)
+ *                        and with dr = r_max / nbins, edges2[m] = (m*dr)*(m*dr)
+ *                        in double, the pair falls into bin
+ *                          k = #{m in 1..nbins : edges2[m] <= d2}
+ *                        and is counted when k < nbins.  AA and BB count each
+ *                        unordered pair once, AB every (receptor, ligand)
+ *                        pair once.  floor(box / r_max) must be >= 3 along x
+ *                        and y, nbins <= KMC_PAIR_MAX_BINS.
+ *   kmc_host_census      the same labels, histogram and summary from a host
+ *                        state view, sequential, no device and no bin limit
+ *                        (label, hist may be NULL). */
+typedef struct kmc_census {
+  int64_t n_components;          /* every component, free monomers included */
+  int64_t n_complexes;           /* >= 1 ligand and size > 1 (the reference's "cluster") */
+  int64_t proteins_in_complexes;
+  int64_t n_cis_dimers;          /* receptor-only components of size 2 */
+  int32_t max_size, max_receptors, max_ligands, max_label; /* largest component; ties: smallest label */
+} kmc_census;
+#define KMC_PAIR_AA 0
+#define KMC_PAIR_AB 1
+#define KMC_PAIR_BB 2
+#define KMC_CENSUS_MAX_BINS 4096
+#define KMC_PAIR_MAX_BINS 4096
+int kmc_components(kmc_sim* s, int32_t* label);
+int kmc_oligomer_census(kmc_sim* s, int32_t max_r, int32_t max_l, int64_t* hist, kmc_census* out);
+int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int64_t* counts);
+int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t max_r, int32_t max_l,
+                    int64_t* hist, kmc_census* out);
+/* Device milliseconds of the last kmc_components / kmc_oligomer_census /
+ * kmc_pair_counts call: HIP events on the handle's stream around its kernels
+ * and clears (the result copies to the host excluded); 0 before the first. */
+double kmc_analysis_ms(const kmc_sim* s);
+
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */
 int kmc_format_bond_line(const kmc_params* p, const kmc_obs* o, char* buf, size_t n);   /* main.cpp:2251 */

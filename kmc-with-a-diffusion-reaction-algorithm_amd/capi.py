@@ -128,6 +128,29 @@ class StateView(C.Structure):
     ]
 
 
+class Census(C.Structure):
+    """kmc_census — summary of the bond graph's components (kmc_oligomer_census)."""
+
+    _fields_ = [
+        ("n_components", C.c_int64),
+        ("n_complexes", C.c_int64),
+        ("proteins_in_complexes", C.c_int64),
+        ("n_cis_dimers", C.c_int64),
+        ("max_size", C.c_int32),
+        ("max_receptors", C.c_int32),
+        ("max_ligands", C.c_int32),
+        ("max_label", C.c_int32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+PAIR_AA, PAIR_AB, PAIR_BB = 0, 1, 2   # KMC_PAIR_*
+PAIRS = {"AA": PAIR_AA, "AB": PAIR_AB, "BB": PAIR_BB}
+CENSUS_MAX_BINS = 4096                # KMC_CENSUS_MAX_BINS (device histogram)
+PAIR_MAX_BINS = 4096                  # KMC_PAIR_MAX_BINS
+
 DD_ROW = 416     # KMC_DD_ROW: one exchanged protein (48 doubles + 8 int32)
 DD_JCAP = 256    # KMC_DD_JCAP
 DD_XCAP = 64     # KMC_DD_XCAP

@@ -13,6 +13,7 @@
 #include "../../include/kmc.h"
 #include "kmc_host.h"
 #include "kmc_kernels.hip"
+#include "kmc_analysis.hip"
 
 using namespace kmcd;
 
@@ -136,6 +137,19 @@ struct kmc_sim {
   bool dd_step_pending = false;     // kmc_dd_step: pack + jumpers after the step's kernels
   unsigned char* dd_step_dst = nullptr;
   double dd_step_S = 0.0;
+  // structure analysis (kmc_analysis.hip): scratch of the first analysis call,
+  // none before it
+  int32_t *an_parent = nullptr, *an_label = nullptr;
+  unsigned long long *an_cnt = nullptr, *an_hist = nullptr;  // [N] packed member counts by root; [AN_HIST_MAX] bins
+  AnOut* an_out = nullptr;
+  int32_t *an_cell = nullptr, *an_rank = nullptr;              // [N] pair binning: cell and rank of each point
+  int32_t *an_ccnt = nullptr, *an_cstart = nullptr, *an_part = nullptr;  // [an_ccap] cell counts, their scan, tile sums
+  size_t an_ccap = 0;
+  double2* an_pts = nullptr;   // [N] (x, y) sorted by cell
+  double* an_edges = nullptr;  // [AN_HIST_MAX + 1] squared bin edges
+  int an_chunk = AN_CHUNK;     // KMC_DEBUG_PAIR_CHUNK: smaller staged chunks (the chunked path at test size)
+  hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
+  double an_ms = 0.0;
 };
 
 namespace {
@@ -440,6 +454,8 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
   s->debug_counts = dc && *dc == '1';
   const char* dsy = getenv("KMC_DEBUG_SYNC");
   s->debug_sync = dsy && *dsy == '1';
+  const char* pc = getenv("KMC_DEBUG_PAIR_CHUNK");  // debug: kmc_pair_counts stages fewer points at a time
+  if (pc && *pc) s->an_chunk = std::max(1, std::min(AN_CHUNK, atoi(pc)));
   // debug: lower the LDS tile capacity so that tiles take the global path
   const char* tc = getenv("KMC_DEBUG_TCAP");
   K.tcap = TCAP;
@@ -517,6 +533,8 @@ int kmc_destroy(kmc_sim* s) {
   for (auto& g : s->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   if (s->side) (void)hipStreamSynchronize(s->side);
+  for (auto& e : s->an_ev)
+    if (e) (void)hipEventDestroy(e);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
   if (s->ev_join) (void)hipEventDestroy(s->ev_join);
   if (s->side) (void)hipStreamDestroy(s->side);
@@ -2067,5 +2085,193 @@ int kmc_dd_counters(kmc_sim* s, int64_t* out) {
   out[1] = c.dd_xbond;
   return KMC_OK;
 }
+
+// ---------------------------------------------------------------- analysis
+// Read-only over the committed state (kmc_analysis.hip): nothing below writes
+// a buffer a step reads, so the trajectory, the step counter and
+// clusters_valid stay as they are.
+
+static int an_check(kmc_sim* s) {
+  if (!s->have_state) return fail(s, KMC_ERR_ARG, "analysis: no state");
+  if (s->K.dd) return fail(s, KMC_ERR_ARG, "analysis: a decomposed window is not analysed");
+  return KMC_OK;
+}
+
+// HIP events around one call's device work on the handle's stream
+static int an_begin(kmc_sim* s) {
+  for (auto& e : s->an_ev)
+    if (!e) HIPCHK(s, hipEventCreate(&e));
+  HIPCHK(s, hipEventRecord(s->an_ev[0], s->stream));
+  return KMC_OK;
+}
+static int an_end(kmc_sim* s) {
+  HIPCHK(s, hipEventRecord(s->an_ev[1], s->stream));
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  float ms = 0;
+  HIPCHK(s, hipEventElapsedTime(&ms, s->an_ev[0], s->an_ev[1]));
+  s->an_ms = ms;
+  return KMC_OK;
+}
+
+// labels (0-based roots, reference order) and the roots' member counts, left
+// on the device; the stream is not waited for
+static int an_components(kmc_sim* s) {
+  const int N = s->K.N, NA = s->K.NA;
+  if (!s->an_out) {
+    int rc = KMC_OK;
+    rc |= dalloc(s, &s->an_parent, (size_t)N);
+    rc |= dalloc(s, &s->an_label, (size_t)N);
+    rc |= dalloc(s, &s->an_cnt, (size_t)N);
+    if (!s->an_hist) rc |= dalloc(s, &s->an_hist, (size_t)AN_HIST_MAX);
+    rc |= dalloc(s, &s->an_out, 1);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "analysis: scratch allocation failed");
+  }
+  hipStream_t st = s->stream;
+  const unsigned g = (unsigned)((N + AN_T - 1) / AN_T);
+  HIPCHK(s, hipMemsetAsync(s->an_out, 0, sizeof(AnOut), st));
+  if (g) {
+    k_an_init<<<g, AN_T, 0, st>>>(s->an_parent, s->an_cnt, N);
+    k_an_hook<<<g, AN_T, 0, st>>>(s->K, s->d, s->an_parent, s->an_out);
+    k_an_flatten<<<g, AN_T, 0, st>>>(s->an_parent, s->an_label, N, s->an_out);
+    k_an_count<<<g, AN_T, 0, st>>>(s->an_label, s->an_cnt, NA, N);
+  }
+  HIPCHK(s, hipGetLastError());
+  return KMC_OK;
+}
+
+int kmc_components(kmc_sim* s, int32_t* label) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = an_components(s);
+  if (rc == KMC_OK) rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  AnOut o;
+  HIPCHK(s, hipMemcpy(&o, s->an_out, sizeof o, hipMemcpyDeviceToHost));
+  if (o.err) return fail(s, KMC_ERR_STATE, "analysis: a bond link leaves the state or the link chains do not end");
+  if (label) {
+    HIPCHK(s, hipMemcpy(label, s->an_label, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    for (int i = 0; i < N; ++i) label[i] += 1;
+  }
+  return KMC_OK;
+}
+
+int kmc_oligomer_census(kmc_sim* s, int32_t max_r, int32_t max_l, int64_t* hist, kmc_census* out) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out || max_r < 0 || max_l < 0) return fail(s, KMC_ERR_ARG, "census: out is needed, max_r and max_l >= 0");
+  const int64_t nbin = hist ? ((int64_t)max_r + 1) * ((int64_t)max_l + 1) : 0;
+  if (nbin > AN_HIST_MAX)
+    return fail(s, KMC_ERR_ARG, "census: more than " + std::to_string(AN_HIST_MAX) + " bins (larger counts clamp into the last row / column)");
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = an_components(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  hipStream_t st = s->stream;
+  if (nbin) HIPCHK(s, hipMemsetAsync(s->an_hist, 0, sizeof(unsigned long long) * (size_t)nbin, st));
+  const unsigned g = (unsigned)std::min<int64_t>(AN_WG_MAX, ((int64_t)N + AN_T - 1) / AN_T);
+  if (g)
+    k_an_census<<<g, AN_T, sizeof(unsigned long long) * (size_t)(nbin + 5), st>>>(
+        s->an_label, s->an_cnt, N, max_r, max_l, nbin ? s->an_hist : nullptr, s->an_out);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  AnOut o;
+  HIPCHK(s, hipMemcpy(&o, s->an_out, sizeof o, hipMemcpyDeviceToHost));
+  if (o.err) return fail(s, KMC_ERR_STATE, "analysis: a bond link leaves the state or the link chains do not end");
+  std::memset(out, 0, sizeof *out);
+  out->n_components = (int64_t)o.n_components;
+  out->n_complexes = (int64_t)o.n_complexes;
+  out->proteins_in_complexes = (int64_t)o.proteins_in_complexes;
+  out->n_cis_dimers = (int64_t)o.n_cis_dimers;
+  if (o.n_components) {
+    const uint32_t root = 0xffffffffu - (uint32_t)o.best;
+    unsigned long long c = 0;
+    HIPCHK(s, hipMemcpy(&c, s->an_cnt + root, sizeof c, hipMemcpyDeviceToHost));
+    out->max_size = (int32_t)(o.best >> 32);
+    out->max_receptors = (int32_t)(uint32_t)c;
+    out->max_ligands = (int32_t)(c >> 32);
+    out->max_label = (int32_t)root + 1;
+  }
+  if (nbin) HIPCHK(s, hipMemcpy(hist, s->an_hist, sizeof(int64_t) * (size_t)nbin, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int64_t* counts) {
+  if (!s) return KMC_ERR_ARG;
+  if (!counts || which < KMC_PAIR_AA || which > KMC_PAIR_BB || !(r_max > 0.0) || !std::isfinite(r_max) || nbins < 1 ||
+      nbins > AN_HIST_MAX)
+    return fail(s, KMC_ERR_ARG, "pair counts: which 0..2, r_max > 0, 1 <= nbins <= " + std::to_string(AN_HIST_MAX));
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const KParams& K = s->K;
+  const double fx = std::floor(K.box_x / r_max), fy = std::floor(K.box_y / r_max);
+  if (!(fx >= 3.0) || !(fy >= 3.0))
+    return fail(s, KMC_ERR_ARG, "pair counts: r_max above a third of the box (fewer than 3 cells along an axis)");
+  AnGrid G;
+  G.ncx = (int)std::min<double>(fx, AN_NC_MAX);
+  G.ncy = (int)std::min<double>(fy, AN_NC_MAX);
+  G.box_x = K.box_x;
+  G.box_y = K.box_y;
+  G.nsets = which == KMC_PAIR_AB ? 2 : 1;
+  G.lo[0] = which == KMC_PAIR_BB ? K.NA : 0;
+  G.hi[0] = which == KMC_PAIR_BB ? K.N : K.NA;
+  G.lo[1] = K.NA;
+  G.hi[1] = K.N;
+  const int N = K.N, ncell = G.ncx * G.ncy, npts = (G.hi[0] - G.lo[0]) + (G.nsets > 1 ? G.hi[1] - G.lo[1] : 0);
+  const size_t ncnt = (size_t)G.nsets * ncell + 1;  // the scan's last entry is the number of points
+  if (!s->an_pts) {
+    rc = KMC_OK;
+    rc |= dalloc(s, &s->an_cell, (size_t)N);
+    rc |= dalloc(s, &s->an_rank, (size_t)N);
+    rc |= dalloc(s, &s->an_pts, (size_t)N);
+    rc |= dalloc(s, &s->an_edges, (size_t)AN_HIST_MAX + 1);
+    if (!s->an_hist) rc |= dalloc(s, &s->an_hist, (size_t)AN_HIST_MAX);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "analysis: scratch allocation failed");
+  }
+  if (ncnt > s->an_ccap) {
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    dfree(s, s->an_ccnt);
+    dfree(s, s->an_cstart);
+    dfree(s, s->an_part);
+    s->an_ccap = 0;
+    rc = KMC_OK;
+    rc |= dalloc(s, &s->an_ccnt, ncnt);
+    rc |= dalloc(s, &s->an_cstart, ncnt);
+    rc |= dalloc(s, &s->an_part, (ncnt + SCAN_TILE - 1) / SCAN_TILE);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "analysis: scratch allocation failed");
+    s->an_ccap = ncnt;
+  }
+  // bin k holds edges2[k] <= d2 < edges2[k + 1], edges2[m] = (m dr)(m dr) in double
+  const double dr = r_max / nbins;
+  std::vector<double> edges2((size_t)nbins + 1);
+  for (int m = 0; m <= nbins; ++m) edges2[m] = (m * dr) * (m * dr);
+  hipStream_t st = s->stream;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpyAsync(s->an_edges, edges2.data(), sizeof(double) * edges2.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemsetAsync(s->an_hist, 0, sizeof(unsigned long long) * (size_t)nbins, st));
+  HIPCHK(s, hipMemsetAsync(s->an_ccnt, 0, sizeof(int32_t) * ncnt, st));
+  if (npts > 0) {
+    const unsigned g = (unsigned)((npts + AN_T - 1) / AN_T);
+    k_an_cell_count<<<g, AN_T, 0, st>>>(s->K, s->d, G, s->an_ccnt, s->an_cell, s->an_rank);
+    const int nb = (int)((ncnt + SCAN_TILE - 1) / SCAN_TILE);
+    k_scan_part<<<nb, 256, 0, st>>>(s->an_ccnt, (int)ncnt, s->an_part);
+    k_scan_top<<<1, 256, 0, st>>>(s->an_part, nb);
+    k_scan_down<<<nb, 256, 0, st>>>(s->an_ccnt, s->an_cstart, (int)ncnt, s->an_part);
+    k_an_cell_scatter<<<g, AN_T, 0, st>>>(s->K, s->d, G, s->an_cstart, s->an_cell, s->an_rank, s->an_pts);
+    const size_t lds = sizeof(unsigned long long) * (size_t)nbins + 2 * sizeof(double2) * (size_t)s->an_chunk;
+    k_an_pairs<<<(unsigned)std::min(ncell, AN_WG_MAX), AN_T, lds, st>>>(G, s->an_cstart, s->an_pts, s->an_edges, nbins,
+                                                                        (float)(1.0 / dr), s->an_chunk, s->an_hist);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);  // (waits: edges2 is read by the copy until here)
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpy(counts, s->an_hist, sizeof(int64_t) * (size_t)nbins, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+double kmc_analysis_ms(const kmc_sim* s) { return s ? s->an_ms : 0.0; }
 
 }  // extern "C"

@@ -667,6 +667,68 @@ int kmc_host_dd_check(int32_t n, const int32_t* gid, const uint8_t* own) {
   return kmch_host::dd_check(n, gid, own, &g_host_err);
 }
 
+// Components of the bond graph and their census (include/kmc.h), sequential:
+// a breadth-first walk from every protein not yet labelled, in index order,
+// so the walk's start is the component's smallest index — its label.
+int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t max_r, int32_t max_l,
+                    int64_t* hist, kmc_census* out) {
+  if (!p || !v || !out || !v->a_int || !v->b_int || p->n_a < 0 || p->n_b < 0 || max_r < 0 || max_l < 0) {
+    g_host_err = "census: params, state and out are needed, max_r and max_l >= 0";
+    return KMC_ERR_ARG;
+  }
+  const int na = p->n_a, nb = p->n_b, n = na + nb;
+  std::vector<int32_t> lab((size_t)n, 0), queue;
+  queue.reserve((size_t)n);
+  std::memset(out, 0, sizeof *out);
+  if (hist) std::fill(hist, hist + ((size_t)max_r + 1) * ((size_t)max_l + 1), (int64_t)0);
+  for (int r = 0; r < n; ++r) {
+    if (lab[r]) continue;
+    queue.clear();
+    queue.push_back(r);
+    lab[r] = r + 1;
+    int nr = 0, nl = 0;
+    for (size_t h = 0; h < queue.size(); ++h) {
+      const int q = queue[h];
+      int nei[3], m = 0;
+      if (q < na) {
+        ++nr;
+        nei[m++] = v->a_int[2 * (size_t)na + q];
+        nei[m++] = v->a_int[4 * (size_t)na + q];
+      } else {
+        ++nl;
+        for (int j = 2; j <= 4; ++j) nei[m++] = v->b_int[(size_t)(4 + j - 1) * nb + (q - na)];
+      }
+      for (int e = 0; e < m; ++e) {
+        if (nei[e] == 0) continue;
+        if (nei[e] < 1 || nei[e] > n) {
+          g_host_err = "census: a bond link of protein " + std::to_string(q + 1) + " leaves the state";
+          return KMC_ERR_STATE;
+        }
+        if (!lab[nei[e] - 1]) {
+          lab[nei[e] - 1] = r + 1;
+          queue.push_back(nei[e] - 1);
+        }
+      }
+    }
+    const int size = nr + nl;
+    out->n_components += 1;
+    if (nl >= 1 && size > 1) {
+      out->n_complexes += 1;
+      out->proteins_in_complexes += size;
+    }
+    if (nl == 0 && nr == 2) out->n_cis_dimers += 1;
+    if (size > out->max_size) {  // (components come in label order: the first of a size keeps the tie)
+      out->max_size = size;
+      out->max_receptors = nr;
+      out->max_ligands = nl;
+      out->max_label = r + 1;
+    }
+    if (hist) hist[(size_t)std::min(nr, (int)max_r) * ((size_t)max_l + 1) + std::min(nl, (int)max_l)] += 1;
+  }
+  if (label) std::copy(lab.begin(), lab.end(), label);
+  return KMC_OK;
+}
+
 int kmc_host_math(int op, const double* x, const double* y, double* out, int64_t n) {
   for (int64_t i = 0; i < n; ++i) {
     double a = x[i], b = y[i], r = 0;

@@ -17,6 +17,12 @@
 //           [--state FILE]   exact checkpoint (include/kmc.h, KMCSTAT1): resumed
 //                            from when it exists (instead of position.cpt) and
 //                            rewritten with position.cpt every out_interval
+//           [--census FILE]  every out_interval, one line per non-empty bin of the
+//                            oligomer census (kmc_oligomer_census): step n_r n_l count
+//           [--rdf WHICH RMAX NBINS FILE]  every out_interval, the lateral pair counts
+//                            (kmc_pair_counts; WHICH = AA, AB or BB): step k count
+//                            (both appended; truncated on a fresh start, like bond.dat;
+//                            census bins clamp at 63 receptors / 63 ligands)
 #include <sys/stat.h>
 
 #include <cstdio>
@@ -69,7 +75,9 @@ int main(int argc, char** argv) {
   kmc_params p;
   kmc_params_default(&p);
   int device = 0;
-  std::string state_path;
+  std::string state_path, census_path, rdf_path;
+  int rdf_which = -1, rdf_nbins = 0;
+  double rdf_rmax = 0.0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -91,6 +99,18 @@ int main(int argc, char** argv) {
     else if (a == "--replica") p.replica = (uint32_t)atoi(next().c_str());
     else if (a == "--device") device = atoi(next().c_str());
     else if (a == "--state") state_path = next();
+    else if (a == "--census") census_path = next();
+    else if (a == "--rdf") {
+      const std::string w = next();
+      rdf_which = w == "AA" ? KMC_PAIR_AA : w == "AB" ? KMC_PAIR_AB : w == "BB" ? KMC_PAIR_BB : -1;
+      rdf_rmax = atof(next().c_str());
+      rdf_nbins = atoi(next().c_str());
+      rdf_path = next();
+      if (rdf_which < 0 || !(rdf_rmax > 0.0) || rdf_nbins < 1 || rdf_nbins > KMC_PAIR_MAX_BINS) {
+        fprintf(stderr, "kmc_run: bad --rdf %s %g %d\n", w.c_str(), rdf_rmax, rdf_nbins);
+        return 2;
+      }
+    }
     else if (a == "--set") {
       std::string kv = next();
       size_t eq = kv.find('=');
@@ -124,6 +144,8 @@ int main(int argc, char** argv) {
     truncate("bond.dat");
     truncate("cluster.log");
     truncate("position.cpt");
+    if (!census_path.empty()) truncate(census_path.c_str());
+    if (!rdf_path.empty()) truncate(rdf_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
   }
@@ -135,6 +157,8 @@ int main(int argc, char** argv) {
       mem((size_t)na + nb + 1);
   kmc_state_view v{ra.data(), rb.data(), ai.data(), bi.data(), {0, 0, 0, 0, 0}, 0, 0};
   std::vector<kmc_obs> obs;
+  const int census_max = 63;  // census rows / columns: 0..63 receptors / ligands, more clamp into the last
+  std::vector<int64_t> hist((size_t)(census_max + 1) * (census_max + 1)), pairs((size_t)rdf_nbins + 1);
   int64_t step = kmc_current_step(s);
   while (step < p.simu_step) {
     int64_t next_out = (step / p.out_interval + 1) * p.out_interval;
@@ -165,6 +189,26 @@ int main(int argc, char** argv) {
       if (rc) return die(s, rc, "clusters");
       rc = kmc_host_append_cluster_log(&p, step, row.data(), mem.data(), "cluster.log");
       if (rc) return die(s, rc, "cluster.log");
+      if (!census_path.empty()) {
+        kmc_census cs;
+        rc = kmc_oligomer_census(s, census_max, census_max, hist.data(), &cs);
+        if (rc) return die(s, rc, "census");
+        f = fopen(census_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, census_path.c_str());
+        for (int r = 0; r <= census_max; ++r)
+          for (int l = 0; l <= census_max; ++l)
+            if (hist[(size_t)r * (census_max + 1) + l])
+              fprintf(f, "%lld %d %d %lld\n", (long long)step, r, l, (long long)hist[(size_t)r * (census_max + 1) + l]);
+        fclose(f);
+      }
+      if (!rdf_path.empty()) {
+        rc = kmc_pair_counts(s, rdf_which, rdf_rmax, rdf_nbins, pairs.data());
+        if (rc) return die(s, rc, "pair counts");
+        f = fopen(rdf_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, rdf_path.c_str());
+        for (int k = 0; k < rdf_nbins; ++k) fprintf(f, "%lld %d %lld\n", (long long)step, k, (long long)pairs[k]);
+        fclose(f);
+      }
     }
   }
   kmc_destroy(s);

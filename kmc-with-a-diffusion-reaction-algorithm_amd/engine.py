@@ -92,6 +92,13 @@ def load_library(path: Optional[str] = None):
     L.kmc_dd_cut_count.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, P(C.c_int32)]
     L.kmc_list_growth.argtypes = [C.c_void_p]
     L.kmc_set_list_growth.argtypes = [C.c_void_p, C.c_int32]
+    L.kmc_components.argtypes = [C.c_void_p, C.c_void_p]
+    L.kmc_oligomer_census.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, P(capi.Census)]
+    L.kmc_pair_counts.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p]
+    L.kmc_host_census.argtypes = [P(capi.Params), P(capi.StateView), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                  P(capi.Census)]
+    L.kmc_analysis_ms.restype = C.c_double
+    L.kmc_analysis_ms.argtypes = [C.c_void_p]
     for f in ("kmc_host_math", "kmc_device_math"):
         getattr(L, f).argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
@@ -146,6 +153,18 @@ def host_load_state(params: capi.Params, path: str) -> capi.HostState:
 def host_validate(params: capi.Params, hs: capi.HostState) -> int:
     v = hs.view()
     return int(load_library().kmc_host_validate(C.byref(params), C.byref(v)))
+
+
+def host_census(params: capi.Params, hs: capi.HostState, max_r: int, max_l: int):
+    """Components of a host state's bond graph, sequentially (kmc_host_census):
+    (label[n_a + n_b] 1-based, hist[max_r + 1, max_l + 1] int64, capi.Census)."""
+    label = np.zeros(params.n_a + params.n_b, dtype=np.int32)
+    hist = np.zeros((max_r + 1, max_l + 1), dtype=np.int64)
+    out = capi.Census()
+    v = hs.view()
+    _host_check(load_library().kmc_host_census(C.byref(params), C.byref(v), label.ctypes.data, max_r, max_l,
+                                               hist.ctypes.data, C.byref(out)))
+    return label, hist, out
 
 
 def host_dd_check(gid: np.ndarray, own: np.ndarray) -> int:
@@ -282,6 +301,37 @@ class Simulation:
         mem = np.zeros(self.params.n_a + self.params.n_b, dtype=np.int32)
         self._check(load_library().kmc_get_clusters(self._h, row.ctypes.data, mem.ctypes.data))
         return row, mem[: int(row.sum())]
+
+    # ---- structure analysis of the current state (kmc_analysis.hip; works before any step)
+    def components(self) -> np.ndarray:
+        """label[i] = smallest reference index (1-based) in protein i+1's bond-graph component."""
+        label = np.zeros(self.params.n_a + self.params.n_b, dtype=np.int32)
+        self._check(load_library().kmc_components(self._h, label.ctypes.data))
+        return label
+
+    def census(self, max_r: int, max_l: int):
+        """(hist[max_r + 1, max_l + 1] int64 of components by (receptors, ligands), larger counts clamped
+        into the last row / column; capi.Census summary) — kmc_oligomer_census."""
+        if max_r < 0 or max_l < 0:
+            raise ValueError("census: max_r, max_l >= 0")
+        hist = np.zeros((max_r + 1, max_l + 1), dtype=np.int64)
+        out = capi.Census()
+        self._check(load_library().kmc_oligomer_census(self._h, max_r, max_l, hist.ctypes.data, C.byref(out)))
+        return hist, out
+
+    def pair_counts(self, which, r_max: float, nbins: int) -> np.ndarray:
+        """Lateral pair-distance counts[nbins] (int64) of species pair `which` ("AA", "AB", "BB" or
+        capi.PAIR_*) below r_max — kmc_pair_counts; analysis.rdf turns them into g(r)."""
+        which = capi.PAIRS.get(which, which) if isinstance(which, str) else which
+        counts = np.zeros(max(int(nbins), 1), dtype=np.int64)
+        self._check(load_library().kmc_pair_counts(self._h, int(which), float(r_max), int(nbins),
+                                                   counts.ctypes.data))
+        return counts
+
+    @property
+    def analysis_ms(self) -> float:
+        """Device milliseconds (HIP events) of the last components / census / pair_counts call."""
+        return float(load_library().kmc_analysis_ms(self._h))
 
     @property
     def current_step(self) -> int:
