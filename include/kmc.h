@@ -224,9 +224,99 @@ int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int6
 int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t max_r, int32_t max_l,
                     int64_t* hist, kmc_census* out);
 /* Device milliseconds of the last kmc_components / kmc_oligomer_census /
- * kmc_pair_counts call: HIP events on the handle's stream around its kernels
- * and clears (the result copies to the host excluded); 0 before the first. */
+ * kmc_pair_counts / kmc_track_* call: HIP events on the handle's stream around
+ * its kernels and clears (the result copies to the host excluded); 0 before
+ * the first. */
 double kmc_analysis_ms(const kmc_sim* s);
+
+/* Displacement tracking: unwrapped displacements since a time
+ * origin, for the mean-squared displacement and the self part of the van Hove
+ * function, and the survival of the bonds that existed at the origin.  Like
+ * the structure analysis the calls read the CURRENT state, launch nothing
+ * inside kmc_step and leave the state, the step counter and kmc_get_clusters'
+ * validity untouched; the caller places kmc_track_update between kmc_step
+ * calls (kmc_step may replay steps internally, and slots are re-sorted: the
+ * tracker is a layer of its own, indexed by reference index i = 0..N-1,
+ * receptors first, then ligands).  A protein's position is (x, y) of its bead
+ * [1][1], as in kmc_pair_counts.  One origin per handle.
+ *
+ *   kmc_track_begin   the current state becomes the origin: per protein
+ *                     prev = position, u = (0, 0), flags = 0, the origin links
+ *                     as reference indices (receptor: nei2, nei4, nei3; ligand:
+ *                     nei2..4) and the origin class.  max_jump <= 0 means
+ *                     min(box_x, box_y) / 4, else 0 < max_jump <= min(box) / 2.
+ *                     Scratch is allocated by the first call, freed by
+ *                     kmc_track_end / kmc_destroy.
+ *   classes           0 receptor with nei2 == 0 and nei3 == 0 (free)
+ *                     1 receptor with nei2 == 0 and nei3 != 0 (cis only)
+ *                     2 receptor with nei2 != 0 (bound to a ligand)
+ *                     3 ligand without a link     4 ligand with a link
+ *                     — fixed at the origin.
+ *   kmc_track_update  per protein, in double, no fused multiply-add:
+ *                       dx = x - prev.x; dx = dx - box_x * round(dx / box_x)
+ *                     (round half away from zero; the same in y),
+ *                       u.x = u.x + dx; u.y = u.y + dy; prev = (x, y);
+ *                     flags |= 2 ("jumped") when |dx| >= max_jump or |dy| >=
+ *                     max_jump; flags |= 1 ("changed") when a current link (as
+ *                     a reference index) or the receptor's nei4 differs from
+ *                     the origin's.  Both bits are sticky.  info (may be NULL)
+ *                     receives the steps, the number of updates, the largest
+ *                     |dx| and |dy| of any update since begin, and how many
+ *                     proteins carry each bit.  A second call at the same step
+ *                     adds d = 0.
+ *                     CAVEAT: a large minimum-image displacement is not an
+ *                     error.  The model moves a cis dimer or a complex that
+ *                     wraps around the box by up to sqrt(rot_D * time_step) * L
+ *                     tangentially in that one step, far more
+ *                     than diffusion does; such proteins are flagged "jumped"
+ *                     and left out of the clean sums.
+ *   kmc_track_sample  read-only over the tracker as of the last update.  With
+ *                     q[i] = u.x*u.x + u.y*u.y: per class n, n_clean (flags ==
+ *                     0), sum_u2 and sum_u2_clean; the survival counters — R–L
+ *                     bonds counted at the receptor: rl0 (origin nei2 != 0),
+ *                     rl_now (the current nei2 and nei4 equal the origin's),
+ *                     rl_kept (they did at every update so far); cis bonds at
+ *                     the lower-index receptor: cis0, cis_now, cis_kept (nei3).
+ *                     The ten double sums are defined bit for bit: the term of
+ *                     protein i is q[i] if it belongs to the sum's set, else
+ *                     0.0; the vector is padded with 0.0 to a multiple of 256;
+ *                     each block of 256 is reduced by the halving tree — for
+ *                     h = 128, 64, ..., 1: t[j] = t[j] + t[j + h] for j < h —
+ *                     and the block results form the next vector, until one
+ *                     value is left.
+ *                     vanhove (may be NULL) [KMC_TRACK_CLASSES][nbins]: the
+ *                     clean members of each class by q, with kmc_pair_counts'
+ *                     bin rule: dr = r_max / nbins, edges2[m] = (m*dr)*(m*dr),
+ *                     k = #{m in 1..nbins : edges2[m] <= q}, counted when
+ *                     k < nbins; 1 <= nbins <= KMC_TRACK_MAX_BINS, r_max > 0.
+ *   kmc_track_displacements  u as ux[N] then uy[N], and the flags (may be
+ *                     NULL): diagnostics and tests.
+ *   kmc_track_end     drops the tracker and frees its scratch.
+ * KMC_ERR_ARG for a null / out-of-range argument, a handle without state, a
+ * decomposed window and a tracker that was not begun; kmc_set_state,
+ * kmc_load_*, kmc_init_random and kmc_dd_set_state drop the tracker (its
+ * origin described another state). */
+#define KMC_TRACK_CLASSES 5
+#define KMC_TRACK_MAX_BINS 512
+#define KMC_TRACK_CHANGED 1
+#define KMC_TRACK_JUMPED 2
+typedef struct kmc_track_info {
+  int64_t origin_step, last_step; /* step of kmc_track_begin / of the last update */
+  int64_t n_updates;
+  double max_dx, max_dy;          /* largest |dx|, |dy| of one update since begin */
+  int64_t n_jumped, n_changed;    /* proteins carrying the bit now */
+} kmc_track_info;
+typedef struct kmc_track_sample_t {
+  int64_t origin_step, last_step;
+  int64_t n[KMC_TRACK_CLASSES], n_clean[KMC_TRACK_CLASSES];
+  double sum_u2[KMC_TRACK_CLASSES], sum_u2_clean[KMC_TRACK_CLASSES];
+  int64_t rl0, rl_now, rl_kept, cis0, cis_now, cis_kept;
+} kmc_track_sample_t;
+int kmc_track_begin(kmc_sim* s, double max_jump);
+int kmc_track_update(kmc_sim* s, kmc_track_info* info);
+int kmc_track_sample(kmc_sim* s, double r_max, int32_t nbins, kmc_track_sample_t* out, int64_t* vanhove);
+int kmc_track_displacements(kmc_sim* s, double* u, uint8_t* flags);
+int kmc_track_end(kmc_sim* s);
 
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */

@@ -151,6 +151,60 @@ PAIRS = {"AA": PAIR_AA, "AB": PAIR_AB, "BB": PAIR_BB}
 CENSUS_MAX_BINS = 4096                # KMC_CENSUS_MAX_BINS (device histogram)
 PAIR_MAX_BINS = 4096                  # KMC_PAIR_MAX_BINS
 
+TRACK_CLASSES = 5                     # KMC_TRACK_CLASSES
+TRACK_MAX_BINS = 512                  # KMC_TRACK_MAX_BINS
+TRACK_CHANGED, TRACK_JUMPED = 1, 2    # KMC_TRACK_CHANGED / KMC_TRACK_JUMPED (flag bits)
+
+
+class TrackInfo(C.Structure):
+    """kmc_track_info — what kmc_track_update reports."""
+
+    _fields_ = [
+        ("origin_step", C.c_int64),
+        ("last_step", C.c_int64),
+        ("n_updates", C.c_int64),
+        ("max_dx", C.c_double),
+        ("max_dy", C.c_double),
+        ("n_jumped", C.c_int64),
+        ("n_changed", C.c_int64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class TrackSample(C.Structure):
+    """kmc_track_sample_t — per-class counts and sums of squared displacements, bond survival."""
+
+    _fields_ = [
+        ("origin_step", C.c_int64),
+        ("last_step", C.c_int64),
+        ("n", C.c_int64 * TRACK_CLASSES),
+        ("n_clean", C.c_int64 * TRACK_CLASSES),
+        ("sum_u2", C.c_double * TRACK_CLASSES),
+        ("sum_u2_clean", C.c_double * TRACK_CLASSES),
+        ("rl0", C.c_int64),
+        ("rl_now", C.c_int64),
+        ("rl_kept", C.c_int64),
+        ("cis0", C.c_int64),
+        ("cis_now", C.c_int64),
+        ("cis_kept", C.c_int64),
+    ]
+
+    SURVIVAL = ("rl0", "rl_now", "rl_kept", "cis0", "cis_now", "cis_kept")
+
+    def as_dict(self) -> dict:
+        """Plain Python / numpy values: the arrays as int64 / float64 numpy arrays."""
+        d = {"origin_step": int(self.origin_step), "last_step": int(self.last_step)}
+        for k in ("n", "n_clean"):
+            d[k] = np.array(list(getattr(self, k)), dtype=np.int64)
+        for k in ("sum_u2", "sum_u2_clean"):
+            d[k] = np.array(list(getattr(self, k)), dtype=np.float64)
+        for k in self.SURVIVAL:
+            d[k] = int(getattr(self, k))
+        return d
+
+
 DD_ROW = 416     # KMC_DD_ROW: one exchanged protein (48 doubles + 8 int32)
 DD_JCAP = 256    # KMC_DD_JCAP
 DD_XCAP = 64     # KMC_DD_XCAP

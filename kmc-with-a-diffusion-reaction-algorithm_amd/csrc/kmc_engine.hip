@@ -14,6 +14,7 @@
 #include "kmc_host.h"
 #include "kmc_kernels.hip"
 #include "kmc_analysis.hip"
+#include "kmc_dynamics.hip"
 
 using namespace kmcd;
 
@@ -150,6 +151,18 @@ struct kmc_sim {
   int an_chunk = AN_CHUNK;     // KMC_DEBUG_PAIR_CHUNK: smaller staged chunks (the chunked path at test size)
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   double an_ms = 0.0;
+  // displacement tracking (kmc_dynamics.hip): scratch of the first
+  // kmc_track_begin, none before it; trk_on: an origin is set (a new state
+  // drops it)
+  bool trk_on = false;
+  Trk trk = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  TrkAcc* trk_acc = nullptr;
+  TrkOut* trk_out = nullptr;
+  double *trk_part[2] = {nullptr, nullptr};  // the reduction tree's levels, ping-pong
+  double* trk_edges = nullptr;               // [TRK_BINS_MAX + 1] squared bin edges
+  unsigned long long* trk_vh = nullptr;      // [TRK_CLASSES][TRK_BINS_MAX] van Hove bins
+  double trk_max_jump = 0.0;
+  int64_t trk_origin = 0, trk_last = 0, trk_updates = 0;
 };
 
 namespace {
@@ -827,6 +840,7 @@ static int set_state_impl(kmc_sim* s, const kmc_state_view* v) {
   s->need_full = true;
   s->clusters_valid = false;
   s->snap_valid = false;
+  s->trk_on = false;  // the tracker's origin described another state
   return KMC_OK;
 }
 
@@ -2273,5 +2287,187 @@ int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int6
 }
 
 double kmc_analysis_ms(const kmc_sim* s) { return s ? s->an_ms : 0.0; }
+
+// ---------------------------------------------------------------- displacement tracking
+// kmc_dynamics.hip: the tracker is a layer of its own over the committed
+// state; its calls write only the trk_* buffers.
+
+static int trk_check(kmc_sim* s) {
+  const int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  if (!s->trk_on) return fail(s, KMC_ERR_ARG, "track: no origin (kmc_track_begin; a new state drops the tracker)");
+  return KMC_OK;
+}
+
+static void trk_free(kmc_sim* s) {
+  dfree(s, s->trk.prev);
+  dfree(s, s->trk.u);
+  dfree(s, s->trk.flags);
+  dfree(s, s->trk.cls);
+  dfree(s, s->trk.link0);
+  dfree(s, s->trk_acc);
+  dfree(s, s->trk_out);
+  dfree(s, s->trk_part[0]);
+  dfree(s, s->trk_part[1]);
+  dfree(s, s->trk_edges);
+  dfree(s, s->trk_vh);
+}
+
+int kmc_track_begin(kmc_sim* s, double max_jump) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const double half = 0.5 * std::min(s->K.box_x, s->K.box_y);
+  if (!(max_jump <= 0.0) && !(max_jump <= half))  // (a NaN fails both)
+    return fail(s, KMC_ERR_ARG, "track: max_jump above half the box (or not a number)");
+  const int N = s->K.N;
+  if (!s->trk_acc) {
+    const size_t nblk = ((size_t)N + TRK_T - 1) / TRK_T;
+    rc = KMC_OK;
+    rc |= dalloc(s, &s->trk.prev, (size_t)N);
+    rc |= dalloc(s, &s->trk.u, (size_t)N);
+    rc |= dalloc(s, &s->trk.flags, (size_t)N);
+    rc |= dalloc(s, &s->trk.cls, (size_t)N);
+    rc |= dalloc(s, &s->trk.link0, 3 * (size_t)N);
+    rc |= dalloc(s, &s->trk_out, 1);
+    rc |= dalloc(s, &s->trk_part[0], TRK_NSUM * nblk);
+    rc |= dalloc(s, &s->trk_part[1], TRK_NSUM * ((nblk + TRK_T - 1) / TRK_T));
+    rc |= dalloc(s, &s->trk_edges, (size_t)TRK_BINS_MAX + 1);
+    rc |= dalloc(s, &s->trk_vh, (size_t)TRK_CLASSES * TRK_BINS_MAX);
+    rc |= dalloc(s, &s->trk_acc, 1);
+    if (rc != KMC_OK) {
+      trk_free(s);
+      return fail(s, KMC_ERR_HIP, "track: scratch allocation failed");
+    }
+  }
+  s->trk_on = false;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemsetAsync(s->trk_acc, 0, sizeof(TrkAcc), s->stream));
+  if (N > 0) k_trk_begin<<<(unsigned)((N + TRK_T - 1) / TRK_T), TRK_T, 0, s->stream>>>(s->K, s->d, s->trk);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  s->trk_max_jump = max_jump <= 0.0 ? 0.5 * half : max_jump;
+  s->trk_origin = s->trk_last = s->step_done;
+  s->trk_updates = 0;
+  s->trk_on = true;
+  return KMC_OK;
+}
+
+int kmc_track_update(kmc_sim* s, kmc_track_info* info) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = trk_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  // the maxima persist since begin; the flag counts are of this update
+  HIPCHK(s, hipMemsetAsync(&s->trk_acc->n_jumped, 0, 2 * sizeof(unsigned long long), s->stream));
+  if (N > 0)
+    k_trk_update<<<(unsigned)((N + TRK_T - 1) / TRK_T), TRK_T, 0, s->stream>>>(s->K, s->d, s->trk, s->trk_max_jump,
+                                                                             s->trk_acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  s->trk_last = s->step_done;
+  s->trk_updates += 1;
+  if (info) {
+    TrkAcc a;
+    HIPCHK(s, hipMemcpy(&a, s->trk_acc, sizeof a, hipMemcpyDeviceToHost));
+    info->origin_step = s->trk_origin;
+    info->last_step = s->trk_last;
+    info->n_updates = s->trk_updates;
+    std::memcpy(&info->max_dx, &a.max_dx, sizeof(double));
+    std::memcpy(&info->max_dy, &a.max_dy, sizeof(double));
+    info->n_jumped = (int64_t)a.n_jumped;
+    info->n_changed = (int64_t)a.n_changed;
+  }
+  return KMC_OK;
+}
+
+int kmc_track_sample(kmc_sim* s, double r_max, int32_t nbins, kmc_track_sample_t* out, int64_t* vanhove) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out || !(r_max > 0.0) || !std::isfinite(r_max) || nbins < 1 || nbins > TRK_BINS_MAX)
+    return fail(s, KMC_ERR_ARG, "track sample: out is needed, r_max > 0, 1 <= nbins <= " + std::to_string(TRK_BINS_MAX));
+  int rc = trk_check(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  const double dr = r_max / nbins;
+  std::vector<double> edges2((size_t)nbins + 1);
+  for (int m = 0; m <= nbins; ++m) edges2[m] = (m * dr) * (m * dr);
+  hipStream_t st = s->stream;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpyAsync(s->trk_edges, edges2.data(), sizeof(double) * edges2.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemsetAsync(s->trk_out, 0, sizeof(TrkOut), st));
+  if (vanhove) HIPCHK(s, hipMemsetAsync(s->trk_vh, 0, sizeof(unsigned long long) * TRK_CLASSES * (size_t)nbins, st));
+  // level 1: blocks of 256 proteins -> part[0][s][nblk]; then the tree's next levels until one value per sum
+  int n = (N + TRK_T - 1) / TRK_T, cur = 0;
+  if (n > 0) {
+    const size_t lds = sizeof(unsigned long long) * (size_t)(TRK_NSUM * TRK_T + TRK_NCNT + (vanhove ? TRK_CLASSES * nbins : 0));
+    k_trk_sample<<<(unsigned)std::min(n, AN_WG_MAX), TRK_T, lds, st>>>(s->K, s->d, s->trk, s->trk_edges, nbins,
+                                                                      (float)(1.0 / dr), vanhove ? s->trk_vh : nullptr, n,
+                                                                      s->trk_part[0], s->trk_out);
+    while (n > 1) {
+      const int nout = (n + TRK_T - 1) / TRK_T;
+      k_trk_tree<<<dim3((unsigned)nout, TRK_NSUM), TRK_T, 0, st>>>(s->trk_part[cur], n, s->trk_part[cur ^ 1], nout);
+      n = nout;
+      cur ^= 1;
+    }
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);  // (waits: edges2 is read by the copy until here)
+  if (rc != KMC_OK) return rc;
+  TrkOut o;
+  double sums[TRK_NSUM] = {0};
+  HIPCHK(s, hipMemcpy(&o, s->trk_out, sizeof o, hipMemcpyDeviceToHost));
+  if (n == 1) HIPCHK(s, hipMemcpy(sums, s->trk_part[cur], sizeof sums, hipMemcpyDeviceToHost));
+  std::memset(out, 0, sizeof *out);
+  out->origin_step = s->trk_origin;
+  out->last_step = s->trk_last;
+  for (int c = 0; c < TRK_CLASSES; ++c) {
+    out->n[c] = (int64_t)o.cnt[c];
+    out->n_clean[c] = (int64_t)o.cnt[TRK_CLASSES + c];
+    out->sum_u2[c] = sums[c];
+    out->sum_u2_clean[c] = sums[TRK_CLASSES + c];
+  }
+  out->rl0 = (int64_t)o.cnt[10];
+  out->rl_now = (int64_t)o.cnt[11];
+  out->rl_kept = (int64_t)o.cnt[12];
+  out->cis0 = (int64_t)o.cnt[13];
+  out->cis_now = (int64_t)o.cnt[14];
+  out->cis_kept = (int64_t)o.cnt[15];
+  if (vanhove)
+    HIPCHK(s, hipMemcpy(vanhove, s->trk_vh, sizeof(int64_t) * TRK_CLASSES * (size_t)nbins, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_track_displacements(kmc_sim* s, double* u, uint8_t* flags) {
+  if (!s) return KMC_ERR_ARG;
+  if (!u) return fail(s, KMC_ERR_ARG, "track displacements: u is needed");
+  const int rc = trk_check(s);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  std::vector<double2> h(N);
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  HIPCHK(s, hipMemcpy(h.data(), s->trk.u, sizeof(double2) * N, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < N; ++i) {
+    u[i] = h[i].x;
+    u[N + i] = h[i].y;
+  }
+  if (flags) {
+    HIPCHK(s, hipMemcpy(flags, s->trk.flags, N, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N; ++i) flags[i] &= (uint8_t)(KMC_TRACK_CHANGED | KMC_TRACK_JUMPED);
+  }
+  return KMC_OK;
+}
+
+int kmc_track_end(kmc_sim* s) {
+  if (!s) return KMC_ERR_ARG;
+  if (s->stream) HIPCHK(s, hipStreamSynchronize(s->stream));
+  trk_free(s);
+  s->trk_on = false;
+  return KMC_OK;
+}
 
 }  // extern "C"

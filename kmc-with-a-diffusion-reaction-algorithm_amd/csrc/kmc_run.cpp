@@ -23,6 +23,14 @@
 //                            (kmc_pair_counts; WHICH = AA, AB or BB): step k count
 //                            (both appended; truncated on a fresh start, like bond.dat;
 //                            census bins clamp at 63 receptors / 63 ligands)
+//           [--dyn EVERY RMAX NBINS FILE]  displacement tracking (kmc_track_*): the origin is
+//                            the state the process starts or resumes from (the tracker is
+//                            not checkpointed: a resume starts a new origin, every line
+//                            carries it); kmc_step runs in pieces of at most EVERY steps
+//                            with an update after each; every out_interval FILE gets
+//                              msd step origin class n n_clean sum_u2 sum_u2_clean
+//                              surv step origin rl0 rl_now rl_kept cis0 cis_now cis_kept
+//                              vh step class k count        (non-empty van Hove bins)
 #include <sys/stat.h>
 
 #include <cstdio>
@@ -75,9 +83,10 @@ int main(int argc, char** argv) {
   kmc_params p;
   kmc_params_default(&p);
   int device = 0;
-  std::string state_path, census_path, rdf_path;
-  int rdf_which = -1, rdf_nbins = 0;
-  double rdf_rmax = 0.0;
+  std::string state_path, census_path, rdf_path, dyn_path;
+  int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0;
+  double rdf_rmax = 0.0, dyn_rmax = 0.0;
+  int64_t dyn_every = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -108,6 +117,16 @@ int main(int argc, char** argv) {
       rdf_path = next();
       if (rdf_which < 0 || !(rdf_rmax > 0.0) || rdf_nbins < 1 || rdf_nbins > KMC_PAIR_MAX_BINS) {
         fprintf(stderr, "kmc_run: bad --rdf %s %g %d\n", w.c_str(), rdf_rmax, rdf_nbins);
+        return 2;
+      }
+    }
+    else if (a == "--dyn") {
+      dyn_every = atoll(next().c_str());
+      dyn_rmax = atof(next().c_str());
+      dyn_nbins = atoi(next().c_str());
+      dyn_path = next();
+      if (dyn_every < 1 || !(dyn_rmax > 0.0) || dyn_nbins < 1 || dyn_nbins > KMC_TRACK_MAX_BINS) {
+        fprintf(stderr, "kmc_run: bad --dyn %lld %g %d\n", (long long)dyn_every, dyn_rmax, dyn_nbins);
         return 2;
       }
     }
@@ -146,6 +165,7 @@ int main(int argc, char** argv) {
     truncate("position.cpt");
     if (!census_path.empty()) truncate(census_path.c_str());
     if (!rdf_path.empty()) truncate(rdf_path.c_str());
+    if (!dyn_path.empty()) truncate(dyn_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
   }
@@ -159,14 +179,30 @@ int main(int argc, char** argv) {
   std::vector<kmc_obs> obs;
   const int census_max = 63;  // census rows / columns: 0..63 receptors / ligands, more clamp into the last
   std::vector<int64_t> hist((size_t)(census_max + 1) * (census_max + 1)), pairs((size_t)rdf_nbins + 1);
+  std::vector<int64_t> vh((size_t)KMC_TRACK_CLASSES * dyn_nbins + 1);
+  if (!dyn_path.empty()) {
+    rc = kmc_track_begin(s, 0.0);
+    if (rc) return die(s, rc, "track begin");
+  }
   int64_t step = kmc_current_step(s);
   while (step < p.simu_step) {
     int64_t next_out = (step / p.out_interval + 1) * p.out_interval;
     int64_t end = next_out < p.simu_step ? next_out : p.simu_step;
     int64_t n = end - step;
     obs.resize((size_t)n);
-    rc = kmc_step(s, n, obs.data());
-    if (rc) return die(s, rc, "kmc_step");
+    if (dyn_path.empty()) {
+      rc = kmc_step(s, n, obs.data());
+      if (rc) return die(s, rc, "kmc_step");
+    } else {
+      for (int64_t done = 0; done < n;) {
+        const int64_t m = n - done < dyn_every ? n - done : dyn_every;
+        rc = kmc_step(s, m, obs.data() + done);
+        if (rc) return die(s, rc, "kmc_step");
+        rc = kmc_track_update(s, nullptr);
+        if (rc) return die(s, rc, "track update");
+        done += m;
+      }
+    }
     step = end;
     if (step % p.out_interval == 0) {
       rc = kmc_write_cpt(s, "position.cpt");
@@ -207,6 +243,25 @@ int main(int argc, char** argv) {
         f = fopen(rdf_path.c_str(), "ab");
         if (!f) return die(s, KMC_ERR_IO, rdf_path.c_str());
         for (int k = 0; k < rdf_nbins; ++k) fprintf(f, "%lld %d %lld\n", (long long)step, k, (long long)pairs[k]);
+        fclose(f);
+      }
+      if (!dyn_path.empty()) {
+        kmc_track_sample_t ts;
+        rc = kmc_track_sample(s, dyn_rmax, dyn_nbins, &ts, vh.data());
+        if (rc) return die(s, rc, "track sample");
+        f = fopen(dyn_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, dyn_path.c_str());
+        const long long o = (long long)ts.origin_step;
+        for (int c = 0; c < KMC_TRACK_CLASSES; ++c)
+          fprintf(f, "msd %lld %lld %d %lld %lld %.17g %.17g\n", (long long)step, o, c, (long long)ts.n[c],
+                  (long long)ts.n_clean[c], ts.sum_u2[c], ts.sum_u2_clean[c]);
+        fprintf(f, "surv %lld %lld %lld %lld %lld %lld %lld %lld\n", (long long)step, o, (long long)ts.rl0,
+                (long long)ts.rl_now, (long long)ts.rl_kept, (long long)ts.cis0, (long long)ts.cis_now,
+                (long long)ts.cis_kept);
+        for (int c = 0; c < KMC_TRACK_CLASSES; ++c)
+          for (int k = 0; k < dyn_nbins; ++k)
+            if (vh[(size_t)c * dyn_nbins + k])
+              fprintf(f, "vh %lld %d %d %lld\n", (long long)step, c, k, (long long)vh[(size_t)c * dyn_nbins + k]);
         fclose(f);
       }
     }

@@ -99,6 +99,11 @@ def load_library(path: Optional[str] = None):
                                   P(capi.Census)]
     L.kmc_analysis_ms.restype = C.c_double
     L.kmc_analysis_ms.argtypes = [C.c_void_p]
+    L.kmc_track_begin.argtypes = [C.c_void_p, C.c_double]
+    L.kmc_track_update.argtypes = [C.c_void_p, P(capi.TrackInfo)]
+    L.kmc_track_sample.argtypes = [C.c_void_p, C.c_double, C.c_int32, P(capi.TrackSample), C.c_void_p]
+    L.kmc_track_displacements.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kmc_track_end.argtypes = [C.c_void_p]
     for f in ("kmc_host_math", "kmc_device_math"):
         getattr(L, f).argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
@@ -330,8 +335,60 @@ class Simulation:
 
     @property
     def analysis_ms(self) -> float:
-        """Device milliseconds (HIP events) of the last components / census / pair_counts call."""
+        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* call."""
         return float(load_library().kmc_analysis_ms(self._h))
+
+    # ---- displacement tracking since a time origin (kmc_dynamics.hip; DESIGN.md §11)
+    def track_begin(self, max_jump: float = 0.0) -> None:
+        """The current state becomes the origin (max_jump <= 0: a quarter of the shorter box side)."""
+        self._check(load_library().kmc_track_begin(self._h, float(max_jump)))
+
+    def track_update(self) -> capi.TrackInfo:
+        """Add the minimum-image displacement since the last update to every protein's u; call it between
+        step() calls, often enough that no protein moves half a box in between."""
+        info = capi.TrackInfo()
+        self._check(load_library().kmc_track_update(self._h, C.byref(info)))
+        return info
+
+    def track_sample(self, r_max: float, nbins: int):
+        """(capi.TrackSample, vanhove[TRACK_CLASSES, nbins] int64) of the tracker as of the last update —
+        kmc_track_sample; analysis.msd turns the sample into per-class means."""
+        vh = np.zeros((capi.TRACK_CLASSES, max(int(nbins), 1)), dtype=np.int64)
+        out = capi.TrackSample()
+        self._check(load_library().kmc_track_sample(self._h, float(r_max), int(nbins), C.byref(out), vh.ctypes.data))
+        return out, vh
+
+    def track_displacements(self):
+        """(u[N, 2] float64, flags[N] uint8: capi.TRACK_CHANGED | capi.TRACK_JUMPED) by reference index."""
+        n = self.params.n_a + self.params.n_b
+        u = np.zeros((2, n), dtype=np.float64)
+        flags = np.zeros(n, dtype=np.uint8)
+        self._check(load_library().kmc_track_displacements(self._h, u.ctypes.data, flags.ctypes.data))
+        return np.ascontiguousarray(u.T), flags
+
+    def track_end(self) -> None:
+        self._check(load_library().kmc_track_end(self._h))
+
+    def run_tracked(self, nsteps: int, every: int, sample_every: int, r_max: float, nbins: int):
+        """Advance nsteps steps in pieces of at most `every` steps with a track_update after each piece,
+        sampling whenever `sample_every` more steps have passed (a multiple of `every` keeps the samples
+        evenly spaced).  The tracker must have been begun.  Returns (records[nsteps], samples), samples =
+        [(step, capi.TrackSample, vanhove)]."""
+        if nsteps < 0 or every < 1 or sample_every < 1:
+            raise ValueError("run_tracked: nsteps >= 0, every >= 1, sample_every >= 1")
+        recs = np.zeros(nsteps, dtype=capi.OBS_DTYPE)
+        samples = []
+        done = since = 0
+        while done < nsteps:
+            n = min(every, nsteps - done)
+            self.step(n, recs[done:done + n])
+            done += n
+            since += n
+            self.track_update()
+            if since >= sample_every:
+                since = 0
+                samples.append((self.current_step,) + self.track_sample(r_max, nbins))
+        return recs, samples
 
     @property
     def current_step(self) -> int:
