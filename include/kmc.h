@@ -224,7 +224,7 @@ int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int6
 int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t max_r, int32_t max_l,
                     int64_t* hist, kmc_census* out);
 /* Device milliseconds of the last kmc_components / kmc_oligomer_census /
- * kmc_pair_counts / kmc_track_* call: HIP events on the handle's stream around
+ * kmc_pair_counts / kmc_track_* / kmc_unwrap / kmc_cluster_* call: HIP events on the handle's stream around
  * its kernels and clears (the result copies to the host excluded); 0 before
  * the first. */
 double kmc_analysis_ms(const kmc_sim* s);
@@ -317,6 +317,98 @@ int kmc_track_update(kmc_sim* s, kmc_track_info* info);
 int kmc_track_sample(kmc_sim* s, double r_max, int32_t nbins, kmc_track_sample_t* out, int64_t* vanhove);
 int kmc_track_displacements(kmc_sim* s, double* u, uint8_t* flags);
 int kmc_track_end(kmc_sim* s);
+
+/* Cluster geometry: a periodic image for every protein, the
+ * spanning (percolation) bits of every component, and the exact integer
+ * moments behind the radius of gyration and the gyration tensor.  Like the
+ * structure analysis the calls read the CURRENT state on the device in a
+ * fixed number of launches, launch nothing inside kmc_step, leave the state,
+ * the step counter and kmc_get_clusters' validity untouched and are timed by
+ * kmc_analysis_ms; their scratch is their own (allocated by the first call,
+ * freed by kmc_destroy), so they interleave freely with kmc_components /
+ * kmc_oligomer_census / kmc_pair_counts / kmc_track_*.
+ *
+ * Definitions — the device, kmc_host_cluster_geometry and the tests share
+ * them bit for bit (doubles, no fused multiply-add, round = half away from
+ * zero):
+ *   graph, position   the bond graph of kmc_components; a protein's position
+ *                     is (x, y) of its bead [1][1], as in kmc_pair_counts.
+ *   integer coords    X_i = (int64) round(x_i * 1024.0), BX = (int64)
+ *                     round(box_x * 1024.0); the same in y.  The quantum is
+ *                     2^-10 A; the product is exact.
+ *   edge shift        for a bond i-j seen from i,
+ *                       n_x(i->j) = -(int) round((x_j - x_i) / box_x)
+ *                     (the same in y); n(j->i) = -n(i->j), ties at half a box
+ *                     included.
+ *   image shift       with r the component's label (its smallest reference
+ *                     index): off(r) = (0, 0) and off(j) = off(i) + n(i->j)
+ *                     along any bond path; the unwrapped coordinate is
+ *                     U_i = X_i + off_x(i) * BX.
+ *   spanning bits     a component carries bit 1 when some bond cycle has a
+ *                     non-zero total n_x, bit 2 for n_y: for the offsets of
+ *                     any spanning tree, some edge has off(j) - off(i) !=
+ *                     n(i->j) on that axis.  The bits do not depend on the
+ *                     tree.  The offsets of a spanning component are not
+ *                     unique: its members report shift (0, 0) and it is left
+ *                     out of all moments.
+ *   moments           for a component of size n >= 2 without spanning bits,
+ *                     D_i = U_i - U_r per axis:
+ *                       S1x = sum Dx, S1y = sum Dy                  (int64)
+ *                       S2xx = sum Dx^2, S2yy = sum Dy^2, S2xy = sum Dx*Dy
+ *                                          (128 bits, terms and sums exact)
+ *                       m = n * (S2xx + S2yy) - (S1x^2 + S1y^2)  (128 bits, >= 0)
+ *                       Rg^2 = m / n^2 / 2^20                       (A^2)
+ *                     A kmc_i128 is the two's-complement number hi * 2^64 + lo.
+ *
+ *   kmc_unwrap            label[i-1] as kmc_components; shift = sx[N] then
+ *                         sy[N], the image shift of every protein ((0, 0) in
+ *                         a spanning component); span[i-1] = the bits of
+ *                         protein i's component.  Every output may be NULL.
+ *   kmc_cluster_geometry  table[k], k = min(size, max_size), over the
+ *                         components without spanning bits and size >= 2:
+ *                         their number, the sum of their sizes and the sum of
+ *                         their m (bins 0 and 1 stay zero; the last bin is
+ *                         the overflow bin: it holds one size only when
+ *                         sum_size == count * max_size).  2 <= max_size <=
+ *                         KMC_GEOM_MAX_SIZE; table may be NULL.  out: the
+ *                         measured and the spanning components, and the
+ *                         census' largest component (ties: smallest label)
+ *                         with its bits.
+ *   kmc_cluster_list      one row per component of at least min_size (>= 2)
+ *                         members, spanning ones included (their sums are
+ *                         zero), sorted by label.  When more than cap
+ *                         qualify: KMC_ERR_CAPACITY, *n = the true count and
+ *                         rows unspecified; otherwise *n rows are written.
+ *                         rows may be NULL when cap is 0.
+ *   kmc_host_cluster_geometry  kmc_unwrap's and kmc_cluster_geometry's
+ *                         outputs from a host state view: a sequential
+ *                         breadth-first walk from each label, no device, no
+ *                         bin limit (every output but out may be NULL).
+ * KMC_ERR_ARG for a null / out-of-range argument, a handle without state and a
+ * decomposed window; KMC_ERR_STATE when a bond link leaves [0, n_a + n_b] or
+ * the links do not form finite chains (every device loop is bounded by
+ * n_a + n_b: none can hang); KMC_ERR_CAPACITY when an edge or an accumulated
+ * image shift leaves [-32767, 32767] (the device keeps them as int16). */
+#define KMC_GEOM_MAX_SIZE 1023
+#define KMC_SPAN_X 1
+#define KMC_SPAN_Y 2
+typedef struct kmc_i128 { uint64_t lo; int64_t hi; } kmc_i128;
+typedef struct kmc_geom_bin { int64_t count, sum_size; kmc_i128 sum_m; } kmc_geom_bin;
+typedef struct kmc_geom {
+  int64_t n_measured;            /* components without spanning bits and size >= 2 */
+  int64_t n_spanning, n_span_x, n_span_y, proteins_in_spanning;
+  int32_t largest_label, largest_size, largest_span, reserved; /* the census' largest component and its bits */
+} kmc_geom;
+typedef struct kmc_cluster {
+  int32_t label, n_r, n_l, span;
+  int64_t s1x, s1y;
+  kmc_i128 s2xx, s2yy, s2xy;     /* zero when span != 0 */
+} kmc_cluster;
+int kmc_unwrap(kmc_sim* s, int32_t* label, int32_t* shift, uint8_t* span);
+int kmc_cluster_geometry(kmc_sim* s, int32_t max_size, kmc_geom_bin* table, kmc_geom* out);
+int kmc_cluster_list(kmc_sim* s, int32_t min_size, int64_t cap, kmc_cluster* rows, int64_t* n);
+int kmc_host_cluster_geometry(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t* shift,
+                              uint8_t* span, int32_t max_size, kmc_geom_bin* table, kmc_geom* out);
 
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */

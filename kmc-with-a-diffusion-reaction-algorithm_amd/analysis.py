@@ -1,14 +1,18 @@
 """Post-processing of the on-device structure analysis (engine.Simulation.census /
 pair_counts) and displacement tracking (track_sample): g(r) from the lateral
-pair counts, per-class mean-squared displacements and the diffusion fit, and
-the replica sums of integer histograms and float64 sums.
+pair counts, per-class mean-squared displacements and the diffusion fit, the
+radius of gyration by cluster size, the fractal fit and the cluster shapes from
+the cluster geometry (cluster_geometry / cluster_list), and the replica sums of
+integer histograms, float64 sums and geometry tables.
 
 The counts and sums themselves come from libkmc (kmc_analysis.hip,
-kmc_dynamics.hip); nothing here touches a trajectory.
+kmc_dynamics.hip, kmc_geometry.hip); nothing here touches a trajectory.
 """
 from __future__ import annotations
 
 import numpy as np
+
+from . import capi
 
 
 def rdf(counts, n_i: int, n_j: int, box_x: float, box_y: float, r_max: float, same: bool) -> np.ndarray:
@@ -89,3 +93,111 @@ def reduce_sums(array, device=None, group=None) -> np.ndarray:
     if dist.is_available() and dist.is_initialized():
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
     return t.cpu().numpy()
+
+
+# ---------------------------------------------------------------- cluster geometry
+def rg_by_size(table):
+    """Mean squared radius of gyration by cluster size from kmc_cluster_geometry's
+    table (capi.GEOM_BIN_DTYPE, bin k = min(size, max_size)).
+
+    Returns (sizes, counts, rg2, overflow): the sizes 2 .. max_size − 1 that hold a
+    cluster, their counts and mean Rg² in Å² — sum_m / (count · n² · 2^20), the
+    integer quotient rounded once — and the last bin apart, as a dict with its
+    count, sum_size and rg2.  That bin mixes every size >= max_size; its rg2 is
+    given only when sum_size == count · max_size (all of them are exactly
+    max_size), else None."""
+    table = np.asarray(table)
+    max_size = len(table) - 1
+    m = capi.geom_m(table)
+    sizes, counts, rg2 = [], [], []
+    for k in range(2, max_size):
+        c = int(table["count"][k])
+        if c:
+            sizes.append(k)
+            counts.append(c)
+            rg2.append(m[k] / (c * k * k * (1 << 20)))
+    c, ss = int(table["count"][max_size]), int(table["sum_size"][max_size])
+    over = dict(count=c, sum_size=ss, rg2=m[max_size] / (c * max_size * max_size * (1 << 20))
+                if c and ss == c * max_size else None)
+    return (np.array(sizes, dtype=np.int64), np.array(counts, dtype=np.int64), np.array(rg2, dtype=np.float64), over)
+
+
+def fractal_fit(sizes, rg2, counts, min_size: int = 2):
+    """Fractal dimension from Rg ∝ n^(1/d_f): the least-squares line of log Rg
+    (= log(rg2) / 2) over log n, every size >= min_size with rg2 > 0 weighted by
+    its count.  Returns (slope, intercept, d_f = 1 / slope).  Needs two sizes."""
+    n = np.asarray(sizes, dtype=np.float64)
+    r2 = np.asarray(rg2, dtype=np.float64)
+    w = np.asarray(counts, dtype=np.float64)
+    keep = (n >= min_size) & (r2 > 0) & (w > 0)
+    if np.count_nonzero(keep) < 2:
+        raise ValueError("fractal_fit: fewer than two sizes to fit")
+    x, y, w = np.log(n[keep]), 0.5 * np.log(r2[keep]), w[keep]
+    xm, ym = np.sum(w * x) / w.sum(), np.sum(w * y) / w.sum()
+    slope = float(np.sum(w * (x - xm) * (y - ym)) / np.sum(w * (x - xm) ** 2))
+    return slope, float(ym - slope * xm), 1.0 / slope
+
+
+def cluster_shapes(rows, params, xy):
+    """Shape of each row of kmc_cluster_list (capi.Cluster) in float64 from its
+    integer sums.  xy[N, 2] are the positions (bead [1][1], Å) by reference
+    index: a row's sums are taken against its label's position.
+
+    Returns a dict of arrays over the rows: label, size, span, centre[., 2] (the
+    centre of mass wrapped into the box), rg (Å), lam1 >= lam2 (the eigenvalues
+    of the gyration tensor, Å²; rg² = lam1 + lam2) and asphericity
+    ((lam1 − lam2)² / (lam1 + lam2)²: 0 a disc, 1 a rod).  Spanning rows have
+    no shape: NaN."""
+    xy = np.asarray(xy, dtype=np.float64)
+    box = (params.box_x, params.box_y)
+    q = float(1 << 20)
+    out = dict(label=[], size=[], span=[], centre=[], rg=[], lam1=[], lam2=[], asphericity=[])
+    for r in rows:
+        d = r.as_dict()
+        n = d["n_r"] + d["n_l"]
+        out["label"].append(d["label"])
+        out["size"].append(n)
+        out["span"].append(d["span"])
+        if d["span"]:
+            out["centre"].append((np.nan, np.nan))
+            for k in ("rg", "lam1", "lam2", "asphericity"):
+                out[k].append(np.nan)
+            continue
+        c = []
+        for ax, s1 in enumerate((d["s1x"], d["s1y"])):
+            xr = np.round(xy[d["label"] - 1, ax] * 1024.0)  # X_r (half-way cases never matter at 2^-10 Å)
+            v = (xr + s1 / n) / 1024.0
+            c.append(v - box[ax] * np.floor(v / box[ax] + 0.5))
+        gxx = (n * d["s2xx"] - d["s1x"] ** 2) / (n * n) / q
+        gyy = (n * d["s2yy"] - d["s1y"] ** 2) / (n * n) / q
+        gxy = (n * d["s2xy"] - d["s1x"] * d["s1y"]) / (n * n) / q
+        half, det = 0.5 * (gxx + gyy), np.hypot(0.5 * (gxx - gyy), gxy)
+        l1, l2 = half + det, max(half - det, 0.0)
+        out["centre"].append(tuple(c))
+        out["rg"].append(np.sqrt(gxx + gyy))
+        out["lam1"].append(l1)
+        out["lam2"].append(l2)
+        out["asphericity"].append(((l1 - l2) / (l1 + l2)) ** 2 if l1 + l2 > 0 else 0.0)
+    return {k: np.array(v, dtype=np.int64 if k in ("label", "size", "span") else np.float64) for k, v in out.items()}
+
+
+def reduce_geom(table, device=None, group=None) -> np.ndarray:
+    """SUM all-reduce of kmc_cluster_geometry tables over the ranks of an
+    ensemble.  count and sum_size go as they are; the 128-bit sum of m goes as
+    int64 columns that cannot overflow — the two 32-bit halves of its low word
+    and the high word — summed by reduce_counts and put together again as
+    Python integers on the host.  Without an initialised process group the
+    table comes back unchanged."""
+    table = np.ascontiguousarray(table, dtype=capi.GEOM_BIN_DTYPE)
+    lo = table["sum_m_lo"].astype(np.uint64)
+    cols = np.stack([table["count"], table["sum_size"], (lo & np.uint64(0xFFFFFFFF)).astype(np.int64),
+                     (lo >> np.uint64(32)).astype(np.int64), table["sum_m_hi"]])
+    cols = reduce_counts(cols, device=device, group=group)
+    out = np.zeros(len(table), dtype=table.dtype)
+    out["count"], out["sum_size"] = cols[0], cols[1]
+    for k in range(len(table)):
+        m = ((int(cols[4][k]) << 64) + (int(cols[3][k]) << 32) + int(cols[2][k])) & ((1 << 128) - 1)
+        out["sum_m_lo"][k] = m & 0xFFFFFFFFFFFFFFFF
+        hi = m >> 64
+        out["sum_m_hi"][k] = hi - (1 << 64) if hi >> 63 else hi
+    return out

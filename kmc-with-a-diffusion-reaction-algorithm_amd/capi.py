@@ -205,6 +205,74 @@ class TrackSample(C.Structure):
         return d
 
 
+GEOM_MAX_SIZE = 1023                  # KMC_GEOM_MAX_SIZE (device table bins)
+SPAN_X, SPAN_Y = 1, 2                 # KMC_SPAN_X / KMC_SPAN_Y (spanning bits)
+
+
+class I128(C.Structure):
+    """kmc_i128 — the two's-complement number hi * 2^64 + lo."""
+
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_int64)]
+
+    def __int__(self) -> int:
+        return (int(self.hi) << 64) + int(self.lo)
+
+
+class GeomBin(C.Structure):
+    """kmc_geom_bin — one size bin of kmc_cluster_geometry's table."""
+
+    _fields_ = [("count", C.c_int64), ("sum_size", C.c_int64), ("sum_m", I128)]
+
+
+# kmc_geom_bin as a numpy record: the 128-bit sum as its two words
+GEOM_BIN_DTYPE = np.dtype([("count", "<i8"), ("sum_size", "<i8"), ("sum_m_lo", "<u8"), ("sum_m_hi", "<i8")])
+assert GEOM_BIN_DTYPE.itemsize == C.sizeof(GeomBin)
+
+
+class Geom(C.Structure):
+    """kmc_geom — summary of kmc_cluster_geometry."""
+
+    _fields_ = [
+        ("n_measured", C.c_int64),
+        ("n_spanning", C.c_int64),
+        ("n_span_x", C.c_int64),
+        ("n_span_y", C.c_int64),
+        ("proteins_in_spanning", C.c_int64),
+        ("largest_label", C.c_int32),
+        ("largest_size", C.c_int32),
+        ("largest_span", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
+class Cluster(C.Structure):
+    """kmc_cluster — one row of kmc_cluster_list."""
+
+    _fields_ = [
+        ("label", C.c_int32),
+        ("n_r", C.c_int32),
+        ("n_l", C.c_int32),
+        ("span", C.c_int32),
+        ("s1x", C.c_int64),
+        ("s1y", C.c_int64),
+        ("s2xx", I128),
+        ("s2yy", I128),
+        ("s2xy", I128),
+    ]
+
+    def as_dict(self) -> dict:
+        """Plain Python ints, the 128-bit sums whole."""
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+def geom_m(table) -> list:
+    """The 128-bit sum of m of every bin of a GEOM_BIN_DTYPE table, as Python ints."""
+    return [(int(hi) << 64) + int(lo) for lo, hi in zip(table["sum_m_lo"], table["sum_m_hi"])]
+
+
 DD_ROW = 416     # KMC_DD_ROW: one exchanged protein (48 doubles + 8 int32)
 DD_JCAP = 256    # KMC_DD_JCAP
 DD_XCAP = 64     # KMC_DD_XCAP

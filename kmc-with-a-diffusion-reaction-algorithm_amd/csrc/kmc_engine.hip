@@ -14,6 +14,7 @@
 #include "kmc_host.h"
 #include "kmc_kernels.hip"
 #include "kmc_analysis.hip"
+#include "kmc_geometry.hip"
 #include "kmc_dynamics.hip"
 
 using namespace kmcd;
@@ -149,6 +150,17 @@ struct kmc_sim {
   double2* an_pts = nullptr;   // [N] (x, y) sorted by cell
   double* an_edges = nullptr;  // [AN_HIST_MAX + 1] squared bin edges
   int an_chunk = AN_CHUNK;     // KMC_DEBUG_PAIR_CHUNK: smaller staged chunks (the chunked path at test size)
+  // cluster geometry (kmc_geometry.hip): scratch of the first geometry call, its
+  // own (an interleaved kmc_components / census / track_* call touches none of it)
+  unsigned long long *geo_word = nullptr, *geo_cnt = nullptr;  // [N] (parent, rel) words; packed member counts by root
+  unsigned long long *geo_acc = nullptr, *geo_table = nullptr; // [N][GEO_ACC] moments by root; [GEO_MAX_SIZE + 1][GEO_BIN] bins
+  longlong2* geo_X = nullptr;                                  // [N] integer coordinates
+  int32_t* geo_label = nullptr;
+  int2* geo_off = nullptr;       // [N] image shift against the root
+  uint32_t* geo_span = nullptr;  // [N] spanning bits by root
+  GeoOut* geo_out = nullptr;
+  kmc_cluster* geo_rows = nullptr;  // [geo_rows_cap] kmc_cluster_list's rows
+  size_t geo_rows_cap = 0;
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   double an_ms = 0.0;
   // displacement tracking (kmc_dynamics.hip): scratch of the first
@@ -2287,6 +2299,166 @@ int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int6
 }
 
 double kmc_analysis_ms(const kmc_sim* s) { return s ? s->an_ms : 0.0; }
+
+// ---------------------------------------------------------------- cluster geometry
+// kmc_geometry.hip: read-only like the analysis above, on scratch of its own.
+
+static_assert(sizeof(kmc_geom_bin) == sizeof(unsigned long long) * GEO_BIN, "a table bin is GEO_BIN words");
+static_assert(sizeof(kmc_cluster) == 80, "kmc_cluster layout");
+static_assert(KMC_GEOM_MAX_SIZE == GEO_MAX_SIZE, "kmc.h and kmc_geometry.hip agree on the table limit");
+
+// labels, image shifts, spanning bits, member counts and moments by root, left
+// on the device (five launches); the stream is not waited for
+static int geo_run(kmc_sim* s) {
+  const int N = s->K.N, NA = s->K.NA;
+  if (!s->geo_out) {
+    int rc = KMC_OK;
+    rc |= dalloc(s, &s->geo_word, (size_t)N);
+    rc |= dalloc(s, &s->geo_cnt, (size_t)N);
+    rc |= dalloc(s, &s->geo_acc, (size_t)N * GEO_ACC);
+    rc |= dalloc(s, &s->geo_table, (size_t)(GEO_MAX_SIZE + 1) * GEO_BIN);
+    rc |= dalloc(s, &s->geo_X, (size_t)N);
+    rc |= dalloc(s, &s->geo_label, (size_t)N);
+    rc |= dalloc(s, &s->geo_off, (size_t)N);
+    rc |= dalloc(s, &s->geo_span, (size_t)N);
+    rc |= dalloc(s, &s->geo_out, 1);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "geometry: scratch allocation failed");
+  }
+  hipStream_t st = s->stream;
+  const unsigned g = (unsigned)((N + AN_T - 1) / AN_T);
+  const long long BX = (long long)kmcm::round_(s->K.box_x * 1024.0), BY = (long long)kmcm::round_(s->K.box_y * 1024.0);
+  HIPCHK(s, hipMemsetAsync(s->geo_out, 0, sizeof(GeoOut), st));
+  if (g) {
+    k_geo_init<<<g, AN_T, 0, st>>>(s->K, s->d, s->geo_word, s->geo_X, s->geo_cnt, s->geo_span, s->geo_acc);
+    k_geo_hook<<<g, AN_T, 0, st>>>(s->K, s->d, s->geo_word, s->geo_out);
+    k_geo_flatten<<<g, AN_T, 0, st>>>(s->geo_word, s->geo_label, s->geo_off, s->geo_cnt, NA, N, s->geo_out);
+    k_geo_check<<<g, AN_T, 0, st>>>(s->K, s->d, s->geo_label, s->geo_off, s->geo_span, s->geo_out);
+    k_geo_moments<<<g, AN_T, 0, st>>>(s->geo_label, s->geo_off, s->geo_X, s->geo_span, BX, BY, N, s->geo_acc);
+  }
+  HIPCHK(s, hipGetLastError());
+  return KMC_OK;
+}
+
+// the device's verdict of the last geometry call
+static int geo_result(kmc_sim* s, GeoOut* o) {
+  HIPCHK(s, hipMemcpy(o, s->geo_out, sizeof *o, hipMemcpyDeviceToHost));
+  if (o->err & 1u)
+    return fail(s, KMC_ERR_STATE, "geometry: a bond link leaves the state or the link chains do not end");
+  if (o->err & 2u) return fail(s, KMC_ERR_CAPACITY, "geometry: an image shift leaves [-32767, 32767]");
+  return KMC_OK;
+}
+
+int kmc_unwrap(kmc_sim* s, int32_t* label, int32_t* shift, uint8_t* span) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = geo_run(s);
+  if (rc == KMC_OK) rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  GeoOut o;
+  rc = geo_result(s, &o);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  std::vector<int32_t> lab(N);
+  std::vector<uint32_t> sp(N);
+  HIPCHK(s, hipMemcpy(lab.data(), s->geo_label, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(sp.data(), s->geo_span, sizeof(uint32_t) * N, hipMemcpyDeviceToHost));
+  if (shift) {
+    std::vector<int2> off(N);
+    HIPCHK(s, hipMemcpy(off.data(), s->geo_off, sizeof(int2) * N, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N; ++i) {
+      const bool wraps = sp[lab[i]] != 0;  // (its offsets depend on the tree: not reported)
+      shift[i] = wraps ? 0 : off[i].x;
+      shift[N + i] = wraps ? 0 : off[i].y;
+    }
+  }
+  if (span)
+    for (size_t i = 0; i < N; ++i) span[i] = (uint8_t)sp[lab[i]];
+  if (label)
+    for (size_t i = 0; i < N; ++i) label[i] = lab[i] + 1;
+  return KMC_OK;
+}
+
+int kmc_cluster_geometry(kmc_sim* s, int32_t max_size, kmc_geom_bin* table, kmc_geom* out) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out || max_size < 2 || max_size > GEO_MAX_SIZE)
+    return fail(s, KMC_ERR_ARG, "cluster geometry: out is needed, 2 <= max_size <= " + std::to_string(GEO_MAX_SIZE) +
+                                    " (larger clusters clamp into the last bin)");
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = geo_run(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  const size_t nbin = table ? (size_t)max_size + 1 : 0;
+  hipStream_t st = s->stream;
+  if (nbin) HIPCHK(s, hipMemsetAsync(s->geo_table, 0, sizeof(kmc_geom_bin) * nbin, st));
+  const unsigned g = (unsigned)std::min<int64_t>(GEO_TABLE_WG, ((int64_t)N + AN_T - 1) / AN_T);
+  if (g)
+    k_geo_table<<<g, AN_T, sizeof(unsigned long long) * (nbin * GEO_BIN + 6), st>>>(
+        s->geo_label, s->geo_cnt, s->geo_span, s->geo_acc, N, max_size, nbin ? s->geo_table : nullptr, s->geo_out);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  GeoOut o;
+  rc = geo_result(s, &o);
+  if (rc != KMC_OK) return rc;
+  std::memset(out, 0, sizeof *out);
+  out->n_measured = (int64_t)o.n_measured;
+  out->n_spanning = (int64_t)o.n_spanning;
+  out->n_span_x = (int64_t)o.n_span_x;
+  out->n_span_y = (int64_t)o.n_span_y;
+  out->proteins_in_spanning = (int64_t)o.proteins_in_spanning;
+  if (o.best) {
+    const uint32_t root = 0xffffffffu - (uint32_t)o.best;
+    uint32_t sp = 0;
+    HIPCHK(s, hipMemcpy(&sp, s->geo_span + root, sizeof sp, hipMemcpyDeviceToHost));
+    out->largest_label = (int32_t)root + 1;
+    out->largest_size = (int32_t)(o.best >> 32);
+    out->largest_span = (int32_t)sp;
+  }
+  if (nbin) HIPCHK(s, hipMemcpy(table, s->geo_table, sizeof(kmc_geom_bin) * nbin, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_cluster_list(kmc_sim* s, int32_t min_size, int64_t cap, kmc_cluster* rows, int64_t* n) {
+  if (!s) return KMC_ERR_ARG;
+  if (!n || min_size < 2 || cap < 0 || (cap > 0 && !rows))
+    return fail(s, KMC_ERR_ARG, "cluster list: n is needed, min_size >= 2, cap >= 0, rows for cap > 0");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  // no more than N / min_size roots can qualify: a larger cap needs no larger buffer
+  const size_t dcap = (size_t)std::min<int64_t>(cap, N / min_size);
+  if (dcap > s->geo_rows_cap) {
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    dfree(s, s->geo_rows);
+    s->geo_rows_cap = 0;
+    if (dalloc(s, &s->geo_rows, dcap) != KMC_OK) return fail(s, KMC_ERR_HIP, "geometry: scratch allocation failed");
+    s->geo_rows_cap = dcap;
+  }
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = geo_run(s);
+  if (rc != KMC_OK) return rc;
+  const unsigned g = (unsigned)((N + AN_T - 1) / AN_T);
+  if (g)
+    k_geo_list<<<g, AN_T, 0, s->stream>>>(s->geo_label, s->geo_cnt, s->geo_span, s->geo_acc, N, min_size,
+                                          (long long)dcap, s->geo_rows, s->geo_out);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  GeoOut o;
+  rc = geo_result(s, &o);
+  if (rc != KMC_OK) return rc;
+  *n = (int64_t)o.n_rows;
+  if (*n > cap)
+    return fail(s, KMC_ERR_CAPACITY, "cluster list: " + std::to_string(*n) + " components qualify, cap is " +
+                                         std::to_string(cap));
+  if (*n) {
+    HIPCHK(s, hipMemcpy(rows, s->geo_rows, sizeof(kmc_cluster) * (size_t)*n, hipMemcpyDeviceToHost));
+    std::sort(rows, rows + *n, [](const kmc_cluster& a, const kmc_cluster& b) { return a.label < b.label; });
+  }
+  return KMC_OK;
+}
 
 // ---------------------------------------------------------------- displacement tracking
 // kmc_dynamics.hip: the tracker is a layer of its own over the committed

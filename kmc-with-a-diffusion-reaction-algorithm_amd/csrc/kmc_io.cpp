@@ -729,6 +729,121 @@ int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label
   return KMC_OK;
 }
 
+// Cluster geometry (include/kmc.h), sequential: a breadth-first walk from every
+// protein not yet labelled, in index order — the start is the label, its image
+// shift (0, 0), and a member takes its shift from the member that reached it;
+// then every edge of the component is compared with the shifts (the spanning
+// bits), and the moments are summed in 128-bit integers.
+int kmc_host_cluster_geometry(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t* shift,
+                              uint8_t* span, int32_t max_size, kmc_geom_bin* table, kmc_geom* out) {
+  if (!p || !v || !out || !v->a_int || !v->b_int || !v->ra || !v->rb || p->n_a < 0 || p->n_b < 0 || max_size < 2) {
+    g_host_err = "cluster geometry: params, state and out are needed, max_size >= 2";
+    return KMC_ERR_ARG;
+  }
+  const int na = p->n_a, nb = p->n_b, n = na + nb;
+  const double box[2] = {p->box_x, p->box_y};
+  const long long B[2] = {(long long)kmcm::round_(p->box_x * 1024.0), (long long)kmcm::round_(p->box_y * 1024.0)};
+  auto pos = [&](int q, int c) { return q < na ? v->ra[RA(na, 1, 1, c, q)] : v->rb[RB(nb, 1, 1, c, q - na)]; };
+  auto edge = [&](int i, int j, int c) { return -(int)kmcm::round_((pos(j, c) - pos(i, c)) / box[c]); };
+  auto links = [&](int q, int* nei) {
+    int m = 0;
+    if (q < na) {
+      nei[m++] = v->a_int[2 * (size_t)na + q];
+      nei[m++] = v->a_int[4 * (size_t)na + q];
+    } else {
+      for (int j = 2; j <= 4; ++j) nei[m++] = v->b_int[(size_t)(4 + j - 1) * nb + (q - na)];
+    }
+    return m;
+  };
+  typedef __int128 i128;
+  auto put = [](kmc_i128* w, i128 x) {
+    w->lo = (uint64_t)(unsigned __int128)x;
+    w->hi = (int64_t)(x >> 64);
+  };
+  std::vector<int32_t> lab((size_t)n, 0), sx((size_t)n, 0), sy((size_t)n, 0), queue;
+  std::vector<uint8_t> sp((size_t)n, 0);
+  std::vector<i128> sum_m(table ? (size_t)max_size + 1 : 0, 0);
+  queue.reserve((size_t)n);
+  std::memset(out, 0, sizeof *out);
+  if (table) std::memset(table, 0, sizeof(kmc_geom_bin) * ((size_t)max_size + 1));
+  for (int r = 0; r < n; ++r) {
+    if (lab[r]) continue;
+    queue.clear();
+    queue.push_back(r);
+    lab[r] = r + 1;
+    for (size_t h = 0; h < queue.size(); ++h) {
+      const int q = queue[h];
+      int nei[3];
+      const int m = links(q, nei);
+      for (int e = 0; e < m; ++e) {
+        if (nei[e] == 0) continue;
+        if (nei[e] < 1 || nei[e] > n) {
+          g_host_err = "cluster geometry: a bond link of protein " + std::to_string(q + 1) + " leaves the state";
+          return KMC_ERR_STATE;
+        }
+        const int j = nei[e] - 1;
+        if (lab[j]) continue;
+        lab[j] = r + 1;
+        sx[j] = sx[q] + edge(q, j, 0);
+        sy[j] = sy[q] + edge(q, j, 1);
+        queue.push_back(j);
+      }
+    }
+    int bits = 0;
+    for (int q : queue) {
+      int nei[3];
+      const int m = links(q, nei);
+      for (int e = 0; e < m; ++e) {
+        if (nei[e] == 0) continue;
+        const int j = nei[e] - 1;
+        if (sx[j] - sx[q] != edge(q, j, 0)) bits |= KMC_SPAN_X;
+        if (sy[j] - sy[q] != edge(q, j, 1)) bits |= KMC_SPAN_Y;
+      }
+    }
+    const int size = (int)queue.size();
+    if (size > out->largest_size) {  // (components come in label order: the first of a size keeps the tie)
+      out->largest_size = size;
+      out->largest_label = r + 1;
+      out->largest_span = bits;
+    }
+    if (bits) {
+      out->n_spanning += 1;
+      out->n_span_x += (bits & KMC_SPAN_X) != 0;
+      out->n_span_y += (bits & KMC_SPAN_Y) != 0;
+      out->proteins_in_spanning += size;
+      for (int q : queue) {
+        sp[q] = (uint8_t)bits;
+        sx[q] = sy[q] = 0;
+      }
+      continue;
+    }
+    if (size < 2) continue;
+    out->n_measured += 1;
+    if (!table) continue;
+    long long s1[2] = {0, 0};
+    i128 s2 = 0;
+    for (int q : queue)
+      for (int c = 0; c < 2; ++c) {
+        const long long d = ((long long)kmcm::round_(pos(q, c) * 1024.0) + (long long)(c ? sy[q] : sx[q]) * B[c]) -
+                            (long long)kmcm::round_(pos(r, c) * 1024.0);
+        s1[c] += d;
+        s2 += (i128)d * d;
+      }
+    const int k = std::min(size, (int)max_size);
+    table[k].count += 1;
+    table[k].sum_size += size;
+    sum_m[k] += (i128)size * s2 - ((i128)s1[0] * s1[0] + (i128)s1[1] * s1[1]);
+  }
+  for (size_t k = 0; k < sum_m.size(); ++k) put(&table[k].sum_m, sum_m[k]);
+  if (label) std::copy(lab.begin(), lab.end(), label);
+  if (shift) {
+    std::copy(sx.begin(), sx.end(), shift);
+    std::copy(sy.begin(), sy.end(), shift + n);
+  }
+  if (span) std::copy(sp.begin(), sp.end(), span);
+  return KMC_OK;
+}
+
 int kmc_host_math(int op, const double* x, const double* y, double* out, int64_t n) {
   for (int64_t i = 0; i < n; ++i) {
     double a = x[i], b = y[i], r = 0;

@@ -23,6 +23,12 @@
 //                            (kmc_pair_counts; WHICH = AA, AB or BB): step k count
 //                            (both appended; truncated on a fresh start, like bond.dat;
 //                            census bins clamp at 63 receptors / 63 ligands)
+//           [--geom MAXSIZE FILE]  every out_interval, the cluster geometry
+//                            (kmc_cluster_geometry; 2 <= MAXSIZE <= 1023, larger clusters clamp
+//                            into the last bin), appended like the census: per non-empty bin
+//                              step size count sum_m_hi sum_m_lo      (Rg² = m / n² / 2^20 Å²)
+//                            and one line
+//                              step span n_spanning n_span_x n_span_y largest_size largest_span
 //           [--dyn EVERY RMAX NBINS FILE]  displacement tracking (kmc_track_*): the origin is
 //                            the state the process starts or resumes from (the tracker is
 //                            not checkpointed: a resume starts a new origin, every line
@@ -83,8 +89,8 @@ int main(int argc, char** argv) {
   kmc_params p;
   kmc_params_default(&p);
   int device = 0;
-  std::string state_path, census_path, rdf_path, dyn_path;
-  int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0;
+  std::string state_path, census_path, rdf_path, dyn_path, geom_path;
+  int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0, geom_max = 0;
   double rdf_rmax = 0.0, dyn_rmax = 0.0;
   int64_t dyn_every = 0;
   for (int i = 1; i < argc; ++i) {
@@ -117,6 +123,14 @@ int main(int argc, char** argv) {
       rdf_path = next();
       if (rdf_which < 0 || !(rdf_rmax > 0.0) || rdf_nbins < 1 || rdf_nbins > KMC_PAIR_MAX_BINS) {
         fprintf(stderr, "kmc_run: bad --rdf %s %g %d\n", w.c_str(), rdf_rmax, rdf_nbins);
+        return 2;
+      }
+    }
+    else if (a == "--geom") {
+      geom_max = atoi(next().c_str());
+      geom_path = next();
+      if (geom_max < 2 || geom_max > KMC_GEOM_MAX_SIZE) {
+        fprintf(stderr, "kmc_run: bad --geom %d\n", geom_max);
         return 2;
       }
     }
@@ -166,6 +180,7 @@ int main(int argc, char** argv) {
     if (!census_path.empty()) truncate(census_path.c_str());
     if (!rdf_path.empty()) truncate(rdf_path.c_str());
     if (!dyn_path.empty()) truncate(dyn_path.c_str());
+    if (!geom_path.empty()) truncate(geom_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
   }
@@ -179,6 +194,7 @@ int main(int argc, char** argv) {
   std::vector<kmc_obs> obs;
   const int census_max = 63;  // census rows / columns: 0..63 receptors / ligands, more clamp into the last
   std::vector<int64_t> hist((size_t)(census_max + 1) * (census_max + 1)), pairs((size_t)rdf_nbins + 1);
+  std::vector<kmc_geom_bin> geom((size_t)geom_max + 1);
   std::vector<int64_t> vh((size_t)KMC_TRACK_CLASSES * dyn_nbins + 1);
   if (!dyn_path.empty()) {
     rc = kmc_track_begin(s, 0.0);
@@ -243,6 +259,20 @@ int main(int argc, char** argv) {
         f = fopen(rdf_path.c_str(), "ab");
         if (!f) return die(s, KMC_ERR_IO, rdf_path.c_str());
         for (int k = 0; k < rdf_nbins; ++k) fprintf(f, "%lld %d %lld\n", (long long)step, k, (long long)pairs[k]);
+        fclose(f);
+      }
+      if (!geom_path.empty()) {
+        kmc_geom g;
+        rc = kmc_cluster_geometry(s, geom_max, geom.data(), &g);
+        if (rc) return die(s, rc, "cluster geometry");
+        f = fopen(geom_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, geom_path.c_str());
+        for (int k = 0; k <= geom_max; ++k)
+          if (geom[k].count)
+            fprintf(f, "%lld %d %lld %lld %llu\n", (long long)step, k, (long long)geom[k].count,
+                    (long long)geom[k].sum_m.hi, (unsigned long long)geom[k].sum_m.lo);
+        fprintf(f, "%lld span %lld %lld %lld %d %d\n", (long long)step, (long long)g.n_spanning, (long long)g.n_span_x,
+                (long long)g.n_span_y, g.largest_size, g.largest_span);
         fclose(f);
       }
       if (!dyn_path.empty()) {

@@ -104,6 +104,11 @@ def load_library(path: Optional[str] = None):
     L.kmc_track_sample.argtypes = [C.c_void_p, C.c_double, C.c_int32, P(capi.TrackSample), C.c_void_p]
     L.kmc_track_displacements.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.kmc_track_end.argtypes = [C.c_void_p]
+    L.kmc_unwrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kmc_cluster_geometry.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, P(capi.Geom)]
+    L.kmc_cluster_list.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, P(C.c_int64)]
+    L.kmc_host_cluster_geometry.argtypes = [P(capi.Params), P(capi.StateView), C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int32, C.c_void_p, P(capi.Geom)]
     for f in ("kmc_host_math", "kmc_device_math"):
         getattr(L, f).argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
@@ -170,6 +175,22 @@ def host_census(params: capi.Params, hs: capi.HostState, max_r: int, max_l: int)
     _host_check(load_library().kmc_host_census(C.byref(params), C.byref(v), label.ctypes.data, max_r, max_l,
                                                hist.ctypes.data, C.byref(out)))
     return label, hist, out
+
+
+def host_cluster_geometry(params: capi.Params, hs: capi.HostState, max_size: int):
+    """Cluster geometry of a host state, sequentially (kmc_host_cluster_geometry): (label[N] 1-based,
+    shift[N, 2] int32, span[N] uint8, table[max_size + 1] capi.GEOM_BIN_DTYPE, capi.Geom)."""
+    n = params.n_a + params.n_b
+    label = np.zeros(n, dtype=np.int32)
+    shift = np.zeros((2, n), dtype=np.int32)
+    span = np.zeros(n, dtype=np.uint8)
+    table = np.zeros(max(int(max_size), 0) + 1, dtype=capi.GEOM_BIN_DTYPE)
+    out = capi.Geom()
+    v = hs.view()
+    _host_check(load_library().kmc_host_cluster_geometry(C.byref(params), C.byref(v), label.ctypes.data,
+                                                         shift.ctypes.data, span.ctypes.data, int(max_size),
+                                                         table.ctypes.data, C.byref(out)))
+    return label, np.ascontiguousarray(shift.T), span, table, out
 
 
 def host_dd_check(gid: np.ndarray, own: np.ndarray) -> int:
@@ -333,9 +354,42 @@ class Simulation:
                                                    counts.ctypes.data))
         return counts
 
+    # ---- cluster geometry of the current state (kmc_geometry.hip)
+    def unwrap(self):
+        """(label[N] 1-based as components(), shift[N, 2] int32 periodic image of every protein against its
+        label, span[N] uint8 spanning bits of its component: capi.SPAN_X | capi.SPAN_Y) — kmc_unwrap."""
+        n = self.params.n_a + self.params.n_b
+        label = np.zeros(n, dtype=np.int32)
+        shift = np.zeros((2, n), dtype=np.int32)
+        span = np.zeros(n, dtype=np.uint8)
+        self._check(load_library().kmc_unwrap(self._h, label.ctypes.data, shift.ctypes.data, span.ctypes.data))
+        return label, np.ascontiguousarray(shift.T), span
+
+    def cluster_geometry(self, max_size: int):
+        """(table[max_size + 1] capi.GEOM_BIN_DTYPE by cluster size, larger sizes clamped into the last bin;
+        capi.Geom summary) — kmc_cluster_geometry; analysis.rg_by_size turns the table into Rg²(n)."""
+        table = np.zeros(max(int(max_size), 0) + 1, dtype=capi.GEOM_BIN_DTYPE)
+        out = capi.Geom()
+        self._check(load_library().kmc_cluster_geometry(self._h, int(max_size), table.ctypes.data, C.byref(out)))
+        return table, out
+
+    def cluster_list(self, min_size: int, cap: int = 4096):
+        """Rows (a capi.Cluster array, sorted by label) of the components of at least min_size members —
+        kmc_cluster_list; when more than cap qualify, the call is repeated once with the count it returned."""
+        L = load_library()
+        n = C.c_int64()
+        for _ in range(2):
+            rows = (capi.Cluster * max(int(cap), 1))()
+            rc = L.kmc_cluster_list(self._h, int(min_size), int(cap), rows, C.byref(n))
+            if rc != capi.ERR_CAPACITY or n.value <= cap:
+                break
+            cap = n.value
+        self._check(rc)
+        return rows[: n.value]
+
     @property
     def analysis_ms(self) -> float:
-        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* call."""
+        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / unwrap / cluster_* call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
     # ---- displacement tracking since a time origin (kmc_dynamics.hip; DESIGN.md §11)
