@@ -224,7 +224,7 @@ int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int6
 int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t max_r, int32_t max_l,
                     int64_t* hist, kmc_census* out);
 /* Device milliseconds of the last kmc_components / kmc_oligomer_census /
- * kmc_pair_counts / kmc_track_* / kmc_unwrap / kmc_cluster_* call: HIP events on the handle's stream around
+ * kmc_pair_counts / kmc_track_* / kmc_unwrap / kmc_cluster_* / kmc_structure_factor call: HIP events on the handle's stream around
  * its kernels and clears (the result copies to the host excluded); 0 before
  * the first. */
 double kmc_analysis_ms(const kmc_sim* s);
@@ -409,6 +409,59 @@ int kmc_cluster_geometry(kmc_sim* s, int32_t max_size, kmc_geom_bin* table, kmc_
 int kmc_cluster_list(kmc_sim* s, int32_t min_size, int64_t cap, kmc_cluster* rows, int64_t* n);
 int kmc_host_cluster_geometry(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t* shift,
                               uint8_t* span, int32_t max_size, kmc_geom_bin* table, kmc_geom* out);
+
+/* Static structure factor: per species the sums of every
+ * selected protein's (cos, sin) of q . r at the wave vectors of the half plane,
+ * as exact integers.  Like the structure analysis the call reads the CURRENT
+ * state on the device (valid straight after kmc_set_state / kmc_load_*),
+ * launches nothing inside kmc_step, leaves the state, the step counter, the
+ * tracker and kmc_get_clusters' validity untouched and is timed by
+ * kmc_analysis_ms; its scratch is its own (allocated by the first call, freed
+ * by kmc_destroy).
+ *
+ * Definitions — the device, kmc_host_structure_factor and the tests share
+ * them bit for bit (doubles, no fused multiply-add; round = half away from
+ * zero, sin and cos the library's own, kmc_math.h):
+ *   position        (x, y) of bead [1][1], as in kmc_pair_counts.
+ *   integer coords  X_i = (int64) round(x_i * 1024.0), BX = (int64)
+ *                   round(box_x * 1024.0); the same in y (§12's 2^-10 A).
+ *                   KMC_ERR_ARG when BX < 1 or BY < 1.
+ *   wave vectors    q(h, k) = 2 pi (h / box_x, k / box_y), h = 0..hmax,
+ *                   k = -kmax..kmax (the half plane: rho(-q) = conj rho(q));
+ *                   0 <= hmax, kmax <= KMC_SK_MAX; nq = (hmax + 1)(2 kmax + 1),
+ *                   (h, k) has index h (2 kmax + 1) + (k + kmax).
+ *   axis phase      for a multiplier m >= 0 (h, or |k|), coordinate X, box B:
+ *                     p = (m X) mod B in [0, B) (the floor modulus: X may be
+ *                     negative); if (2 p >= B) p -= B;
+ *                     t = (double) p / (double) B; a = 6.283185307179586 * t;
+ *                     c = cos(a), s = sin(a)
+ *                   — (cx, sx) from (h, X_i, BX), (cy, sy) from (|k|, Y_i, BY);
+ *                   for k < 0, sy = -sy and cy is unchanged.
+ *   term            re = cx*cy - sx*sy, im = sx*cy + cx*sy;
+ *                   tc = (int64) round(re * 1073741824.0), ts = (int64)
+ *                   round(im * 1073741824.0) (2^30: product and conversion
+ *                   are exact).
+ *   sums            C_A(q) = sum tc, S_A(q) = sum ts over the selected
+ *                   receptors, C_B, S_B over the selected ligands: int64,
+ *                   exact, the same bits in any order of summation;
+ *                   |sum| < 2^62 for every N the engine accepts.
+ *   selection       KMC_SK_ALL: every protein.  KMC_SK_BOUND: the receptors
+ *                   with nei2 != 0 or nei3 != 0 and the ligands with any of
+ *                   nei2..4 != 0 (the clustered phase).
+ * sums is [4][nq]: C_A, S_A, C_B, S_B; n_sel = the receptors and the ligands
+ * selected.  With rho = (C + i S) / 2^30 the partials are S_AA = |rho_A|^2 /
+ * N_A, S_BB = |rho_B|^2 / N_B, S_AB = Re(rho_A conj rho_B) / sqrt(N_A N_B) and
+ * S_NN = |rho_A + rho_B|^2 / (N_A + N_B).
+ * kmc_host_structure_factor: the same from a host state view, sequentially, no
+ * device.  KMC_ERR_ARG for a null / out-of-range argument, a handle without
+ * state and a decomposed window. */
+#define KMC_SK_MAX 64
+#define KMC_SK_ALL 0
+#define KMC_SK_BOUND 1
+int kmc_structure_factor(kmc_sim* s, int32_t hmax, int32_t kmax, int32_t select,
+                         int64_t* sums /* [4][nq]: C_A, S_A, C_B, S_B */, int64_t n_sel[2]);
+int kmc_host_structure_factor(const kmc_params* p, const kmc_state_view* v, int32_t hmax, int32_t kmax,
+                              int32_t select, int64_t* sums, int64_t n_sel[2]);
 
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */

@@ -2,11 +2,14 @@
 pair_counts) and displacement tracking (track_sample): g(r) from the lateral
 pair counts, per-class mean-squared displacements and the diffusion fit, the
 radius of gyration by cluster size, the fractal fit and the cluster shapes from
-the cluster geometry (cluster_geometry / cluster_list), and the replica sums of
-integer histograms, float64 sums and geometry tables.
+the cluster geometry (cluster_geometry / cluster_list), the partial static
+structure factors S(q) and their radial average from the integer sums of
+structure_factor, and the replica sums of integer histograms, float64 sums and
+geometry tables.
 
 The counts and sums themselves come from libkmc (kmc_analysis.hip,
-kmc_dynamics.hip, kmc_geometry.hip); nothing here touches a trajectory.
+kmc_dynamics.hip, kmc_geometry.hip, kmc_structure.hip); nothing here touches a
+trajectory.
 """
 from __future__ import annotations
 
@@ -201,3 +204,56 @@ def reduce_geom(table, device=None, group=None) -> np.ndarray:
         hi = m >> 64
         out["sum_m_hi"][k] = hi - (1 << 64) if hi >> 63 else hi
     return out
+
+
+# ---------------------------------------------------------------- structure factor
+def structure_factor(sums, n_sel) -> dict:
+    """The partial structure factors from kmc_structure_factor's integer sums
+    (sums[4, ...]: C_A, S_A, C_B, S_B; n_sel = the receptors and ligands summed
+    over).  With rho = (C + iS) / 2^30, float64 arrays of the sums' grid:
+      AA = |rho_A|^2 / N_A,  BB = |rho_B|^2 / N_B,
+      AB = Re(rho_A conj rho_B) / sqrt(N_A N_B),  NN = |rho_A + rho_B|^2 / (N_A + N_B).
+    A partial whose species is empty is all zeros.
+
+    Replicas: S(q) of an ensemble is the float64 mean of the per-replica values
+    — sum them with reduce_sums and divide by the number of replicas.  The
+    integer sums of different replicas must NOT be added: they are amplitudes
+    of unrelated configurations, and their sum's square is not a sum of squares."""
+    sums = np.asarray(sums)
+    if sums.shape[0] != 4:
+        raise ValueError("structure_factor: sums is [4, ...] (C_A, S_A, C_B, S_B)")
+    ca, sa, cb, sb = (sums[i].astype(np.float64) / float(1 << 30) for i in range(4))
+    n_a, n_b = float(n_sel[0]), float(n_sel[1])
+    zero = np.zeros_like(ca)
+    return {
+        "AA": (ca * ca + sa * sa) / n_a if n_a > 0 else zero.copy(),
+        "BB": (cb * cb + sb * sb) / n_b if n_b > 0 else zero.copy(),
+        "AB": (ca * cb + sa * sb) / np.sqrt(n_a * n_b) if n_a > 0 and n_b > 0 else zero.copy(),
+        "NN": ((ca + cb) ** 2 + (sa + sb) ** 2) / (n_a + n_b) if n_a + n_b > 0 else zero.copy(),
+    }
+
+
+def sq_radial(S, box_x: float, box_y: float, nbins: int, q_max: float):
+    """Radial average of one partial S[hmax + 1, 2 kmax + 1] (structure_factor's
+    grid: h = 0..hmax, k = -kmax..kmax) over |q|, q = 2 pi (h / box_x, k / box_y).
+
+    Bin b covers [b dq, (b + 1) dq), dq = q_max / nbins.  Every independent wave
+    vector counts once: q = 0 is left out; of the h = 0 row only k > 0 is used
+    (k < 0 are its Friedel copies, S(-q) = S(q)); every h > 0 vector is used.
+    Returns (bin centres, the mean S per bin — NaN where a bin is empty —, the
+    number of wave vectors per bin)."""
+    S = np.asarray(S, dtype=np.float64)
+    if S.ndim != 2 or S.shape[1] % 2 != 1 or nbins < 1 or not q_max > 0:
+        raise ValueError("sq_radial: S is [hmax + 1, 2 kmax + 1], nbins >= 1, q_max > 0")
+    kmax = S.shape[1] // 2
+    h = np.arange(S.shape[0], dtype=np.float64)[:, None]
+    k = np.arange(-kmax, kmax + 1, dtype=np.float64)[None, :]
+    q = 2.0 * np.pi * np.sqrt((h / box_x) ** 2 + (k / box_y) ** 2)
+    use = (h > 0) | (k > 0)
+    dq = q_max / nbins
+    b = np.floor(q / dq).astype(np.int64)
+    use &= b < nbins
+    count = np.bincount(b[use], minlength=nbins).astype(np.int64)
+    total = np.bincount(b[use], weights=S[use], minlength=nbins)
+    mean = np.divide(total, count, out=np.full(nbins, np.nan), where=count > 0)
+    return (np.arange(nbins, dtype=np.float64) + 0.5) * dq, mean, count

@@ -273,6 +273,16 @@ def geom_m(table) -> list:
     return [(int(hi) << 64) + int(lo) for lo, hi in zip(table["sum_m_lo"], table["sum_m_hi"])]
 
 
+SK_MAX = 64                           # KMC_SK_MAX: largest hmax / kmax of kmc_structure_factor
+SK_ALL, SK_BOUND = 0, 1               # KMC_SK_ALL / KMC_SK_BOUND (the proteins summed over)
+SK_SELECT = {"all": SK_ALL, "bound": SK_BOUND}
+
+
+def sk_select(select) -> int:
+    """'all' / 'bound' or the KMC_SK_* number itself, as the int32 the library takes."""
+    return SK_SELECT[select] if isinstance(select, str) else int(select)
+
+
 DD_ROW = 416     # KMC_DD_ROW: one exchanged protein (48 doubles + 8 int32)
 DD_JCAP = 256    # KMC_DD_JCAP
 DD_XCAP = 64     # KMC_DD_XCAP

@@ -15,6 +15,7 @@
 #include "kmc_kernels.hip"
 #include "kmc_analysis.hip"
 #include "kmc_geometry.hip"
+#include "kmc_structure.hip"
 #include "kmc_dynamics.hip"
 
 using namespace kmcd;
@@ -161,6 +162,8 @@ struct kmc_sim {
   GeoOut* geo_out = nullptr;
   kmc_cluster* geo_rows = nullptr;  // [geo_rows_cap] kmc_cluster_list's rows
   size_t geo_rows_cap = 0;
+  // structure factor (kmc_structure.hip): [4][SK_NQ_MAX] sums, then the two selection counts; its own, whatever N
+  unsigned long long* sk_sums = nullptr;
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   double an_ms = 0.0;
   // displacement tracking (kmc_dynamics.hip): scratch of the first
@@ -2457,6 +2460,55 @@ int kmc_cluster_list(kmc_sim* s, int32_t min_size, int64_t cap, kmc_cluster* row
     HIPCHK(s, hipMemcpy(rows, s->geo_rows, sizeof(kmc_cluster) * (size_t)*n, hipMemcpyDeviceToHost));
     std::sort(rows, rows + *n, [](const kmc_cluster& a, const kmc_cluster& b) { return a.label < b.label; });
   }
+  return KMC_OK;
+}
+
+// ---------------------------------------------------------------- structure factor
+// kmc_structure.hip: read-only like the analysis above, one launch on scratch of its own.
+
+static_assert(KMC_SK_MAX == SK_MAX, "kmc.h and kmc_structure.h agree on the grid limit");
+#define SK_NQ_MAX ((SK_MAX + 1) * (2 * SK_MAX + 1))
+
+int kmc_structure_factor(kmc_sim* s, int32_t hmax, int32_t kmax, int32_t select, int64_t* sums, int64_t n_sel[2]) {
+  if (!s) return KMC_ERR_ARG;
+  if (!sums || !n_sel || hmax < 0 || hmax > SK_MAX || kmax < 0 || kmax > SK_MAX ||
+      (select != KMC_SK_ALL && select != KMC_SK_BOUND))
+    return fail(s, KMC_ERR_ARG, "structure factor: sums and n_sel are needed, 0 <= hmax, kmax <= " +
+                                    std::to_string(SK_MAX) + ", select is KMC_SK_ALL or KMC_SK_BOUND");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  SkArgs a;
+  a.hmax = hmax;
+  a.kmax = kmax;
+  a.select = select;
+  a.W = 2 * kmax + 1;
+  a.nq = (hmax + 1) * a.W;
+  const int nqb = (a.nq + SK_QB - 1) / SK_QB;
+  a.qb = (a.nq + nqb - 1) / nqb;
+  a.nh_max = std::min(hmax + 1, (a.qb - 1) / a.W + 2);
+  a.E = a.nh_max + kmax + 1;
+  a.BX = (long long)kmcm::round_(s->K.box_x * 1024.0);
+  a.BY = (long long)kmcm::round_(s->K.box_y * 1024.0);
+  if (a.BX < 1 || a.BY < 1) return fail(s, KMC_ERR_ARG, "structure factor: the box is below 2^-10 A");
+  if (a.E > SK_E_MAX) return fail(s, KMC_ERR_CAPACITY, "structure factor: axis tables beyond SK_E_MAX");
+  if (!s->sk_sums && dalloc(s, &s->sk_sums, (size_t)4 * SK_NQ_MAX + 2) != KMC_OK)
+    return fail(s, KMC_ERR_HIP, "structure factor: scratch allocation failed");
+  const size_t nw = (size_t)4 * a.nq;
+  unsigned long long* d_nsel = s->sk_sums + (size_t)4 * SK_NQ_MAX;
+  const int ntile = (std::max(s->K.NA, s->K.NB) + SK_TILE - 1) / SK_TILE;
+  const dim3 grid((unsigned)std::max(1, std::min(ntile, SK_WG / nqb)), (unsigned)nqb);
+  const size_t lds = (sizeof(double2) * (size_t)SK_TILE * a.E + sizeof(longlong2) * SK_TILE + sizeof(int) * (SK_TILE + 1) + 15) / 16 * 16;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  hipStream_t st = s->stream;
+  HIPCHK(s, hipMemsetAsync(s->sk_sums, 0, sizeof(unsigned long long) * nw, st));
+  HIPCHK(s, hipMemsetAsync(d_nsel, 0, sizeof(unsigned long long) * 2, st));
+  k_sk_sums<<<grid, SK_T, lds, st>>>(s->K, s->d, a, s->sk_sums, d_nsel);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpy(sums, s->sk_sums, sizeof(int64_t) * nw, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(n_sel, d_nsel, sizeof(int64_t) * 2, hipMemcpyDeviceToHost));
   return KMC_OK;
 }
 

@@ -24,6 +24,7 @@
 #include "kmc_math.h"
 #include "kmc_philox.h"
 #include "kmc_state_hash.h"
+#include "kmc_structure.h"
 
 namespace {
 
@@ -841,6 +842,59 @@ int kmc_host_cluster_geometry(const kmc_params* p, const kmc_state_view* v, int3
     std::copy(sy.begin(), sy.end(), shift + n);
   }
   if (span) std::copy(sp.begin(), sp.end(), span);
+  return KMC_OK;
+}
+
+// Structure factor (include/kmc.h), sequential: per selected protein the axis
+// tables of h = 0..hmax and |k| = 0..kmax, then one term per wave vector added
+// to its species' sums.
+int kmc_host_structure_factor(const kmc_params* p, const kmc_state_view* v, int32_t hmax, int32_t kmax,
+                              int32_t select, int64_t* sums, int64_t n_sel[2]) {
+  if (!p || !v || !sums || !n_sel || !v->a_int || !v->b_int || !v->ra || !v->rb || p->n_a < 0 || p->n_b < 0 ||
+      hmax < 0 || hmax > KMC_SK_MAX || kmax < 0 || kmax > KMC_SK_MAX ||
+      (select != KMC_SK_ALL && select != KMC_SK_BOUND)) {
+    g_host_err = "structure factor: params, state, sums and n_sel are needed, 0 <= hmax, kmax <= 64, select 0 or 1";
+    return KMC_ERR_ARG;
+  }
+  const int na = p->n_a, nb = p->n_b, n = na + nb;
+  const int64_t B[2] = {(int64_t)kmcm::round_(p->box_x * 1024.0), (int64_t)kmcm::round_(p->box_y * 1024.0)};
+  if (B[0] < 1 || B[1] < 1) {
+    g_host_err = "structure factor: the box is below 2^-10 A";
+    return KMC_ERR_ARG;
+  }
+  const int W = 2 * kmax + 1;
+  const size_t nq = (size_t)(hmax + 1) * W;
+  std::memset(sums, 0, sizeof(int64_t) * 4 * nq);
+  n_sel[0] = n_sel[1] = 0;
+  double cx[KMC_SK_MAX + 1], sx[KMC_SK_MAX + 1], cy[KMC_SK_MAX + 1], sy[KMC_SK_MAX + 1];
+  for (int q = 0; q < n; ++q) {
+    const int sp = q < na ? 0 : 1;
+    if (select == KMC_SK_BOUND) {
+      bool bound;
+      if (q < na) bound = v->a_int[2 * (size_t)na + q] != 0 || v->a_int[4 * (size_t)na + q] != 0;
+      else {
+        bound = false;
+        for (int j = 2; j <= 4; ++j) bound = bound || v->b_int[(size_t)(4 + j - 1) * nb + (q - na)] != 0;
+      }
+      if (!bound) continue;
+    }
+    n_sel[sp] += 1;
+    const double x = q < na ? v->ra[RA(na, 1, 1, 0, q)] : v->rb[RB(nb, 1, 1, 0, q - na)];
+    const double y = q < na ? v->ra[RA(na, 1, 1, 1, q)] : v->rb[RB(nb, 1, 1, 1, q - na)];
+    const int64_t X = (int64_t)kmcm::round_(x * 1024.0), Y = (int64_t)kmcm::round_(y * 1024.0);
+    for (int h = 0; h <= hmax; ++h) kmcs::axis_phase(h, X, B[0], &cx[h], &sx[h]);
+    for (int k = 0; k <= kmax; ++k) kmcs::axis_phase(k, Y, B[1], &cy[k], &sy[k]);
+    int64_t* C = sums + (size_t)(2 * sp) * nq;
+    int64_t* S = sums + (size_t)(2 * sp + 1) * nq;
+    for (int h = 0; h <= hmax; ++h)
+      for (int k = -kmax; k <= kmax; ++k) {
+        const int ak = k < 0 ? -k : k;
+        int64_t tc, ts;
+        kmcs::term(cx[h], sx[h], cy[ak], sy[ak], k < 0, &tc, &ts);
+        C[(size_t)h * W + (k + kmax)] += tc;
+        S[(size_t)h * W + (k + kmax)] += ts;
+      }
+  }
   return KMC_OK;
 }
 

@@ -29,6 +29,10 @@
 //                              step size count sum_m_hi sum_m_lo      (Rg² = m / n² / 2^20 Å²)
 //                            and one line
 //                              step span n_spanning n_span_x n_span_y largest_size largest_span
+//           [--sq HMAX KMAX FILE]  every out_interval, the structure factor sums of every
+//                            protein (kmc_structure_factor, KMC_SK_ALL; 0 <= HMAX, KMAX <= 64),
+//                            appended like the census: one line per wave vector
+//                              step h k C_A S_A C_B S_B      (exact integers, terms in units of 2^-30)
 //           [--dyn EVERY RMAX NBINS FILE]  displacement tracking (kmc_track_*): the origin is
 //                            the state the process starts or resumes from (the tracker is
 //                            not checkpointed: a resume starts a new origin, every line
@@ -89,8 +93,8 @@ int main(int argc, char** argv) {
   kmc_params p;
   kmc_params_default(&p);
   int device = 0;
-  std::string state_path, census_path, rdf_path, dyn_path, geom_path;
-  int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0, geom_max = 0;
+  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path;
+  int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0, geom_max = 0, sq_hmax = 0, sq_kmax = 0;
   double rdf_rmax = 0.0, dyn_rmax = 0.0;
   int64_t dyn_every = 0;
   for (int i = 1; i < argc; ++i) {
@@ -131,6 +135,15 @@ int main(int argc, char** argv) {
       geom_path = next();
       if (geom_max < 2 || geom_max > KMC_GEOM_MAX_SIZE) {
         fprintf(stderr, "kmc_run: bad --geom %d\n", geom_max);
+        return 2;
+      }
+    }
+    else if (a == "--sq") {
+      sq_hmax = atoi(next().c_str());
+      sq_kmax = atoi(next().c_str());
+      sq_path = next();
+      if (sq_hmax < 0 || sq_hmax > KMC_SK_MAX || sq_kmax < 0 || sq_kmax > KMC_SK_MAX) {
+        fprintf(stderr, "kmc_run: bad --sq %d %d\n", sq_hmax, sq_kmax);
         return 2;
       }
     }
@@ -181,6 +194,7 @@ int main(int argc, char** argv) {
     if (!rdf_path.empty()) truncate(rdf_path.c_str());
     if (!dyn_path.empty()) truncate(dyn_path.c_str());
     if (!geom_path.empty()) truncate(geom_path.c_str());
+    if (!sq_path.empty()) truncate(sq_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
   }
@@ -195,6 +209,8 @@ int main(int argc, char** argv) {
   const int census_max = 63;  // census rows / columns: 0..63 receptors / ligands, more clamp into the last
   std::vector<int64_t> hist((size_t)(census_max + 1) * (census_max + 1)), pairs((size_t)rdf_nbins + 1);
   std::vector<kmc_geom_bin> geom((size_t)geom_max + 1);
+  const size_t sq_nq = (size_t)(sq_hmax + 1) * (2 * sq_kmax + 1);
+  std::vector<int64_t> sq(sq_path.empty() ? 0 : 4 * sq_nq);
   std::vector<int64_t> vh((size_t)KMC_TRACK_CLASSES * dyn_nbins + 1);
   if (!dyn_path.empty()) {
     rc = kmc_track_begin(s, 0.0);
@@ -273,6 +289,18 @@ int main(int argc, char** argv) {
                     (long long)geom[k].sum_m.hi, (unsigned long long)geom[k].sum_m.lo);
         fprintf(f, "%lld span %lld %lld %lld %d %d\n", (long long)step, (long long)g.n_spanning, (long long)g.n_span_x,
                 (long long)g.n_span_y, g.largest_size, g.largest_span);
+        fclose(f);
+      }
+      if (!sq_path.empty()) {
+        int64_t n_sel[2];
+        rc = kmc_structure_factor(s, sq_hmax, sq_kmax, KMC_SK_ALL, sq.data(), n_sel);
+        if (rc) return die(s, rc, "structure factor");
+        f = fopen(sq_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, sq_path.c_str());
+        for (size_t q = 0; q < sq_nq; ++q)
+          fprintf(f, "%lld %d %d %lld %lld %lld %lld\n", (long long)step, (int)(q / (2 * sq_kmax + 1)),
+                  (int)(q % (2 * sq_kmax + 1)) - sq_kmax, (long long)sq[q], (long long)sq[sq_nq + q],
+                  (long long)sq[2 * sq_nq + q], (long long)sq[3 * sq_nq + q]);
         fclose(f);
       }
       if (!dyn_path.empty()) {

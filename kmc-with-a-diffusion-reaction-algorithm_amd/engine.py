@@ -109,6 +109,9 @@ def load_library(path: Optional[str] = None):
     L.kmc_cluster_list.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, P(C.c_int64)]
     L.kmc_host_cluster_geometry.argtypes = [P(capi.Params), P(capi.StateView), C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int32, C.c_void_p, P(capi.Geom)]
+    L.kmc_structure_factor.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.kmc_host_structure_factor.argtypes = [P(capi.Params), P(capi.StateView), C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p]
     for f in ("kmc_host_math", "kmc_device_math"):
         getattr(L, f).argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
@@ -191,6 +194,25 @@ def host_cluster_geometry(params: capi.Params, hs: capi.HostState, max_size: int
                                                          shift.ctypes.data, span.ctypes.data, int(max_size),
                                                          table.ctypes.data, C.byref(out)))
     return label, np.ascontiguousarray(shift.T), span, table, out
+
+
+def _sk_buffers(hmax: int, kmax: int):
+    """(sums[4, hmax + 1, 2 kmax + 1] int64, n_sel[2] int64) for a structure factor call; a grid out of range
+    gets the smallest buffers (the library refuses the call before it writes)."""
+    ok = 0 <= int(hmax) <= capi.SK_MAX and 0 <= int(kmax) <= capi.SK_MAX
+    shape = (4, int(hmax) + 1, 2 * int(kmax) + 1) if ok else (4, 1, 1)
+    return np.zeros(shape, dtype=np.int64), np.zeros(2, dtype=np.int64)
+
+
+def host_structure_factor(params: capi.Params, hs: capi.HostState, hmax: int, kmax: int, select="all"):
+    """Structure factor sums of a host state, sequentially (kmc_host_structure_factor): (sums[4, hmax + 1,
+    2 kmax + 1] int64 — C_A, S_A, C_B, S_B —, n_sel[2] int64), as Simulation.structure_factor."""
+    sums, n_sel = _sk_buffers(hmax, kmax)
+    v = hs.view()
+    _host_check(load_library().kmc_host_structure_factor(C.byref(params), C.byref(v), int(hmax), int(kmax),
+                                                         capi.sk_select(select), sums.ctypes.data,
+                                                         n_sel.ctypes.data))
+    return sums, n_sel
 
 
 def host_dd_check(gid: np.ndarray, own: np.ndarray) -> int:
@@ -387,9 +409,21 @@ class Simulation:
         self._check(rc)
         return rows[: n.value]
 
+    # ---- static structure factor of the current state (kmc_structure.hip)
+    def structure_factor(self, hmax: int, kmax: int, select="all"):
+        """(sums[4, hmax + 1, 2 kmax + 1] int64: C_A, S_A, C_B, S_B at q = 2 pi (h / box_x, k / box_y), h = 0..hmax,
+        k = -kmax..kmax; n_sel[2] int64: the receptors and ligands summed over) — kmc_structure_factor.  select:
+        "all", or "bound" for the proteins that hold a bond.  The sums are exact integers (terms in units of
+        2^-30); analysis.structure_factor turns them into the partial S(q)."""
+        sums, n_sel = _sk_buffers(hmax, kmax)
+        self._check(load_library().kmc_structure_factor(self._h, int(hmax), int(kmax), capi.sk_select(select),
+                                                        sums.ctypes.data, n_sel.ctypes.data))
+        return sums, n_sel
+
     @property
     def analysis_ms(self) -> float:
-        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / unwrap / cluster_* call."""
+        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / unwrap / cluster_* /
+        structure_factor call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
     # ---- displacement tracking since a time origin (kmc_dynamics.hip; DESIGN.md §11)
