@@ -50,6 +50,12 @@ struct KParams {
   int dd;         // 1: this handle simulates one slab's window of a decomposed trajectory (kmc_dd_set_state):
                   // random streams keyed by the global reference index (Dev::gid), observables over the
                   // proteins this slab owns (Dev::dd_own); 0: the whole trajectory
+  int step_chain;    // 1 (default on the single-stream path; KMC_STEP_CHAIN=0 turns it off: the same results):
+                     // ukind[] / owner[] are kept from step to step and k_finalize reclassifies only the
+                     // proteins whose bonds changed; ignored in a decomposed window (dd)
+  int dbg_classify;  // debug (KMC_DEBUG_CLASSIFY=1): the kept ukind[] / owner[] are compared with the full
+                     // rule on every plain step (a difference latches ERR_RESOLVE)
+  int dbg_counts;    // diagnostics (KMC_DEBUG_COUNTS=1): the step chain's counters (Ctl::n_bfs_reg, n_chk_heavy)
 };
 
 // per-step control block in device memory (replayable without host writes)
@@ -88,6 +94,16 @@ struct Ctl {
   // decomposed trajectories (KParams::dd), since kmc_dd_set_state: collisions found between a unit this
   // slab owns and a unit it holds as a halo copy; bonds formed between an owned and a halo protein
   uint32_t dd_xcol, dd_xbond;
+  // incremental classification (KParams::step_chain): entries of Dev::ulog written by the last k_finalize;
+  // diagnostics: proteins k_finalize reclassified since the state was set
+  uint32_t n_ulog, n_reclass;
+  // the BFS in the leading workgroups of k_propose_free (step_chain): descriptors of cx_list at the start of
+  // the step (k_finalize; the parameters' workgroups walk these, the BFS threads handle what they append);
+  // diagnostics since the state was set: complexes registered by that BFS, heavy complexes listed by the
+  // parameters' thread
+  uint32_t n_cx0, n_bfs_reg, n_chk_heavy;
+  uint32_t n_cx1;  // descriptors when k_move_members ran: what k_complex_heavy's extent scan walks (its own
+                   // launch's overflow BFS appends behind them)
 };
 
 // One slab window's per-step exchange report (kmc_dd_finish; the layout of

@@ -442,6 +442,8 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
   rc |= dalloc(s, &d.cx_alive, NB);
   rc |= dalloc(s, &d.bfs_cand, NB);
   rc |= dalloc(s, &d.dlist, 2 * (size_t)N);
+  rc |= dalloc(s, &d.ulog, (size_t)N + NB);
+  rc |= dalloc(s, &d.cx_slot, NB);
   rc |= dalloc(s, &d.pend, N);
   rc |= dalloc(s, &d.ccnt, N);
   rc |= dalloc(s, &d.overflow, NB);
@@ -480,6 +482,7 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
   s->poison = po && *po == '1';
   const char* dc = getenv("KMC_DEBUG_COUNTS");
   s->debug_counts = dc && *dc == '1';
+  K.dbg_counts = s->debug_counts;
   const char* dsy = getenv("KMC_DEBUG_SYNC");
   s->debug_sync = dsy && *dsy == '1';
   const char* pc = getenv("KMC_DEBUG_PAIR_CHUNK");  // debug: kmc_pair_counts stages fewer points at a time
@@ -510,6 +513,13 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
     // than they hide: profiles/r06/ab_cx_stream3_*); KMC_CX_STREAM=0..3 forces a mode
     const char* cs = getenv("KMC_CX_STREAM");
     s->cx_stream = (cs && *cs) ? std::max(0, std::min(3, atoi(cs))) : ((int64_t)N >= CX_STREAM_N ? 3 : 0);
+    // the step's head off the serial chain: on the single-stream
+    // path by default; KMC_STEP_CHAIN=0: k_classify every step, as the side-stream
+    // modes and a decomposed window
+    const char* sc = getenv("KMC_STEP_CHAIN");
+    K.step_chain = !(sc && *sc == '0') && s->cx_stream == 0 && NB > 0 && (int64_t)N < (1ll << ULOG_SHIFT);
+    const char* dcl = getenv("KMC_DEBUG_CLASSIFY");
+    K.dbg_classify = dcl && *dcl == '1';
     const char* cpw = getenv("KMC_CX_PARAMS_WG");
     s->cx_params_wg = cpw && *cpw ? std::max(0, atoi(cpw)) : 0;
     const char* ht = getenv("KMC_DEBUG_HTAG");  // debug: fewer tagged home entries (the searched lookup)
@@ -1060,13 +1070,22 @@ static int launch_step(kmc_sim* s, bool re_sort) {
   // complexes: the previous step's k_finalize dissolved those whose bonds
   // changed; a full rebuild (after a re-sort, a new state, an undone chunk,
   // KMC_FULL_BFS) resets them all here
-  if (K.NB > 0 && (s->need_full || re_sort || s->always_full))
-    TIMED(KI_CX_KILL, (k_cx_kill<<<std::min(gN, 1024), T, 0, st>>>(K, d)));
+  const bool full = s->need_full || re_sort || s->always_full;
+  if (K.NB > 0 && full) TIMED(KI_CX_KILL, (k_cx_kill<<<std::min(gN, 1024), T, 0, st>>>(K, d)));
   s->need_full = false;
   // slots per thread of the per-slot passes k_classify / k_diss_observe
   const int per = K.N >= COARSE_N ? 4 : 1, gP = (K.N + T * per - 1) / (T * per);
-  if (per == 4) TIMED(KI_CLASSIFY, (k_classify<4><<<gP, T, 0, st>>>(K, d)));
-  else TIMED(KI_CLASSIFY, (k_classify<1><<<gP, T, 0, st>>>(K, d)));
+  // ukind[] / owner[] of every slot: each step, or (KParams::step_chain) only
+  // when the state or the slot numbering changed outside a step — a new
+  // state, a re-sort, an undone chunk — the previous step's k_finalize having
+  // reclassified the proteins whose bonds changed
+  if (!(K.step_chain && !K.dd) || full) {
+    if (per == 4) TIMED(KI_CLASSIFY, (k_classify<4><<<gP, T, 0, st>>>(K, d)));
+    else TIMED(KI_CLASSIFY, (k_classify<1><<<gP, T, 0, st>>>(K, d)));
+  } else if (K.dbg_classify) {
+    if (per == 4) k_classify_check<4><<<gP, T, 0, st>>>(K, d);
+    else k_classify_check<1><<<gP, T, 0, st>>>(K, d);
+  }
   // KI_PROPOSE brackets the whole proposal phase: every protein's R read and
   // R_new written once (the bench's roofline unit).  Complexes kept or newly
   // registered (k_bfs); their rigid-move parameters (cx_params, in the first
@@ -1080,7 +1099,11 @@ static int launch_step(kmc_sim* s, bool re_sort) {
     Bracket b_(s, KI_PROPOSE, st);
     const int gL = std::min(2048, (K.NB + T - 1) / T);  // grid-stride over the descriptor list
     const bool side = s->cx_stream != 0 && K.NB > 0 && !s->use_graphs;
-    if (K.NB > 0 && (!side || s->cx_stream == 3)) {
+    // the step chain (KParams::step_chain, one stream only): the BFS in the
+    // leading workgroups of k_propose_free, k_cx_check's tests in the
+    // parameters' thread, its extent flags in k_complex_heavy
+    const bool chain = K.step_chain && !K.dd;
+    if (K.NB > 0 && !chain && (!side || s->cx_stream == 3)) {
       TIMED(KI_BFS, (k_bfs<<<gB, T, 0, st>>>(K, d)));
     }
     const int gC = K.NB > 0 ? std::min(gL, 512) : 0;  // grid-stride over the descriptor list
@@ -1094,14 +1117,14 @@ static int launch_step(kmc_sim* s, bool re_sort) {
       hipStream_t sd = s->side;
       // cx_params only, alone (one thread per complex up to gL workgroups;
       // 512 / gL / 4 096 workgroups: equal at C5, 128 us, profiles/r06/ab_cx_params_wg_C5)
-      k_propose_free<<<gP3, T, 0, st>>>(K, d, gP3);
+      k_propose_free<0><<<gP3, T, 0, st>>>(K, d, gP3, 0);
       TIMED(KI_MOVE_MEMBERS, (k_move_members<<<gN, T, 0, st>>>(K, d)));
       HIPCHK(s, hipEventRecord(s->ev_fork, st));
       HIPCHK(s, hipStreamWaitEvent(sd, s->ev_fork, 0));
       TIMED_ON(KI_CX_CHECK, sd, (k_cx_check<<<gL, T, 0, sd>>>(K, d)));
       TIMED_ON(KI_CX_HEAVY, sd, (k_complex_heavy<<<1024, T, 0, sd>>>(K, d)));
       HIPCHK(s, hipEventRecord(s->ev_join, sd));
-      TIMED(KI_PROPOSE_FREE, (k_propose_free<<<gN, T, 0, st>>>(K, d, 0)));  // the free units
+      TIMED(KI_PROPOSE_FREE, (k_propose_free<0><<<gN, T, 0, st>>>(K, d, 0, 0)));  // the free units
       HIPCHK(s, hipStreamWaitEvent(st, s->ev_join, 0));
     } else if (side) {
       // the complex chain — BFS of the candidates, rigid-move parameters,
@@ -1115,14 +1138,14 @@ static int launch_step(kmc_sim* s, bool re_sort) {
       HIPCHK(s, hipEventRecord(s->ev_fork, st));
       HIPCHK(s, hipStreamWaitEvent(sd, s->ev_fork, 0));
       TIMED_ON(KI_BFS, sd, (k_bfs<<<gB, T, 0, sd>>>(K, d)));
-      k_propose_free<<<gC, T, 0, sd>>>(K, d, gC);  // cx_params only (the bracket of the id is the free units')
+      k_propose_free<0><<<gC, T, 0, sd>>>(K, d, gC, 0);  // cx_params only (the bracket of the id is the free units')
       if (s->cx_stream == 1) {
         TIMED_ON(KI_MOVE_MEMBERS, sd, (k_move_members<<<gN, T, 0, sd>>>(K, d)));
         TIMED_ON(KI_CX_CHECK, sd, (k_cx_check<<<gL, T, 0, sd>>>(K, d)));
         TIMED_ON(KI_CX_HEAVY, sd, (k_complex_heavy<<<1024, T, 0, sd>>>(K, d)));
       }
       HIPCHK(s, hipEventRecord(s->ev_join, sd));
-      TIMED(KI_PROPOSE_FREE, (k_propose_free<<<gN, T, 0, st>>>(K, d, 0)));  // the free units
+      TIMED(KI_PROPOSE_FREE, (k_propose_free<0><<<gN, T, 0, st>>>(K, d, 0, 0)));  // the free units
       HIPCHK(s, hipStreamWaitEvent(st, s->ev_join, 0));
       if (s->cx_stream == 2) {  // the members' streams after the free units', on the main stream
         TIMED(KI_MOVE_MEMBERS, (k_move_members<<<gN, T, 0, st>>>(K, d)));
@@ -1130,10 +1153,12 @@ static int launch_step(kmc_sim* s, bool re_sort) {
         TIMED(KI_CX_HEAVY, (k_complex_heavy<<<1024, T, 0, st>>>(K, d)));
       }
     } else {
-      TIMED(KI_PROPOSE_FREE, (k_propose_free<<<gC + gN, T, 0, st>>>(K, d, gC)));
+      const int gF = chain ? gB : 0;  // the BFS workgroups
+      if (chain) TIMED(KI_PROPOSE_FREE, (k_propose_free<1><<<gF + gC + gN, T, 0, st>>>(K, d, gC, gF)));
+      else TIMED(KI_PROPOSE_FREE, (k_propose_free<0><<<gC + gN, T, 0, st>>>(K, d, gC, 0)));
       if (K.NB > 0) {
         TIMED(KI_MOVE_MEMBERS, (k_move_members<<<gN, T, 0, st>>>(K, d)));
-        TIMED(KI_CX_CHECK, (k_cx_check<<<gL, T, 0, st>>>(K, d)));
+        if (!chain) TIMED(KI_CX_CHECK, (k_cx_check<<<gL, T, 0, st>>>(K, d)));
         TIMED(KI_CX_HEAVY, (k_complex_heavy<<<1024, T, 0, st>>>(K, d)));
       }
     }
@@ -1400,9 +1425,10 @@ int kmc_step(kmc_sim* s, int64_t nsteps, kmc_obs* out) {
     s->clusters_valid = true;
     if (s->debug_counts) {
       const uint32_t* l = s->ctl_host->last;
-      fprintf(stderr, "kmc step %lld: candidates %u conflicts %u pending-units %u rejected %u rxn-pairs %u rl-edges %u cis-edges %u bfs-overflow %u outliers %u (list growth 2^%d, replays %lld, snapshots %lld, forced rebuilds %u)\n",
+      fprintf(stderr, "kmc step %lld: candidates %u conflicts %u pending-units %u rejected %u rxn-pairs %u rl-edges %u cis-edges %u bfs-overflow %u outliers %u (list growth 2^%d, replays %lld, snapshots %lld, forced rebuilds %u, reclassified %u, bfs-registered %u, params-heavy %u)\n",
               (long long)s->step_done, l[0], l[1], l[2], l[3], l[4], l[5], l[6], l[7], s->ctl_host->last_outl, s->grow,
-              (long long)s->n_replays, (long long)s->n_snapshots, s->ctl_host->n_forced);
+              (long long)s->n_replays, (long long)s->n_snapshots, s->ctl_host->n_forced, s->ctl_host->n_reclass,
+              s->ctl_host->n_bfs_reg, s->ctl_host->n_chk_heavy);
       if (s->K.dbg_cand) {
         const uint32_t* c = s->ctl_host->cand_kind;
         const uint32_t* r = s->ctl_host->rxn_kind;
@@ -1484,6 +1510,20 @@ int kmc_get_clusters(kmc_sim* s, int32_t* row_len, int32_t* members) {
   std::vector<int32_t> off(NB), size(NB), mem(N), id_of(N), slot_of(N);
   HIPCHK(s, hipStreamSynchronize(s->stream));
   HIPCHK(s, hipMemcpy(kind.data(), s->d.ukind, N, hipMemcpyDeviceToHost));
+  if (s->K.step_chain && !s->K.dd) {
+    // ukind[] already holds the next step's kinds where k_finalize
+    // reclassified: the finished step's kinds of those ligand slots are in
+    // its log (the control block is read back with every chunk)
+    std::vector<int32_t> ulog(std::min<size_t>(s->ctl_host->n_ulog, (size_t)N + NB));
+    if (!ulog.empty())
+      HIPCHK(s, hipMemcpy(ulog.data(), s->d.ulog, sizeof(int32_t) * ulog.size(), hipMemcpyDeviceToHost));
+    // (a dissolved root that was then reclassified has two entries, U_COMPLEX from the dissolve and
+    // the U_NONE the dissolve left: U_COMPLEX, applied last, is its kind in the finished step)
+    for (int pass = 0; pass < 2; ++pass)
+      for (const int32_t e : ulog)
+        if (((uint8_t)(e >> ULOG_SHIFT) == U_COMPLEX) == (pass == 1))
+          kind[e & ((1 << ULOG_SHIFT) - 1)] = (uint8_t)(e >> ULOG_SHIFT);
+  }
   HIPCHK(s, hipMemcpy(off.data(), s->d.cx_off, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
   HIPCHK(s, hipMemcpy(size.data(), s->d.cx_size, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
   std::vector<int32_t> shuf(s->d.mcap);

@@ -67,10 +67,14 @@ struct Dev {
   uint32_t* cx_alive;  // [NB] 1 while ligand lb roots a registered complex
   uint32_t* bfs_cand;  // [NB] step tag: ligand lb runs the BFS this step
   int32_t* dlist;    // [2][N] proteins whose bonds changed during step s (list s & 1)
+  int32_t* ulog;     // [N + NB] slot | kind << ULOG_SHIFT of the ligand slots whose unit kind (U_FREE_B, U_COMPLEX)
+                     // the last k_finalize replaced (KParams::step_chain): kmc_get_clusters reads the finished
+                     // step's kinds through it
   uint32_t* pend;    // [N] round tag: unit still waiting (resolution pass C)
   unsigned long long* ccnt;  // [N] round 0 of unit u's conflict entries (k_col_resolve; 0 between steps)
   int32_t* overflow; // [NB]
   int4* cx_list;     // [NB] descriptors of the registered complexes (kept across steps; cx_params, k_cx_check)
+  int32_t* cx_slot;  // [NB] by root: its descriptor's index in cx_list (the dissolve marks it dead: y = -1)
   int4* cx_heavy;    // [NB] descriptors for k_complex_heavy: larger complexes, and those k_cx_check
                      //      moved but whose lay-down / alignment changes beads
   // Home list (§records): every protein has a home position hp in an order
@@ -235,11 +239,60 @@ __device__ __forceinline__ uint32_t wave_alloc(uint32_t* ctr, uint32_t qn) {
 // ================================================================ 1. classify
 // Unit kinds, main.cpp:584 (free receptor), 682-686 (cis dimer, moved at the
 // lower index), 905 (single ligand = BFS component of size 1).
-// CLASSIFY_PER slots per thread (their first loads issued together; chosen as
-// k_diss_observe's count)
-template <int CLASSIFY_PER>
-__global__ void k_classify(KParams P, Dev d) {
+// The rule for slot p, given its links n2, n3 (receptor: nei2, nei3; ligand:
+// nei2, nei3), s2 (receptor: st2 | st3; ligand: nei4) and r, the root of its
+// registered complex (croot without the flag, -1: none): the unit kind and
+// the owner key (-1: member of a complex the BFS registers this step).  It
+// reads, beyond its arguments, the cis partner's nei2 / nei3 and id_of.
+__device__ __forceinline__ void classify_rule(const KParams& P, const Dev& d, int p, int n2, int n3, int s2, int r,
+                                              uint8_t& kind, int& ownkey) {
+  const int NA = P.NA;
+  kind = U_NONE;
+  int own = -1;
+  if (p < NA) {
+    const int i = p;
+    if (s2 == 0) {
+      kind = U_FREE_A;
+      own = p;
+    } else if (n2 == 0 && n3 != 0 && A_NEI3(d, n3 - 1) == i + 1 && A_NEI2(d, n3 - 1) == 0) {
+      int q = n3 - 1;
+      const bool lead = d.id_of[i] < d.id_of[q];  // moved at the lower reference index
+      own = lead ? i : q;
+      kind = lead ? U_DIMER : U_DIMER_P;
+    }
+  } else if (n2 == 0 && n3 == 0 && s2 == 0) {
+    kind = U_FREE_B;
+    own = p;
+  }
+  // a member of a complex registered in an earlier step and untouched since
+  // (dissolved otherwise): its unit is that complex (new ones are registered
+  // by the BFS)
+  if (r >= 0) {
+    own = r;
+    if (r == p) kind = U_COMPLEX;
+  }
+  ownkey = own < 0 ? -1 : d.id_of[own];
+}
+// the rule's arguments of slot p (croot apart)
+__device__ __forceinline__ void classify_links(const KParams& P, const Dev& d, int p, int& n2, int& n3, int& s2) {
   const int NA = P.NA, NB = P.NB;
+  if (p < NA) {
+    n2 = A_NEI2(d, p);
+    n3 = A_NEI3(d, p);
+    s2 = A_ST2(d, p) | A_ST3(d, p);
+  } else {
+    const int b = p - NA;
+    n2 = B_NEI(d, b, 2);
+    n3 = B_NEI(d, b, 3);
+    s2 = B_NEI(d, b, 4);
+  }
+}
+
+// CLASSIFY_PER slots per thread (their first loads issued together; chosen as
+// k_diss_observe's count).  CHECK (KMC_DEBUG_CLASSIFY): nothing is written,
+// the kept ukind[] / owner[] are compared with the rule instead.
+template <int CLASSIFY_PER, bool CHECK>
+__device__ __forceinline__ void classify_slots(const KParams& P, const Dev& d) {
   const int p0 = blockIdx.x * blockDim.x * CLASSIFY_PER + threadIdx.x;
   // the links / statuses and complex root of every slot of this thread first
   int n2[CLASSIFY_PER], n3[CLASSIFY_PER], s2[CLASSIFY_PER], r[CLASSIFY_PER];
@@ -249,16 +302,7 @@ __global__ void k_classify(KParams P, Dev d) {
     n2[k] = n3[k] = s2[k] = 0;
     r[k] = -1;
     if (p >= P.N) continue;
-    if (p < NA) {
-      n2[k] = A_NEI2(d, p);
-      n3[k] = A_NEI3(d, p);
-      s2[k] = A_ST2(d, p) | A_ST3(d, p);
-    } else {
-      const int b = p - NA;
-      n2[k] = B_NEI(d, b, 2);
-      n3[k] = B_NEI(d, b, 3);
-      s2[k] = B_NEI(d, b, 4);
-    }
+    classify_links(P, d, p, n2[k], n3[k], s2[k]);
     r[k] = d.croot[p];
     if (r[k] >= 0) r[k] &= ~CROOT_BIG;
   }
@@ -266,33 +310,24 @@ __global__ void k_classify(KParams P, Dev d) {
   for (int k = 0; k < CLASSIFY_PER; ++k) {
     const int p = p0 + k * (int)blockDim.x;
     if (p >= P.N) continue;
-    uint8_t kind = U_NONE;
-    int own = -1;
-    if (p < NA) {
-      const int i = p;
-      if (s2[k] == 0) {
-        kind = U_FREE_A;
-        own = p;
-      } else if (n2[k] == 0 && n3[k] != 0 && A_NEI3(d, n3[k] - 1) == i + 1 && A_NEI2(d, n3[k] - 1) == 0) {
-        int q = n3[k] - 1;
-        const bool lead = d.id_of[i] < d.id_of[q];  // moved at the lower reference index
-        own = lead ? i : q;
-        kind = lead ? U_DIMER : U_DIMER_P;
-      }
-    } else if (n2[k] == 0 && n3[k] == 0 && s2[k] == 0) {
-      kind = U_FREE_B;
-      own = p;
+    uint8_t kind;
+    int ownkey;
+    classify_rule(P, d, p, n2[k], n3[k], s2[k], r[k], kind, ownkey);
+    if (CHECK) {
+      if (d.ukind[p] != kind || d.owner[p] != ownkey) atomicOr(&d.ctl->err, ERR_RESOLVE);
+    } else {
+      d.ukind[p] = kind;
+      d.owner[p] = ownkey;
     }
-    // a member of a complex registered in an earlier step and untouched since
-    // (dissolved otherwise): its unit is that complex (new ones are registered
-    // by k_bfs)
-    if (r[k] >= 0) {
-      own = r[k];
-      if (r[k] == p) kind = U_COMPLEX;
-    }
-    d.ukind[p] = kind;
-    d.owner[p] = own < 0 ? -1 : d.id_of[own];  // -1: member of a complex k_bfs registers this step
   }
+}
+template <int CLASSIFY_PER>
+__global__ void k_classify(KParams P, Dev d) {
+  classify_slots<CLASSIFY_PER, false>(P, d);
+}
+template <int CLASSIFY_PER>
+__global__ void k_classify_check(KParams P, Dev d) {
+  classify_slots<CLASSIFY_PER, true>(P, d);
 }
 
 // Complexes are kept from step to step: a BFS row depends only on the bond
@@ -312,11 +347,20 @@ __device__ __forceinline__ void cx_reset_all(const KParams& P, const Dev& d, uin
   if (tid == 0) {
     d.ctl->cx_cursor = 0;
     d.ctl->n_cx = 0;
+    d.ctl->n_cx0 = 0;
     d.ctl->full_now = 1;
   }
 }
 __global__ void k_cx_kill(KParams P, Dev d) {
   cx_reset_all(P, d, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+// the descriptor of the dissolved complex rooted at ligand b, marked dead in
+// cx_list (row offset -1: no longer current, whatever its root becomes) — so
+// that the parameters' workgroups can tell without reading what a BFS
+// running beside them in the same launch writes (cx_alive, cx_off)
+__device__ __forceinline__ void cx_desc_kill(const Dev& d, int b) {
+  const uint32_t sl = (uint32_t)d.cx_slot[b];
+  if (sl < d.mcap / 2) d.cx_list[sl].y = -1;
 }
 // the complexes of the proteins whose bonds changed during `step` (dirty list
 // step & 1), dissolved for step + 1 (k_finalize's workgroup)
@@ -329,11 +373,95 @@ __device__ __forceinline__ void cx_dissolve_dirty(const KParams& P, const Dev& d
     const int r = d.croot[p] & ~CROOT_BIG;
     if (r < 0 || atomicExch(&d.cx_alive[r - NA], 0u) != 1u) continue;
     const int b = r - NA, off = d.cx_off[b], sz = d.cx_size[b];
+    cx_desc_kill(d, b);
     for (int i = 0; i < sz; ++i) {
       const int m = d.members[off + i];
       d.croot[m] = -1;
       if (m >= NA) d.bfs_cand[m - NA] = next;
     }
+  }
+}
+
+// Incremental classification (KParams::step_chain): ukind[] / owner[] are
+// kept from step to step, and k_finalize brings them to the next step's
+// values where the rule's inputs changed — the listed proteins (own links),
+// a listed receptor's cis partner (the partner's nei2 / nei3) and the members
+// of the dissolved complexes (croot) — so a plain step launches no k_classify.
+#define ULOG_SHIFT 28  // Dev::ulog entries: slot | kind << ULOG_SHIFT (step_chain needs N < 2^28)
+__device__ __forceinline__ void reclass_store(const Dev& d, int p, uint8_t kind, int ownkey, uint32_t* nlog) {
+  const uint8_t old = d.ukind[p];
+  // every ligand slot whose kind changes to or from U_FREE_B / U_COMPLEX, with the kind it had (a second
+  // writer of p stores the same new kind and logs nothing; a dissolved root was logged as U_COMPLEX by the
+  // dissolve and reads U_NONE here: kmc_get_clusters lets the U_COMPLEX entry win)
+  const bool unit = old == U_FREE_B || old == U_COMPLEX || kind == U_FREE_B || kind == U_COMPLEX;
+  if (old != kind && unit) d.ulog[atomicAdd(nlog, 1u)] = p | (int)old << ULOG_SHIFT;
+  d.ukind[p] = kind;
+  d.owner[p] = ownkey;
+}
+__device__ __forceinline__ void reclass_one(const KParams& P, const Dev& d, int p, uint8_t& kind, int& ownkey) {
+  int n2, n3, s2;
+  classify_links(P, d, p, n2, n3, s2);
+  classify_rule(P, d, p, n2, n3, s2, -1, kind, ownkey);
+}
+// cx_dissolve_dirty with the reclassification, k_finalize's workgroup (nlog,
+// nrec: LDS counters, zero).  The lower half of the workgroup dissolves: a
+// member of a dissolved complex is bonded, so unless it is listed (or a
+// listed receptor's partner) its kind is U_NONE and its owner the BFS's to
+// write.  The upper half meanwhile evaluates the rule for the listed proteins
+// and their cis partners — all of them without a complex now: a listed
+// protein's complex is dissolved, and its cis partner is either in the same
+// complex or listed itself — and stores after the dissolve, so the rule's
+// loads are not on the workgroup's critical path.
+__device__ __forceinline__ void cx_dissolve_reclass(const KParams& P, const Dev& d, uint32_t step, uint32_t* nlog,
+                                                    uint32_t* nrec) {
+  const int NA = P.NA, NB = P.NB;
+  const uint32_t li = step & 1, n = min(d.ctl->n_dirty[li], (uint32_t)P.N), next = step + 1;
+  const uint32_t half = blockDim.x / 2;
+  const bool upper = threadIdx.x >= half;
+  int p0 = -1, q0 = -1, o0 = -1, oq = -1;
+  uint8_t k0 = U_NONE, kq = U_NONE;
+  if (!upper) {
+    for (uint32_t t = threadIdx.x; t < n; t += half) {
+      const int p = d.dlist[(size_t)li * P.N + t];
+      if (p >= NA) d.bfs_cand[p - NA] = next;
+      const int r = d.croot[p] & ~CROOT_BIG;
+      if (r < 0 || atomicExch(&d.cx_alive[r - NA], 0u) != 1u) continue;
+      const int b = r - NA, off = d.cx_off[b], sz = d.cx_size[b];
+      cx_desc_kill(d, b);
+      d.ulog[atomicAdd(nlog, 1u)] = r | (int)U_COMPLEX << ULOG_SHIFT;
+      for (int i = 0; i < sz; ++i) {
+        const int m = d.members[off + i];
+        d.croot[m] = -1;
+        d.ukind[m] = U_NONE;
+        d.owner[m] = -1;
+        if (m >= NA) d.bfs_cand[m - NA] = next;
+      }
+      atomicAdd(nrec, (uint32_t)sz);
+    }
+  } else if (threadIdx.x - half < n) {
+    p0 = d.dlist[(size_t)li * P.N + (threadIdx.x - half)];
+    const int q = p0 < NA ? A_NEI3(d, p0) : 0;
+    reclass_one(P, d, p0, k0, o0);
+    if (q > 0) {
+      q0 = q - 1;
+      reclass_one(P, d, q0, kq, oq);
+    }
+  }
+  __syncthreads();
+  if (p0 >= 0) reclass_store(d, p0, k0, o0, nlog);
+  if (q0 >= 0) reclass_store(d, q0, kq, oq, nlog);
+  if (p0 >= 0) atomicAdd(nrec, q0 >= 0 ? 2u : 1u);
+  // (a list longer than half the workgroup: the rest after the dissolve)
+  for (uint32_t t = half + threadIdx.x; t < n; t += blockDim.x) {
+    const int p = d.dlist[(size_t)li * P.N + t];
+    const int q = p < NA ? A_NEI3(d, p) : 0;
+    reclass_one(P, d, p, k0, o0);
+    reclass_store(d, p, k0, o0, nlog);
+    if (q > 0) {
+      reclass_one(P, d, q - 1, kq, oq);
+      reclass_store(d, q - 1, kq, oq, nlog);
+    }
+    atomicAdd(nrec, q > 0 ? 2u : 1u);
   }
 }
 
@@ -387,7 +515,7 @@ __device__ __forceinline__ void nbrs3(const KParams& P, const Dev& d, int x, int
 // of at most CXL members take the streamed path, larger ones the
 // global-memory path of k_complex_heavy).
 template <int STRIDE = 1>
-__device__ __forceinline__ void register_complex(const KParams& P, const Dev& d, int p, const int* q, int qn) {
+__device__ __forceinline__ int4 register_complex(const KParams& P, const Dev& d, int p, const int* q, int qn) {
   const int NA = P.NA, NB = P.NB;
   uint32_t off = wave_alloc(&d.ctl->cx_cursor, (uint32_t)qn);
   if (off + qn > d.mcap) {  // cannot happen below mcap / 2 + N (k_cx_kill): the step is undone (kmc_step)
@@ -454,8 +582,10 @@ __device__ __forceinline__ void register_complex(const KParams& P, const Dev& d,
   // while its root is alive with the same row offset (cx_current checks)
   const int4 desc = make_int4(b, (int)off, qn | nb << 16, rootid);
   const uint32_t slot = wave_slot(&d.ctl->n_cx);
+  d.cx_slot[b] = (int)slot;
   if (slot < d.mcap / 2) d.cx_list[slot] = desc;
   else atomicOr(&d.ctl->err, ERR_MEMBERS);
+  return desc;
 }
 
 // One thread per bonded ligand; the queue lives in LDS, one column per thread
@@ -464,13 +594,15 @@ __device__ __forceinline__ void register_complex(const KParams& P, const Dev& d,
 // over the finished queue (independent loads), so each BFS node costs one
 // round of link loads.  Components larger than BFS_QCAP go to the overflow
 // path.
-__global__ void __launch_bounds__(256) k_bfs(KParams P, Dev d) {
-  __shared__ int qs[BFS_QCAP * 256];
+// The BFS of ligand b (qs: the workgroup's BFS_QCAP x 256 LDS queue); true and
+// the descriptor when b roots a component of at most BFS_QCAP members, which
+// is then registered.  The body of k_bfs and of the BFS workgroups of
+// k_propose_free.
+__device__ __forceinline__ bool bfs_one(const KParams& P, const Dev& d, int b, int* qs, int4& desc) {
   const int NA = P.NA, NB = P.NB;
-  int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= NB) return;
-  if (!d.ctl->full_now && d.bfs_cand[b] != d.ctl->step) return;  // its complex is kept (k_cx_kill)
-  if (B_NEI(d, b, 2) == 0 && B_NEI(d, b, 3) == 0 && B_NEI(d, b, 4) == 0) return;
+  if (b >= NB) return false;
+  if (!d.ctl->full_now && d.bfs_cand[b] != d.ctl->step) return false;  // its complex is kept (k_cx_kill)
+  if (B_NEI(d, b, 2) == 0 && B_NEI(d, b, 3) == 0 && B_NEI(d, b, 4) == 0) return false;
   int* q = qs + threadIdx.x;  // q[t * 256]
   int p = NA + b;
   const int pid = d.id_of[p];
@@ -516,18 +648,24 @@ __global__ void __launch_bounds__(256) k_bfs(KParams P, Dev d) {
         }
         bloom |= bit;
         if (qn == BFS_QCAP) {
-          if (lower(qn) || (v >= NA && d.id_of[v] < pid)) return;
+          if (lower(qn) || (v >= NA && d.id_of[v] < pid)) return false;
           uint32_t s = atomicAdd(&d.ctl->n_overflow, 1u);
           d.overflow[s] = b;
-          return;
+          return false;
         }
         q[(qn++) * 256] = v;
       }
     }
     head += nb;
   }
-  if (lower(qn)) return;
-  register_complex<256>(P, d, p, q, qn);
+  if (lower(qn)) return false;
+  desc = register_complex<256>(P, d, p, q, qn);
+  return true;
+}
+__global__ void __launch_bounds__(256) k_bfs(KParams P, Dev d) {
+  __shared__ int qs[BFS_QCAP * 256];
+  int4 desc;
+  bfs_one(P, d, blockIdx.x * blockDim.x + threadIdx.x, qs, desc);
 }
 
 // Component of overflow entry o (larger than BFS_QCAP): one thread, global
@@ -2068,15 +2206,103 @@ __device__ __forceinline__ bool cx_current(const Dev& d, int4 desc) {
 #ifndef CXP_BATCH  // members whose beads cx_params holds in registers at once (its VGPRs bound k_propose_free's)
 #define CXP_BATCH 4
 #endif
-__device__ __forceinline__ void cx_params(const KParams& P, const Dev& d, uint32_t first, uint32_t stride) {
-  const uint32_t n = d.ctl->n_cx, step = d.ctl->step;
-  for (uint32_t c = first; c < n; c += stride) {
-    const int4 desc = d.cx_list[c];
-    if (!cx_current(d, desc)) continue;
+// a streamed complex's rigid move: the parameters (cxp[root]) and one bead
+// moved with them — the one expression of k_move_members and of the
+// parameters' thread's checks (same operands, same order: the same bits)
+struct CxMove {
+  double dx, dy, PBx, PBy, cmx, cmy, cmz;
+  Rot t;
+};
+__device__ __forceinline__ void cx_move_bead(const CxMove& M, double x, double y, double z, double& nx, double& ny,
+                                             double& nz) {
+  const double ox = (x + M.dx) - M.PBx, oy = (y + M.dy) - M.PBy;
+  nx = rx(M.t, ox, oy, z, M.cmx, M.cmy, M.cmz);
+  ny = ry(M.t, ox, oy, z, M.cmx, M.cmy, M.cmz);
+  nz = rz(M.t, ox, oy, z, M.cmx, M.cmy, M.cmz);
+}
+__device__ __forceinline__ double dxy_(double ax, double ay, double bx, double by) {
+  const double dx = ax - bx, dy = ay - by;
+  return kmcm::sqrt_(dx * dx + dy * dy);
+}
+
+#define CX_EXT_HEAVY 2u  // cx_ext bit: the complex is on the heavy list this step (bit 0: k_move_members' extent flag)
+
+// k_cx_check's tests of the one-ligand complex rooted at lb (the lay-down test
+// 1141, the three bond sites' bond_misaligned, cis_misaligned) by the thread
+// that has its parameters in registers: the beads the tests read — the
+// ligand's; of each bonded receptor and its cis partner the [3][1..3] beads —
+// are loaded from R and moved as k_move_members will move them.  The tests
+// are pure, so only the bonded sites are visited, one at a time (a loop: all
+// three sites' rows in registers at once cost k_propose_free a wave per
+// SIMD): the links and the ligand's [1][k] rows first, then per site one
+// round for the ligand's and the receptor's rows and the cis link, one for
+// the cis partner's rows.
+__device__ __forceinline__ bool cx_check_moved(const KParams& P, const Dev& d, const CxMove& M, int lb) {
+  const int NA = P.NA, NB = P.NB;
+  const Beads& R = d.cur;
+  // ligand bead (j, k), j = 1..4, k = 1..2: xy row (j-1)*2 + (k-1), z in row 8 + ((j-1)>>1)*2 + (k-1), half (j-1)&1;
+  // receptor bead (3, k): xy row 8 + (k-1), z the first half of row 20 + (k-1)
+  const int a1r0 = B_NEI(d, lb, 2), a1r1 = B_NEI(d, lb, 3), a1r2 = B_NEI(d, lb, 4);
+  {
+    const double2 xy1 = R.B2(lb, 0), xy2 = R.B2(lb, 1);
+    const double z1 = R.B(lb, 1, 1, 2), z2 = R.B(lb, 1, 2, 2);
+    double nx, ny, nz1, nz2;
+    cx_move_bead(M, xy1.x, xy1.y, z1, nx, ny, nz1);
+    cx_move_bead(M, xy2.x, xy2.y, z2, nx, ny, nz2);
+    if (nz2 != (nz1 + P.rb)) return true;
+  }
+#pragma unroll 1
+  for (int j = 0; j < 3; ++j) {
+    const int a1ref = j == 0 ? a1r0 : j == 1 ? a1r1 : a1r2;
+    if (a1ref <= 0) continue;
+    const int a1 = a1ref - 1, a2ref = A_NEI3(d, a1);
+    const double2 l1 = R.B2(lb, (j + 1) * 2), l2 = R.B2(lb, (j + 1) * 2 + 1);
+    const double lz1 = R.B(lb, j + 2, 1, 2), lz2 = R.B(lb, j + 2, 2, 2);
+    double2 axy[2];
+    double az[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      axy[k] = R.A2(a1, 8 + k);
+      az[k] = R.A(a1, 3, k + 1, 2);
+    }
+    double lx1, ly1, lx2, ly2, ax[3], ay[3], nz;
+    cx_move_bead(M, l1.x, l1.y, lz1, lx1, ly1, nz);
+    cx_move_bead(M, l2.x, l2.y, lz2, lx2, ly2, nz);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) cx_move_bead(M, axy[k].x, axy[k].y, az[k], ax[k], ay[k], nz);
+    // bond_misaligned(lb, j + 2, a1): ligand [j+2][2] vs receptor [3][2], ligand [j+2][1] vs receptor [3][1]
+    const double dd2 = dxy_(lx2, ly2, ax[1], ay[1]);
+    const double dd1 = dxy_(lx1, ly1, ax[0], ay[0]);
+    if (bond_mis_d(P, dd1, dd2)) return true;
+    if (a2ref == 0) continue;
+    const int a2 = a2ref - 1;
+    // (the receptor's own [3][3] bead with its partner's rows: only the cis test reads it)
+    const double2 c1 = R.A2(a2, 8), c3 = R.A2(a2, 10), a3 = R.A2(a1, 10);
+    const double cz1 = R.A(a2, 3, 1, 2), cz3 = R.A(a2, 3, 3, 2), az3 = R.A(a1, 3, 3, 2);
+    double x1, y1, x3, y3;
+    cx_move_bead(M, a3.x, a3.y, az3, ax[2], ay[2], nz);
+    cx_move_bead(M, c1.x, c1.y, cz1, x1, y1, nz);
+    cx_move_bead(M, c3.x, c3.y, cz3, x3, y3, nz);
+    // cis_misaligned(a1, a2): [3][3] vs [3][3], [3][1] vs [3][1]
+    const double cd2 = dxy_(ax[2], ay[2], x3, y3);
+    const double cd1 = dxy_(ax[0], ay[0], x1, y1);
+    if (!AreSame(cd1, P.cis_cut / 2 + P.ra + P.ra) || !AreSame(cd2, P.cis_cut / 2)) return true;
+  }
+  return false;
+}
+
+// The parameters of the complex of descriptor desc (current).  CHAIN
+// (KParams::step_chain): the thread also makes k_cx_check's decision — a
+// complex of several ligands, or one whose tests fail on the moved beads,
+// goes onto the heavy list as moved, its cx_ext word saying so.
+template <bool CHAIN>
+__device__ __forceinline__ void cx_params_one(const KParams& P, const Dev& d, const int4 desc, uint32_t step) {
+  {
     const int csize = desc.z & 0xffff, nB = desc.z >> 16, nA = csize - nB;
+    if (csize == 0) return;  // (a registration that overflowed members[]: the step is undone)
     if (csize > CXL) {  // the global-memory path: rigid move and alignment in k_complex_heavy
       d.cx_heavy[atomicAdd(&d.ctl->n_heavy, 1u)] = desc;
-      continue;
+      return;
     }
     double u0, u1, u2, u3;
     const uint32_t rk = rkey(P, d, desc.w);
@@ -2144,6 +2370,29 @@ __device__ __forceinline__ void cx_params(const KParams& P, const Dev& d, uint32
     for (int a = 0; a < 3; ++a)
 #pragma unroll
       for (int b = 0; b < 3; ++b) o[7 + a * 3 + b] = t.t[a][b];
+    if (CHAIN) {
+      bool heavy = nB != 1;
+      if (!heavy) heavy = cx_check_moved(P, d, CxMove{dx, dy, PBx, PBy, cmx, cmy, cmz, t}, desc.x);
+      if (heavy) {
+        d.cx_ext[desc.x] = CX_EXT_HEAVY;  // (zero between steps; k_move_members, the next launch, may set bit 0)
+        d.cx_heavy[atomicAdd(&d.ctl->n_heavy, 1u)] = make_int4(desc.x | CXD_MOVED, desc.y, desc.z, desc.w);
+        if (P.dbg_counts) atomicAdd(&d.ctl->n_chk_heavy, 1u);
+      }
+    }
+  }
+}
+// complexes c = first, first + stride, ... of the descriptor list.  CHAIN: of
+// the descriptors the step began with — the BFS beside these workgroups
+// appends behind them and handles what it registers itself; a descriptor is
+// current unless the dissolve marked it (cx_desc_kill), so nothing the BFS
+// writes is read here.
+template <bool CHAIN>
+__device__ __forceinline__ void cx_params(const KParams& P, const Dev& d, uint32_t first, uint32_t stride) {
+  const uint32_t n = CHAIN ? d.ctl->n_cx0 : d.ctl->n_cx, step = d.ctl->step;
+  for (uint32_t c = first; c < n; c += stride) {
+    const int4 desc = d.cx_list[c];
+    if (CHAIN ? desc.y < 0 : !cx_current(d, desc)) continue;
+    cx_params_one<CHAIN>(P, d, desc, step);
   }
 }
 
@@ -2160,12 +2409,11 @@ __device__ __forceinline__ void move_member(const KParams& P, const Dev& d, int 
   double2 r[ROWS];
 #pragma unroll
   for (int w = 0; w < ROWS; ++w) r[w] = ld_r(src[bead_elem(i, w, n, ROWS)]);
-  const double dx = cp[0], dy = cp[1], PBx = cp[2], PBy = cp[3], cmx = cp[4], cmy = cp[5], cmz = cp[6];
-  Rot t;
+  CxMove M{cp[0], cp[1], cp[2], cp[3], cp[4], cp[5], cp[6], Rot{}};
 #pragma unroll
   for (int a = 0; a < 3; ++a)
 #pragma unroll
-    for (int b = 0; b < 3; ++b) t.t[a][b] = cp[7 + a * 3 + b];
+    for (int b = 0; b < 3; ++b) M.t.t[a][b] = cp[7 + a * 3 + b];
   // both records (the new one is rewritten by k_complex_heavy when the
   // complex's lay-down / alignment changes beads): reference point [1][1]
   // (row 0), z span of the domain centres (rows 16, 20: z of [1..4][1]) or the
@@ -2191,12 +2439,12 @@ __device__ __forceinline__ void move_member(const KParams& P, const Dev& d, int 
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
       const int r1 = 2 * jp * NK + k, r2 = (2 * jp + 1) * NK + k, rzr = 4 * NK + jp * NK + k;
-      const double z1 = r[rzr].x, z2 = r[rzr].y;
-      const double ox1 = (r[r1].x + dx) - PBx, oy1 = (r[r1].y + dy) - PBy;
-      const double ox2 = (r[r2].x + dx) - PBx, oy2 = (r[r2].y + dy) - PBy;
-      r[r1] = make_double2(rx(t, ox1, oy1, z1, cmx, cmy, cmz), ry(t, ox1, oy1, z1, cmx, cmy, cmz));
-      r[r2] = make_double2(rx(t, ox2, oy2, z2, cmx, cmy, cmz), ry(t, ox2, oy2, z2, cmx, cmy, cmz));
-      r[rzr] = make_double2(rz(t, ox1, oy1, z1, cmx, cmy, cmz), rz(t, ox2, oy2, z2, cmx, cmy, cmz));
+      double x1, y1, z1, x2, y2, z2;
+      cx_move_bead(M, r[r1].x, r[r1].y, r[rzr].x, x1, y1, z1);
+      cx_move_bead(M, r[r2].x, r[r2].y, r[rzr].y, x2, y2, z2);
+      r[r1] = make_double2(x1, y1);
+      r[r2] = make_double2(x2, y2);
+      r[rzr] = make_double2(z1, z2);
     }
 #pragma unroll
   for (int w = 0; w < ROWS; ++w) st_n(dst[bead_elem(i, w, n, ROWS)], r[w]);
@@ -2319,6 +2567,24 @@ __global__ void __launch_bounds__(256, HEAVY_WAVES) k_complex_heavy(KParams P, D
   }
   const uint32_t n = d.ctl->n_heavy;
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
+  if (P.step_chain && !P.dd) {
+    // k_cx_check's last duty (no k_cx_check on this path): the extent flags
+    // k_move_members raised are judged after it, in the same step — by the
+    // waves without a heavy complex (every wave when there are none), one
+    // descriptor per lane.  A flagged complex that is not on the heavy list
+    // broke the bound (the listed ones are realigned below, which checks its
+    // own result).
+    const uint32_t ncx = d.ctl->n_cx1, first = n < nw ? n : 0u;
+    if (w >= first)
+      for (uint32_t c = (w - first) * 64 + lane; c < ncx; c += (nw - first) * 64) {
+        const int4 desc = d.cx_list[c];
+        // (the descriptors k_move_members saw: what the overflow BFS of this launch appends lies behind them)
+        if ((desc.z & 0xffff) > CXL || !cx_current(d, desc)) continue;
+        const uint32_t xb = d.cx_ext[desc.x];
+        if (xb) d.cx_ext[desc.x] = 0u;
+        if (xb == 1u) atomicOr(&d.ctl->err, ERR_GEOMETRY);  // a member's proposal broke the extent bound
+      }
+  }
   for (uint32_t c = w; c < n; c += nw) {
 #ifdef KMC_STAMPS  // diagnostic build: per-phase cycles of the staged path (lane 0 of each wave)
     uint64_t t0_ = Stamper::now(), t_ = t0_;
@@ -2413,6 +2679,7 @@ __device__ __forceinline__ void propose_one(const KParams& P, const Dev& d, int 
 __global__ void __launch_bounds__(256, MEMBER_WAVES) k_move_members(KParams P, Dev d) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x, NA = P.NA;
   if (p >= P.N) return;
+  if (p == 0 && P.step_chain) d.ctl->n_cx1 = min(d.ctl->n_cx, d.mcap / 2);  // fixed before k_complex_heavy's launch
   const int r = d.croot[p];
   if (r < 0 || (r & CROOT_BIG)) return;  // (the flag: no cx_size load on the member's chain)
   const double* cp = d.cxp + (size_t)(r - NA) * CXP;
@@ -2424,15 +2691,44 @@ __global__ void __launch_bounds__(256, MEMBER_WAVES) k_move_members(KParams P, D
 // The complexes' rigid-move parameters (cx_params) run in the first gC
 // workgroups, ahead of the free units: their short dependent chains of loads
 // overlap the free units' HBM stream instead of taking a launch of their own.
-#ifndef FREE_WAVES  // minimum waves per SIMD of k_propose_free
+// With gB > 0 (KParams::step_chain) the BFS of the candidates runs in the gB
+// workgroups ahead of those: the free units need nothing from it (they act on
+// U_FREE_A, U_DIMER and U_FREE_B slots, the BFS writes ukind / owner / croot
+// of bonded proteins only), and a thread that registers a complex goes on
+// with that complex's parameters and checks itself (the parameters'
+// workgroups walk only the descriptors the step began with).
+// Two instances, so that the paths without the BFS role (KMC_STEP_CHAIN=0,
+// the side-stream modes, a decomposed window) run the kernel they always
+// ran: CHAIN 0 has no LDS queue and the allocator's own register count;
+// CHAIN 1 (launched with gB > 0) is held at 3 waves per SIMD, what the dimer
+// path's registers allowed before the BFS role: with the parameters' thread's
+// checks the allocator would take 176 VGPRs (2 waves); held at 168 it spills
+// one 8-byte value, in the prologue of the parameters' loop, not on the free
+// units' paths.
+#ifndef FREE_WAVES  // minimum waves per SIMD of k_propose_free without the BFS role
 #define FREE_WAVES 1
 #endif
-__global__ void __launch_bounds__(256, FREE_WAVES) k_propose_free(KParams P, Dev d, int gC) {
-  if ((int)blockIdx.x < gC) {
-    cx_params(P, d, blockIdx.x * blockDim.x + threadIdx.x, (uint32_t)gC * blockDim.x);
+template <int CHAIN>
+__global__ void __launch_bounds__(256, CHAIN ? 3 : FREE_WAVES) k_propose_free(KParams P, Dev d, int gC, int gB) {
+  if constexpr (CHAIN != 0) {
+    // the BFS role's queue (32 KB: no workgroup fewer per CU at this kernel's 3 waves per SIMD; the
+    // compiler's resource usage)
+    __shared__ int qs[BFS_QCAP * 256];
+    if ((int)blockIdx.x < gB) {
+      int4 desc;
+      if (bfs_one(P, d, blockIdx.x * blockDim.x + threadIdx.x, qs, desc)) {
+        if (P.dbg_counts) atomicAdd(&d.ctl->n_bfs_reg, 1u);
+        cx_params_one<true>(P, d, desc, d.ctl->step);
+      }
+      return;
+    }
+  }
+  const int bid = (int)blockIdx.x - (CHAIN ? gB : 0);
+  if (bid < gC) {
+    cx_params<CHAIN != 0>(P, d, bid * blockDim.x + threadIdx.x, (uint32_t)gC * blockDim.x);
     return;
   }
-  propose_one(P, d, (int)((blockIdx.x - gC) * blockDim.x + threadIdx.x));
+  propose_one(P, d, (int)((bid - gC) * blockDim.x + threadIdx.x));
 }
 
 // ================================================================ 4. resolve
@@ -4519,7 +4815,9 @@ __global__ void __launch_bounds__(256) k_diss_observe(KParams P, Dev d) {
 __global__ void __launch_bounds__(1024) k_finalize(KParams P, Dev d, double time_step, int nblk) {
   __shared__ int red[16][6];
   __shared__ uint32_t tot[5];
+  __shared__ uint32_t nlog, nrec;  // incremental classification: ulog entries, reclassified proteins
   if (threadIdx.x < 5) tot[threadIdx.x] = 0;
+  if (threadIdx.x == 5) nlog = nrec = 0;
   int v[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll 4
   for (int b = threadIdx.x; b < nblk; b += blockDim.x) {
@@ -4548,15 +4846,31 @@ __global__ void __launch_bounds__(1024) k_finalize(KParams P, Dev d, double time
   // dirty list overflowed (read by every thread before thread 0 writes them)
   const uint32_t fstep = d.ctl->step;
   const uint32_t ff = (d.ctl->cx_cursor > P.cx_limit || d.ctl->n_dirty[fstep & 1] > (uint32_t)P.N) ? 1u : 0u;
+  const bool chain = P.step_chain && !P.dd && P.NB > 0;
   if (P.NB > 0) {
     if (ff) {
       cx_reset_all(P, d, threadIdx.x, blockDim.x);
     } else {
-      cx_dissolve_dirty(P, d, fstep);
+      if (chain) cx_dissolve_reclass(P, d, fstep, &nlog, &nrec);
+      else cx_dissolve_dirty(P, d, fstep);
       if (threadIdx.x == 0) d.ctl->full_now = 0;
     }
   }
   __syncthreads();
+  if (chain && ff) {
+    // a forced rebuild: no complex is kept, and the host launches no
+    // k_classify for it (it does not see the decision) — the rule for every
+    // slot here, by this workgroup (rare: members[] half full, or a dirty
+    // list that overflowed)
+    for (int p = threadIdx.x; p < P.N; p += blockDim.x) {
+      uint8_t kind;
+      int ownkey;
+      reclass_one(P, d, p, kind, ownkey);
+      reclass_store(d, p, kind, ownkey, &nlog);
+    }
+    if (threadIdx.x == 0) nrec = (uint32_t)P.N;
+    __syncthreads();
+  }
   if (threadIdx.x != 0) return;
   for (int w = 1; w < (int)(blockDim.x >> 6); ++w)
     for (int f = 0; f < 6; ++f) red[0][f] = f == 5 ? max(red[0][f], red[w][f]) : red[0][f] + red[w][f];
@@ -4583,6 +4897,9 @@ __global__ void __launch_bounds__(1024) k_finalize(KParams P, Dev d, double time
     c->err_first = c->err;
   }
   c->n_forced += ff;  // (diagnostics: full rebuilds latched here)
+  c->n_ulog = nlog;
+  c->n_reclass += nrec;
+  c->n_cx0 = min(c->n_cx, d.mcap / 2);  // the next step's parameters' workgroups walk these; its BFS appends behind them
   c->maxc = maxc;
   c->obs_idx = obs_idx + 1;
   c->step = step + 1;

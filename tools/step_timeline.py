@@ -2,8 +2,10 @@
 
     python tools/step_timeline.py <kernel_trace.csv> [step_index_from_end]
 
-Times are relative to the step's first kernel (k_classify), in µs, so the
-critical path and the launch gaps between dependent kernels are visible.
+A step is what follows a k_finalize up to and including the next one (a plain
+step launches no k_classify since KMC_STEP_CHAIN).  Times are
+relative to the step's first kernel, in µs, so the critical path and the
+launch gaps between dependent kernels are visible.
 """
 import csv
 import sys
@@ -11,8 +13,8 @@ import sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 3
-idx = [i for i, r in enumerate(rows) if "k_classify" in r["Kernel_Name"].split("(")[0]]
-i0, i1 = idx[-k], idx[-k + 1]
+idx = [i for i, r in enumerate(rows) if "k_finalize" in r["Kernel_Name"].split("(")[0]]
+i0, i1 = idx[-k - 1] + 1, idx[-k]
 t0 = int(rows[i0]["Start_Timestamp"])
 prev_end = t0
 busy = 0.0
