@@ -224,7 +224,8 @@ int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int6
 int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t max_r, int32_t max_l,
                     int64_t* hist, kmc_census* out);
 /* Device milliseconds of the last kmc_components / kmc_oligomer_census /
- * kmc_pair_counts / kmc_track_* / kmc_unwrap / kmc_cluster_* / kmc_structure_factor call: HIP events on the handle's stream around
+ * kmc_pair_counts / kmc_track_* / kmc_unwrap / kmc_cluster_* / kmc_structure_factor /
+ * kmc_bond_order / kmc_bond_order_corr call: HIP events on the handle's stream around
  * its kernels and clears (the result copies to the host excluded); 0 before
  * the first. */
 double kmc_analysis_ms(const kmc_sim* s);
@@ -462,6 +463,108 @@ int kmc_structure_factor(kmc_sim* s, int32_t hmax, int32_t kmax, int32_t select,
                          int64_t* sums /* [4][nq]: C_A, S_A, C_B, S_B */, int64_t n_sel[2]);
 int kmc_host_structure_factor(const kmc_params* p, const kmc_state_view* v, int32_t hmax, int32_t kmax,
                               int32_t select, int64_t* sums, int64_t n_sel[2]);
+
+/* Bond-orientational order: the local n-fold order
+ * psi_n(i) = (1/N_i) sum_j exp(i n theta_ij) of every selected protein of one
+ * species, its histogram by neighbour count and |psi|, its global sums, and
+ * the spatial correlation G_n(r) = <psi_n(i) psi_n*(j)>, as exact integers.
+ * Like the other analyses the calls read the CURRENT state on the device
+ * (valid straight after kmc_set_state / kmc_load_*), launch nothing inside
+ * kmc_step, leave the state, the step counter, the tracker, kmc_get_clusters'
+ * validity and the other analyses' scratch untouched and are timed by
+ * kmc_analysis_ms; their scratch is their own (allocated by the first call,
+ * freed by kmc_destroy).
+ *
+ * Definitions — the device, kmc_host_bond_order* and the tests share them bit
+ * for bit (doubles, no fused multiply-add; round = half away from zero, atan2,
+ * sin and cos the library's own, kmc_math.h):
+ *   position        (x, y) of bead [1][1], as in kmc_pair_counts.
+ *   integer coords  X = (int64) round(x * 1024.0), BX = (int64) round(box_x *
+ *                   1024.0); the same in y (§12's 2^-10 A).  KMC_ERR_ARG
+ *                   unless 1 <= BX, BY < 2^31.
+ *   set             which = KMC_BO_A (receptors) or KMC_BO_B (ligands); select
+ *                   = KMC_BO_ALL, or KMC_BO_BOUND: KMC_SK_BOUND's rule (a
+ *                   receptor with nei2 != 0 or nei3 != 0, a ligand with any
+ *                   of nei2..4 != 0).  Centres and neighbours both come from
+ *                   this set.
+ *   displacement    i -> j: DX = (X_j - X_i) mod BX in [0, BX) (the floor
+ *                   modulus); if (2 DX >= BX) DX -= BX; the same in y;
+ *                   D2 = DX*DX + DY*DY in int64.
+ *   neighbours      KMC_BO_WITHIN: every j != i of the set with 0 < D2 <= RC^2,
+ *                   RC = (int64) round(r_cut * 1024.0) — an integer test,
+ *                   inclusive and symmetric; coincident points (D2 = 0) are
+ *                   not neighbours.  Needs r_cut > 0 and floor(BX / RC) >= 3,
+ *                   floor(BY / RC) >= 3 (integer division), else KMC_ERR_ARG.
+ *                   KMC_BO_LINKED (ligands only; which = KMC_BO_A is
+ *                   KMC_ERR_ARG; r_cut is ignored): for each link r != 0 of
+ *                   ligand b's nei2..4: r' = receptor r's nei3 (its cis
+ *                   partner; skipped when 0), b' = receptor r''s nei2
+ *                   (skipped when 0, when b' = b, or when b' is not in the
+ *                   set); b' is a neighbour.  At most three; a ligand reached
+ *                   by two paths counts twice; a neighbour with D2 = 0 is
+ *                   skipped.  The network's own neighbour relation.
+ *   term            theta = atan2((double) DY, (double) DX); a = (double) n *
+ *                   theta, 1 <= n = fold <= KMC_BO_MAX_FOLD;
+ *                   tc = (int64) round(cos(a) * 1073741824.0), ts = (int64)
+ *                   round(sin(a) * 1073741824.0) (2^30).  Every ordered pair
+ *                   is evaluated from its centre's side: the term of j -> i
+ *                   is not derived from that of i -> j.
+ *   per protein     C_i = sum tc, S_i = sum ts, N_i = the number of neighbours
+ *                   — int64, exact, the same bits in any order of summation.
+ *                   N_i > 65535 anywhere: KMC_ERR_CAPACITY.  For N_i > 0
+ *                   pc_i = (int64) round((double) C_i / ((double) N_i *
+ *                   32768.0)), ps_i likewise from S_i (psi_i ~ (pc_i + i ps_i)
+ *                   / 2^15; the operands are exact doubles); for N_i = 0
+ *                   pc_i = ps_i = 0.  m_i = pc_i^2 + ps_i^2.
+ *   histogram       hist[KMC_BO_NN_ROWS][nbins], 1 <= nbins <= 1024: every
+ *                   selected protein in row min(N_i, 15), bin b = #{k in
+ *                   1..nbins-1 : k^2 2^30 <= nbins^2 m_i} — a bin in |psi|
+ *                   decided by integer comparison; the bins sum to n_sel.
+ *   summary         kmc_bond_order_out: n_sel, n_with (N_i > 0), sum_nn = sum
+ *                   N_i, sum_pc, sum_ps, sum_m over the selected proteins.
+ *   per protein out C[n], S[n] (int64), nn[n] (int32) by the species' reference
+ *                   index (n = n_a or n_b), zero for unselected proteins; a
+ *                   NULL pointer skips that copy.  hist may be NULL too.
+ *   correlation     corr[2][nbins], 1 <= nbins <= 4096, over the unordered
+ *                   pairs i < j of the set with N_i > 0 and N_j > 0: dr =
+ *                   r_max / nbins, E_m = (int64) round(((double) m * dr) *
+ *                   1024.0), bin k = #{m in 1..nbins : E_m^2 <= D2}; counted
+ *                   when k < nbins: corr[0][k] += pc_i pc_j + ps_i ps_j,
+ *                   corr[1][k] += 1.  Needs r_max > 0, floor(box / r_max) >= 3
+ *                   and floor(BX / E_nbins) >= 3 on both axes, else
+ *                   KMC_ERR_ARG.  G_n(r_k) = corr[0][k] / corr[1][k] / 2^30;
+ *                   only the real part: the imaginary part changes sign with
+ *                   the order of the pair.
+ * kmc_bond_order_corr is self-contained: it runs the local pass itself.
+ * kmc_host_bond_order / kmc_host_bond_order_corr: the same from a host state
+ * view, sequentially on a cell grid of their own, no device.
+ * KMC_ERR_ARG for a null / out-of-range argument, a handle without state and a
+ * decomposed window; KMC_ERR_STATE (KMC_BO_LINKED) when a ligand's link is not
+ * a receptor in [0, n_a], a receptor's nei3 not a receptor or its nei2 not 0
+ * or a ligand in (n_a, n_a + n_b]; every device loop is bounded, so a bad link
+ * ends the call and cannot hang. */
+#define KMC_BO_A 0
+#define KMC_BO_B 1
+#define KMC_BO_WITHIN 0
+#define KMC_BO_LINKED 1
+#define KMC_BO_ALL 0
+#define KMC_BO_BOUND 1
+#define KMC_BO_MAX_FOLD 12
+#define KMC_BO_NN_ROWS 16
+typedef struct kmc_bond_order_out {
+  int64_t n_sel, n_with, sum_nn, sum_pc, sum_ps, sum_m;
+} kmc_bond_order_out;
+int kmc_bond_order(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select,
+                   int32_t nbins, int64_t* hist /* [KMC_BO_NN_ROWS][nbins] */, kmc_bond_order_out* out,
+                   int64_t* C, int64_t* S, int32_t* nn);
+int kmc_bond_order_corr(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select,
+                        double r_max, int32_t nbins, int64_t* corr /* [2][nbins] */);
+int kmc_host_bond_order(const kmc_params* p, const kmc_state_view* v, int32_t which, int32_t mode, int32_t fold,
+                        double r_cut, int32_t select, int32_t nbins, int64_t* hist, kmc_bond_order_out* out,
+                        int64_t* C, int64_t* S, int32_t* nn);
+int kmc_host_bond_order_corr(const kmc_params* p, const kmc_state_view* v, int32_t which, int32_t mode,
+                             int32_t fold, double r_cut, int32_t select, double r_max, int32_t nbins,
+                             int64_t* corr);
 
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */

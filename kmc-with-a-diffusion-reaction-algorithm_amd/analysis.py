@@ -4,12 +4,13 @@ pair counts, per-class mean-squared displacements and the diffusion fit, the
 radius of gyration by cluster size, the fractal fit and the cluster shapes from
 the cluster geometry (cluster_geometry / cluster_list), the partial static
 structure factors S(q) and their radial average from the integer sums of
-structure_factor, and the replica sums of integer histograms, float64 sums and
-geometry tables.
+structure_factor, the global bond-orientational order and its correlation
+G_n(r) from the integers of bond_order / bond_order_corr, and the replica sums
+of integer histograms, float64 sums and geometry tables.
 
 The counts and sums themselves come from libkmc (kmc_analysis.hip,
-kmc_dynamics.hip, kmc_geometry.hip, kmc_structure.hip); nothing here touches a
-trajectory.
+kmc_dynamics.hip, kmc_geometry.hip, kmc_structure.hip, kmc_bondorder.hip);
+nothing here touches a trajectory.
 """
 from __future__ import annotations
 
@@ -257,3 +258,41 @@ def sq_radial(S, box_x: float, box_y: float, nbins: int, q_max: float):
     total = np.bincount(b[use], weights=S[use], minlength=nbins)
     mean = np.divide(total, count, out=np.full(nbins, np.nan), where=count > 0)
     return (np.arange(nbins, dtype=np.float64) + 0.5) * dq, mean, count
+
+
+# ---------------------------------------------------------------- bond-orientational order
+def bond_order(summary) -> dict:
+    """The global numbers from kmc_bond_order's summary (a capi.BondOrderOut or
+    its as_dict()), float64:
+      psi_abs  = |sum_i psi_i| / n_with — the global |Psi_n|: the modulus of the
+                 mean local order over the proteins that have a neighbour,
+      psi2     = sum_i |psi_i|^2 / n_with — the mean local |psi|^2,
+      mean_nn  = sum_nn / n_sel — the mean neighbour count of the selected set,
+    with psi_i = (pc_i + i ps_i) / 2^15 (zeros when the denominators are zero).
+
+    Replicas: the summary's fields, the histogram hist[16, nbins] and corr are
+    plain integer sums over proteins or pairs, so those of several replicas are
+    additive — sum them with reduce_counts and post-process the totals."""
+    d = summary.as_dict() if hasattr(summary, "as_dict") else dict(summary)
+    n_with, n_sel = float(d["n_with"]), float(d["n_sel"])
+    u = 32768.0
+    re, im = float(d["sum_pc"]) / u, float(d["sum_ps"]) / u
+    return {
+        "psi_abs": float(np.hypot(re, im) / n_with) if n_with > 0 else 0.0,
+        "psi2": float(d["sum_m"]) / (u * u) / n_with if n_with > 0 else 0.0,
+        "mean_nn": float(d["sum_nn"]) / n_sel if n_sel > 0 else 0.0,
+    }
+
+
+def bond_order_corr(corr, r_max: float):
+    """(r, G_n) from kmc_bond_order_corr's corr[2, nbins]: r the bin centres
+    (k + 1/2) r_max / nbins, G_n(r_k) = corr[0, k] / corr[1, k] / 2^30 — the
+    real part of <psi_n(i) psi_n*(j)> at separation r —, NaN where a bin holds
+    no pair.  corr is additive over replicas (reduce_counts) before this call."""
+    corr = np.asarray(corr)
+    if corr.ndim != 2 or corr.shape[0] != 2 or not r_max > 0:
+        raise ValueError("bond_order_corr: corr is [2, nbins], r_max > 0")
+    nbins = corr.shape[1]
+    num, cnt = corr[0].astype(np.float64), corr[1].astype(np.float64)
+    g = np.divide(num, cnt, out=np.full(nbins, np.nan), where=cnt > 0) / float(1 << 30)
+    return (np.arange(nbins, dtype=np.float64) + 0.5) * (r_max / nbins), g

@@ -283,6 +283,35 @@ def sk_select(select) -> int:
     return SK_SELECT[select] if isinstance(select, str) else int(select)
 
 
+BO_A, BO_B = 0, 1                     # KMC_BO_A / KMC_BO_B (the species whose order is measured)
+BO_WITHIN, BO_LINKED = 0, 1           # KMC_BO_WITHIN / KMC_BO_LINKED (the neighbour relation)
+BO_ALL, BO_BOUND = 0, 1               # KMC_BO_ALL / KMC_BO_BOUND (KMC_SK_BOUND's rule)
+BO_MAX_FOLD = 12                      # KMC_BO_MAX_FOLD
+BO_NN_ROWS = 16                       # KMC_BO_NN_ROWS: histogram rows, neighbour counts clamp into the last
+BO_HIST_BINS, BO_CORR_BINS = 1024, 4096  # most bins of kmc_bond_order / kmc_bond_order_corr
+BO_WHICH = {"A": BO_A, "B": BO_B}
+BO_MODE = {"within": BO_WITHIN, "linked": BO_LINKED}
+
+
+def bo_which(which) -> int:
+    """'A' / 'B' or the KMC_BO_* number itself."""
+    return BO_WHICH[which] if isinstance(which, str) else int(which)
+
+
+def bo_mode(mode) -> int:
+    """'within' / 'linked' or the KMC_BO_* number itself."""
+    return BO_MODE[mode] if isinstance(mode, str) else int(mode)
+
+
+class BondOrderOut(C.Structure):
+    """kmc_bond_order_out — the global sums of kmc_bond_order."""
+
+    _fields_ = [(name, C.c_int64) for name in ("n_sel", "n_with", "sum_nn", "sum_pc", "sum_ps", "sum_m")]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 DD_ROW = 416     # KMC_DD_ROW: one exchanged protein (48 doubles + 8 int32)
 DD_JCAP = 256    # KMC_DD_JCAP
 DD_XCAP = 64     # KMC_DD_XCAP

@@ -16,6 +16,7 @@
 #include "kmc_analysis.hip"
 #include "kmc_geometry.hip"
 #include "kmc_structure.hip"
+#include "kmc_bondorder.hip"
 #include "kmc_dynamics.hip"
 
 using namespace kmcd;
@@ -164,6 +165,18 @@ struct kmc_sim {
   size_t geo_rows_cap = 0;
   // structure factor (kmc_structure.hip): [4][SK_NQ_MAX] sums, then the two selection counts; its own, whatever N
   unsigned long long* sk_sums = nullptr;
+  // bond-orientational order (kmc_bondorder.hip): scratch of the first bond order call, its own
+  int32_t *bo_cell = nullptr, *bo_rank = nullptr, *bo_ref = nullptr, *bo_nn = nullptr;  // [max(NA, NB)]
+  int32_t *bo_ccnt = nullptr, *bo_cstart = nullptr, *bo_part = nullptr;  // [bo_ccap] cell counts, their scan, tile sums
+  size_t bo_ccap = 0;
+  longlong2* bo_pts = nullptr;                                 // [max(NA, NB)] integer coordinates sorted by cell
+  int2 *bo_pcs = nullptr, *bo_pcs_sorted = nullptr;            // (pc, ps) by reference index / sorted by cell
+  unsigned long long *bo_C = nullptr, *bo_S = nullptr;         // [max(NA, NB)] sums by reference index
+  unsigned long long *bo_hist = nullptr, *bo_corr = nullptr;   // [BO_NN_ROWS][BO_HIST_BINS]; [2][BO_CORR_BINS]
+  int64_t* bo_E2 = nullptr;                                    // [BO_CORR_BINS + 1] squared integer bin edges
+  BoOut* bo_out = nullptr;
+  int bo_chunk = BO_CHUNK;  // KMC_DEBUG_BO_CHUNK: smaller staged chunks of the correlation (the chunked path at test size)
+  int bo_variant = 1;       // KMC_BO_VARIANT: 0 one lane per centre, 1 the wave's hit queue
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   double an_ms = 0.0;
   // displacement tracking (kmc_dynamics.hip): scratch of the first
@@ -487,6 +500,10 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
   s->debug_sync = dsy && *dsy == '1';
   const char* pc = getenv("KMC_DEBUG_PAIR_CHUNK");  // debug: kmc_pair_counts stages fewer points at a time
   if (pc && *pc) s->an_chunk = std::max(1, std::min(AN_CHUNK, atoi(pc)));
+  const char* bc = getenv("KMC_DEBUG_BO_CHUNK");  // debug: kmc_bond_order_corr stages fewer points at a time
+  if (bc && *bc) s->bo_chunk = std::max(1, std::min(BO_CHUNK, atoi(bc)));
+  const char* bv = getenv("KMC_BO_VARIANT");  // the cutoff pass of kmc_bond_order: 0 lane per centre, 1 hit queue
+  if (bv && *bv) s->bo_variant = *bv == '0' ? 0 : 1;
   // debug: lower the LDS tile capacity so that tiles take the global path
   const char* tc = getenv("KMC_DEBUG_TCAP");
   K.tcap = TCAP;
@@ -2549,6 +2566,221 @@ int kmc_structure_factor(kmc_sim* s, int32_t hmax, int32_t kmax, int32_t select,
   if (rc != KMC_OK) return rc;
   HIPCHK(s, hipMemcpy(sums, s->sk_sums, sizeof(int64_t) * nw, hipMemcpyDeviceToHost));
   HIPCHK(s, hipMemcpy(n_sel, d_nsel, sizeof(int64_t) * 2, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+// ---------------------------------------------------------------- bond-orientational order
+// kmc_bondorder.hip: read-only like the analysis above, on scratch of its own.
+
+static_assert(KMC_BO_MAX_FOLD == BO_MAX_FOLD && KMC_BO_NN_ROWS == BO_NN_ROWS, "kmc.h and kmc_bondorder.h agree");
+static_assert(sizeof(kmc_bond_order_out) == 6 * sizeof(unsigned long long), "kmc_bond_order_out is BoOut's six sums");
+
+// a workgroup's dynamic LDS beyond the 64 KiB every launch may ask for (the CU has 160 KiB)
+static void bo_lds_limit(const void* kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    (void)hipGetLastError();  // the launch itself reports what it cannot have
+}
+
+// the arguments both calls share, checked and turned into the kernels'; the scratch of the first call
+static int bo_setup(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select, BoArgs* a) {
+  if ((which != KMC_BO_A && which != KMC_BO_B) || (mode != KMC_BO_WITHIN && mode != KMC_BO_LINKED) || fold < 1 ||
+      fold > BO_MAX_FOLD || (select != KMC_BO_ALL && select != KMC_BO_BOUND) ||
+      (mode == KMC_BO_LINKED && which != KMC_BO_B))
+    return fail(s, KMC_ERR_ARG, "bond order: which 0 or 1, mode 0 or 1 (linked: ligands only), 1 <= fold <= " +
+                                    std::to_string(BO_MAX_FOLD) + ", select 0 or 1");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const KParams& K = s->K;
+  const double bx = kmcm::round_(K.box_x * 1024.0), by = kmcm::round_(K.box_y * 1024.0);
+  if (!(bx >= 1.0) || !(by >= 1.0) || !(bx < (double)BO_BOX_MAX) || !(by < (double)BO_BOX_MAX))
+    return fail(s, KMC_ERR_ARG, "bond order: the box is below 2^-10 A or not below 2^21 A");
+  a->which = which;
+  a->mode = mode;
+  a->fold = fold;
+  a->select = select;
+  a->base = which == KMC_BO_A ? 0 : K.NA;
+  a->n = which == KMC_BO_A ? K.NA : K.NB;
+  a->BX = (long long)bx;
+  a->BY = (long long)by;
+  a->RC2 = 0;
+  a->ncx = a->ncy = 0;
+  if (mode == KMC_BO_WITHIN) {
+    const long long RC =
+        r_cut > 0.0 && r_cut * 1024.0 < (double)BO_BOX_MAX ? (long long)kmcm::round_(r_cut * 1024.0) : 0;
+    if (RC < 1 || a->BX / RC < 3 || a->BY / RC < 3)
+      return fail(s, KMC_ERR_ARG, "bond order: r_cut must be positive and at most a third of the box (3 cells along an axis)");
+    a->RC2 = RC * RC;
+    a->ncx = (int)std::min<long long>(a->BX / RC, BO_NC_MAX);
+    a->ncy = (int)std::min<long long>(a->BY / RC, BO_NC_MAX);
+  }
+  if (!s->bo_out) {
+    const size_t n = (size_t)std::max(K.NA, K.NB);
+    rc = KMC_OK;
+    rc |= dalloc(s, &s->bo_cell, n);
+    rc |= dalloc(s, &s->bo_rank, n);
+    rc |= dalloc(s, &s->bo_ref, n);
+    rc |= dalloc(s, &s->bo_nn, n);
+    rc |= dalloc(s, &s->bo_pts, n);
+    rc |= dalloc(s, &s->bo_pcs, n);
+    rc |= dalloc(s, &s->bo_pcs_sorted, n);
+    rc |= dalloc(s, &s->bo_C, n);
+    rc |= dalloc(s, &s->bo_S, n);
+    rc |= dalloc(s, &s->bo_hist, (size_t)BO_NN_ROWS * BO_HIST_BINS);
+    rc |= dalloc(s, &s->bo_corr, (size_t)2 * BO_CORR_BINS);
+    rc |= dalloc(s, &s->bo_E2, (size_t)BO_CORR_BINS + 1);
+    rc |= dalloc(s, &s->bo_out, 1);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "bond order: scratch allocation failed");
+  }
+  return KMC_OK;
+}
+
+// the set binned on the grid a->ncx x a->ncy (nn_filter: only the proteins with neighbours, with their (pc, ps))
+static int bo_grid(kmc_sim* s, const BoArgs& a, bool corr_grid) {
+  const size_t ncnt = (size_t)a.ncx * a.ncy + 1;  // the scan's last entry is the number of binned points
+  if (ncnt > s->bo_ccap) {
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    dfree(s, s->bo_ccnt);
+    dfree(s, s->bo_cstart);
+    dfree(s, s->bo_part);
+    s->bo_ccap = 0;
+    int rc = KMC_OK;
+    rc |= dalloc(s, &s->bo_ccnt, ncnt);
+    rc |= dalloc(s, &s->bo_cstart, ncnt);
+    rc |= dalloc(s, &s->bo_part, (ncnt + SCAN_TILE - 1) / SCAN_TILE);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "bond order: scratch allocation failed");
+    s->bo_ccap = ncnt;
+  }
+  hipStream_t st = s->stream;
+  HIPCHK(s, hipMemsetAsync(s->bo_ccnt, 0, sizeof(int32_t) * ncnt, st));
+  const unsigned g = (unsigned)((a.n + BO_T - 1) / BO_T);
+  const int nb = (int)((ncnt + SCAN_TILE - 1) / SCAN_TILE);
+  if (g)
+    k_bo_cell_count<<<g, BO_T, 0, st>>>(s->K, s->d, a, corr_grid ? s->bo_nn : nullptr, s->bo_ccnt, s->bo_cell,
+                                        s->bo_rank, s->bo_out);
+  k_scan_part<<<nb, 256, 0, st>>>(s->bo_ccnt, (int)ncnt, s->bo_part);
+  k_scan_top<<<1, 256, 0, st>>>(s->bo_part, nb);
+  k_scan_down<<<nb, 256, 0, st>>>(s->bo_ccnt, s->bo_cstart, (int)ncnt, s->bo_part);
+  if (g)
+    k_bo_cell_scatter<<<g, BO_T, 0, st>>>(s->K, s->d, a, s->bo_cstart, s->bo_cell, s->bo_rank, s->bo_pts, s->bo_ref,
+                                          corr_grid ? s->bo_pcs : nullptr, s->bo_pcs_sorted);
+  HIPCHK(s, hipGetLastError());
+  return KMC_OK;
+}
+
+// the local pass and the reduce, left on the device: (C, S, N) and (pc, ps) by reference index, the six sums and,
+// for nbins > 0, the histogram.  The stream is not waited for.
+static int bo_local(kmc_sim* s, const BoArgs& a, int nbins) {
+  hipStream_t st = s->stream;
+  const size_t n = (size_t)a.n;
+  HIPCHK(s, hipMemsetAsync(s->bo_out, 0, sizeof(BoOut), st));
+  HIPCHK(s, hipMemsetAsync(s->bo_C, 0, sizeof(unsigned long long) * n, st));
+  HIPCHK(s, hipMemsetAsync(s->bo_S, 0, sizeof(unsigned long long) * n, st));
+  HIPCHK(s, hipMemsetAsync(s->bo_nn, 0xff, sizeof(int32_t) * n, st));  // -1: outside the set until a centre writes its count
+  if (nbins) HIPCHK(s, hipMemsetAsync(s->bo_hist, 0, sizeof(unsigned long long) * (size_t)BO_NN_ROWS * nbins, st));
+  if (a.n == 0) return KMC_OK;
+  if (a.mode == KMC_BO_WITHIN) {
+    const int rc = bo_grid(s, a, false);
+    if (rc != KMC_OK) return rc;
+    if (s->bo_variant == 0) {
+      const unsigned g = (unsigned)std::min<int64_t>(BO_WG_MAX, ((int64_t)a.n + BO_T - 1) / BO_T);
+      k_bo_local_lane<<<g, BO_T, 0, st>>>(a, s->bo_cstart, s->bo_pts, s->bo_ref, s->bo_C, s->bo_S, s->bo_nn);
+    } else {
+      const unsigned g = (unsigned)std::min<int64_t>(4 * BO_WG_MAX, ((int64_t)a.n + BO_T - 1) / BO_T);
+      k_bo_local_queue<<<g, BO_T, 0, st>>>(a, s->bo_cstart, s->bo_pts, s->bo_ref, s->bo_C, s->bo_S, s->bo_nn);
+    }
+  } else {
+    k_bo_local_linked<<<(unsigned)((a.n + BO_T - 1) / BO_T), BO_T, 0, st>>>(s->K, s->d, a, s->bo_C, s->bo_S, s->bo_nn,
+                                                                            s->bo_out);
+  }
+  const size_t lds = sizeof(unsigned long long) * (6 + (size_t)BO_NN_ROWS * nbins);
+  bo_lds_limit((const void*)k_bo_reduce, lds);
+  const unsigned g = (unsigned)std::min<int64_t>(nbins > 64 ? 256 : BO_WG_MAX, ((int64_t)a.n + BO_T - 1) / BO_T);
+  k_bo_reduce<<<g, BO_T, lds, st>>>(a.n, nbins, s->bo_C, s->bo_S, s->bo_nn, s->bo_pcs, nbins ? s->bo_hist : nullptr,
+                                    s->bo_out);
+  HIPCHK(s, hipGetLastError());
+  return KMC_OK;
+}
+
+static int bo_result(kmc_sim* s, BoOut* o) {
+  HIPCHK(s, hipMemcpy(o, s->bo_out, sizeof *o, hipMemcpyDeviceToHost));
+  if (o->err & 1u) return fail(s, KMC_ERR_STATE, "bond order: a bond link leaves the state");
+  if (o->err & 2u) return fail(s, KMC_ERR_CAPACITY, "bond order: a protein with more than 65535 neighbours");
+  return KMC_OK;
+}
+
+int kmc_bond_order(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select, int32_t nbins,
+                   int64_t* hist, kmc_bond_order_out* out, int64_t* C, int64_t* S, int32_t* nn) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out || nbins < 1 || nbins > BO_HIST_BINS)
+    return fail(s, KMC_ERR_ARG, "bond order: out is needed, 1 <= nbins <= " + std::to_string(BO_HIST_BINS));
+  BoArgs a;
+  int rc = bo_setup(s, which, mode, fold, r_cut, select, &a);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = bo_local(s, a, hist ? nbins : 0);
+  if (rc == KMC_OK) rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  BoOut o;
+  rc = bo_result(s, &o);
+  if (rc != KMC_OK) return rc;
+  std::memcpy(out, o.sum, sizeof *out);
+  const size_t n = (size_t)a.n;
+  if (hist) HIPCHK(s, hipMemcpy(hist, s->bo_hist, sizeof(int64_t) * (size_t)BO_NN_ROWS * nbins, hipMemcpyDeviceToHost));
+  if (C && n) HIPCHK(s, hipMemcpy(C, s->bo_C, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+  if (S && n) HIPCHK(s, hipMemcpy(S, s->bo_S, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+  if (nn && n) {
+    HIPCHK(s, hipMemcpy(nn, s->bo_nn, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i)
+      if (nn[i] < 0) nn[i] = 0;  // outside the set
+  }
+  return KMC_OK;
+}
+
+int kmc_bond_order_corr(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select,
+                        double r_max, int32_t nbins, int64_t* corr) {
+  if (!s) return KMC_ERR_ARG;
+  if (!corr || nbins < 1 || nbins > BO_CORR_BINS || !(r_max > 0.0) || !std::isfinite(r_max))
+    return fail(s, KMC_ERR_ARG, "bond order: corr is needed, r_max > 0, 1 <= nbins <= " + std::to_string(BO_CORR_BINS));
+  BoArgs a;
+  int rc = bo_setup(s, which, mode, fold, r_cut, select, &a);
+  if (rc != KMC_OK) return rc;
+  const double dr = r_max / nbins;
+  const int64_t EN = r_max * 1024.0 < (double)BO_BOX_MAX ? kmcb::corr_edge(nbins, dr) : 0;
+  if (EN < 1 || !(std::floor(s->K.box_x / r_max) >= 3.0) || !(std::floor(s->K.box_y / r_max) >= 3.0) ||
+      a.BX / EN < 3 || a.BY / EN < 3)
+    return fail(s, KMC_ERR_ARG, "bond order: r_max must be at least 2^-10 A and at most a third of the box (3 cells along an axis)");
+  std::vector<int64_t> E2((size_t)nbins + 1);
+  for (int m = 0; m <= nbins; ++m) {
+    const int64_t e = kmcb::corr_edge(m, dr);
+    E2[m] = e * e;
+  }
+  hipStream_t st = s->stream;
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = bo_local(s, a, 0);
+  if (rc != KMC_OK) return rc;
+  BoOut o;
+  HIPCHK(s, hipStreamSynchronize(st));
+  rc = bo_result(s, &o);  // a local pass that failed ends the call before the pair walk
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpyAsync(s->bo_E2, E2.data(), sizeof(int64_t) * E2.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemsetAsync(s->bo_corr, 0, sizeof(unsigned long long) * 2 * (size_t)nbins, st));
+  if (a.n > 0) {
+    BoArgs g = a;  // the second grid: cells no narrower than the last edge
+    g.ncx = (int)std::min<int64_t>(a.BX / EN, BO_NC_MAX);
+    g.ncy = (int)std::min<int64_t>(a.BY / EN, BO_NC_MAX);
+    rc = bo_grid(s, g, true);
+    if (rc != KMC_OK) return rc;
+    const size_t lds = 48 * (size_t)s->bo_chunk + sizeof(unsigned long long) * 2 * (size_t)nbins;
+    bo_lds_limit((const void*)k_bo_corr, lds);
+    k_bo_corr<<<(unsigned)std::min(g.ncx * g.ncy, BO_WG_MAX), BO_T, lds, st>>>(
+        g, s->bo_cstart, s->bo_pts, s->bo_pcs_sorted, s->bo_E2, nbins, (float)(1.0 / (dr * 1024.0)), s->bo_chunk,
+        s->bo_corr);
+    HIPCHK(s, hipGetLastError());
+  }
+  rc = an_end(s);  // (waits: E2 is read by the copy until here)
+  if (rc == KMC_OK) rc = bo_result(s, &o);  // the second grid's index check
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpy(corr, s->bo_corr, sizeof(int64_t) * 2 * (size_t)nbins, hipMemcpyDeviceToHost));
   return KMC_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/kmc.h"
+#include "kmc_bondorder.h"
 #include "kmc_host.h"
 #include "kmc_math.h"
 #include "kmc_philox.h"
@@ -895,6 +896,241 @@ int kmc_host_structure_factor(const kmc_params* p, const kmc_state_view* v, int3
         S[(size_t)h * W + (k + kmax)] += ts;
       }
   }
+  return KMC_OK;
+}
+
+// Bond-orientational order (include/kmc.h), sequential.  The local pass leaves
+// the set, its integer coordinates and every protein's (C, S, N) by the
+// species' reference index; neighbours within the cutoff come from a
+// counting-sorted periodic cell grid (the 3 x 3 cells around a centre), so the
+// cost is linear in the set whatever its size.
+extern "C++" {
+namespace {
+
+struct BoHost {
+  int n = 0;          // proteins of the species
+  int64_t B[2] = {0, 0};
+  std::vector<uint8_t> sel;
+  std::vector<int64_t> X, Y, C, S;
+  std::vector<int32_t> nn;
+};
+
+struct BoCells {
+  int ncx = 0, ncy = 0;
+  std::vector<int32_t> start, item;  // cell c holds item[start[c] .. start[c + 1])
+  void build(const BoHost& h, const std::vector<int32_t>& who, int ncx_, int ncy_) {
+    ncx = ncx_;
+    ncy = ncy_;
+    start.assign((size_t)ncx * ncy + 1, 0);
+    item.resize(who.size());
+    std::vector<int32_t> cell(who.size());
+    for (size_t t = 0; t < who.size(); ++t) {
+      const int i = who[t];
+      cell[t] = kmcb::cell_of(kmcb::wrap(h.Y[i], h.B[1]), ncy, h.B[1]) * ncx +
+                kmcb::cell_of(kmcb::wrap(h.X[i], h.B[0]), ncx, h.B[0]);
+      start[(size_t)cell[t] + 1] += 1;
+    }
+    for (size_t c = 0; c + 1 < start.size(); ++c) start[c + 1] += start[c];
+    std::vector<int32_t> fill(start.begin(), start.end() - 1);
+    for (size_t t = 0; t < who.size(); ++t) item[(size_t)fill[cell[t]]++] = who[t];
+  }
+  // f(j) for every item of the 3 x 3 cells around point i's cell (distinct cells: ncx, ncy >= 3)
+  template <typename F>
+  void around(const BoHost& h, int i, F f) const {
+    const int cx = kmcb::cell_of(kmcb::wrap(h.X[i], h.B[0]), ncx, h.B[0]);
+    const int cy = kmcb::cell_of(kmcb::wrap(h.Y[i], h.B[1]), ncy, h.B[1]);
+    for (int oy = -1; oy <= 1; ++oy)
+      for (int ox = -1; ox <= 1; ++ox) {
+        const size_t c = (size_t)((cy + oy + ncy) % ncy) * ncx + (cx + ox + ncx) % ncx;
+        for (int32_t t = start[c]; t < start[c + 1]; ++t) f(item[(size_t)t]);
+      }
+  }
+};
+
+int bo_host_local(const kmc_params* p, const kmc_state_view* v, int32_t which, int32_t mode, int32_t fold,
+                  double r_cut, int32_t select, BoHost* h, std::string* err) {
+  if (!p || !v || !v->a_int || !v->b_int || !v->ra || !v->rb || p->n_a < 0 || p->n_b < 0 ||
+      (which != KMC_BO_A && which != KMC_BO_B) || (mode != KMC_BO_WITHIN && mode != KMC_BO_LINKED) || fold < 1 ||
+      fold > KMC_BO_MAX_FOLD || (select != KMC_BO_ALL && select != KMC_BO_BOUND) ||
+      (mode == KMC_BO_LINKED && which != KMC_BO_B)) {
+    *err = "bond order: params and state are needed, which 0 or 1, mode 0 or 1 (linked: ligands only), 1 <= fold <= 12, select 0 or 1";
+    return KMC_ERR_ARG;
+  }
+  const int na = p->n_a, nb = p->n_b, n = which == KMC_BO_A ? na : nb;
+  const double bx = kmcm::round_(p->box_x * 1024.0), by = kmcm::round_(p->box_y * 1024.0);
+  if (!(bx >= 1.0) || !(by >= 1.0) || !(bx < (double)BO_BOX_MAX) || !(by < (double)BO_BOX_MAX)) {
+    *err = "bond order: the box is below 2^-10 A or not below 2^21 A";
+    return KMC_ERR_ARG;
+  }
+  h->n = n;
+  h->B[0] = (int64_t)bx;
+  h->B[1] = (int64_t)by;
+  int64_t RC = 0;
+  if (mode == KMC_BO_WITHIN) {
+    const double rc = r_cut > 0.0 && r_cut * 1024.0 < (double)BO_BOX_MAX ? kmcm::round_(r_cut * 1024.0) : 0.0;
+    RC = (int64_t)rc;
+    if (RC < 1 || h->B[0] / RC < 3 || h->B[1] / RC < 3) {
+      *err = "bond order: r_cut must be positive and at most a third of the box (3 cells along an axis)";
+      return KMC_ERR_ARG;
+    }
+  }
+  h->sel.assign((size_t)n, 1);
+  h->X.resize((size_t)n);
+  h->Y.resize((size_t)n);
+  h->C.assign((size_t)n, 0);
+  h->S.assign((size_t)n, 0);
+  h->nn.assign((size_t)n, 0);
+  std::vector<int32_t> who;
+  for (int i = 0; i < n; ++i) {
+    if (which == KMC_BO_A) {
+      h->X[i] = (int64_t)kmcm::round_(v->ra[RA(na, 1, 1, 0, i)] * 1024.0);
+      h->Y[i] = (int64_t)kmcm::round_(v->ra[RA(na, 1, 1, 1, i)] * 1024.0);
+      if (select == KMC_BO_BOUND) h->sel[i] = v->a_int[2 * (size_t)na + i] != 0 || v->a_int[4 * (size_t)na + i] != 0;
+    } else {
+      h->X[i] = (int64_t)kmcm::round_(v->rb[RB(nb, 1, 1, 0, i)] * 1024.0);
+      h->Y[i] = (int64_t)kmcm::round_(v->rb[RB(nb, 1, 1, 1, i)] * 1024.0);
+      if (select == KMC_BO_BOUND) {
+        bool bound = false;
+        for (int j = 2; j <= 4; ++j) bound = bound || v->b_int[(size_t)(4 + j - 1) * nb + i] != 0;
+        h->sel[i] = bound;
+      }
+    }
+    if (h->sel[i]) who.push_back(i);
+  }
+  auto add = [&](int i, int j) {
+    const int64_t DX = kmcb::fold(h->X[j] - h->X[i], h->B[0]), DY = kmcb::fold(h->Y[j] - h->Y[i], h->B[1]);
+    if (DX == 0 && DY == 0) return;
+    int64_t tc, ts;
+    kmcb::term(fold, DX, DY, &tc, &ts);
+    h->C[i] += tc;
+    h->S[i] += ts;
+    h->nn[i] += 1;
+  };
+  if (mode == KMC_BO_WITHIN) {
+    BoCells g;
+    g.build(*h, who, (int)std::min<int64_t>(h->B[0] / RC, BO_NC_MAX), (int)std::min<int64_t>(h->B[1] / RC, BO_NC_MAX));
+    const int64_t RC2 = RC * RC;
+    for (int i : who) {
+      int64_t cnt = 0;
+      g.around(*h, i, [&](int j) {
+        const int64_t DX = kmcb::fold(h->X[j] - h->X[i], h->B[0]), DY = kmcb::fold(h->Y[j] - h->Y[i], h->B[1]);
+        const int64_t D2 = DX * DX + DY * DY;
+        if (D2 <= 0 || D2 > RC2) return;
+        if (++cnt <= BO_NN_MAX) add(i, j);
+      });
+      if (cnt > BO_NN_MAX) {
+        *err = "bond order: a protein with more than 65535 neighbours";
+        return KMC_ERR_CAPACITY;
+      }
+    }
+  } else {
+    for (int b : who) {
+      for (int j = 2; j <= 4; ++j) {
+        const int r = v->b_int[(size_t)(4 + j - 1) * nb + b];
+        if (r == 0) continue;
+        int r2 = 0, l = 0;
+        bool ok = r >= 1 && r <= na;
+        if (ok) {
+          r2 = v->a_int[4 * (size_t)na + (r - 1)];
+          ok = r2 >= 0 && r2 <= na;
+        }
+        if (ok && r2 != 0) {
+          l = v->a_int[2 * (size_t)na + (r2 - 1)];
+          ok = l == 0 || (l > na && l <= na + nb);
+        }
+        if (!ok) {
+          *err = "bond order: a link followed from ligand " + std::to_string(b + 1) + " leaves the state";
+          return KMC_ERR_STATE;
+        }
+        if (r2 == 0 || l == 0) continue;
+        const int b2 = l - 1 - na;
+        if (b2 == b || !h->sel[b2]) continue;
+        add(b, b2);
+      }
+    }
+  }
+  return KMC_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int kmc_host_bond_order(const kmc_params* p, const kmc_state_view* v, int32_t which, int32_t mode, int32_t fold,
+                        double r_cut, int32_t select, int32_t nbins, int64_t* hist, kmc_bond_order_out* out,
+                        int64_t* C, int64_t* S, int32_t* nn) {
+  if (!out || nbins < 1 || nbins > BO_HIST_BINS) {
+    g_host_err = "bond order: out is needed, 1 <= nbins <= 1024";
+    return KMC_ERR_ARG;
+  }
+  BoHost h;
+  const int rc = bo_host_local(p, v, which, mode, fold, r_cut, select, &h, &g_host_err);
+  if (rc != KMC_OK) return rc;
+  std::memset(out, 0, sizeof *out);
+  if (hist) std::fill(hist, hist + (size_t)KMC_BO_NN_ROWS * nbins, (int64_t)0);
+  for (int i = 0; i < h.n; ++i) {
+    if (!h.sel[i]) continue;
+    const int64_t N = h.nn[i];
+    const int64_t pc = N ? kmcb::normalise(h.C[i], N) : 0, ps = N ? kmcb::normalise(h.S[i], N) : 0;
+    const int64_t m = pc * pc + ps * ps;
+    out->n_sel += 1;
+    out->n_with += N > 0;
+    out->sum_nn += N;
+    out->sum_pc += pc;
+    out->sum_ps += ps;
+    out->sum_m += m;
+    if (hist) hist[(size_t)std::min<int64_t>(N, KMC_BO_NN_ROWS - 1) * nbins + kmcb::mag_bin(m, nbins)] += 1;
+  }
+  if (C) std::copy(h.C.begin(), h.C.end(), C);
+  if (S) std::copy(h.S.begin(), h.S.end(), S);
+  if (nn) std::copy(h.nn.begin(), h.nn.end(), nn);
+  return KMC_OK;
+}
+
+int kmc_host_bond_order_corr(const kmc_params* p, const kmc_state_view* v, int32_t which, int32_t mode,
+                             int32_t fold, double r_cut, int32_t select, double r_max, int32_t nbins,
+                             int64_t* corr) {
+  if (!corr || nbins < 1 || nbins > BO_CORR_BINS || !(r_max > 0.0) || !std::isfinite(r_max)) {
+    g_host_err = "bond order: corr is needed, r_max > 0, 1 <= nbins <= 4096";
+    return KMC_ERR_ARG;
+  }
+  BoHost h;
+  const int rc = bo_host_local(p, v, which, mode, fold, r_cut, select, &h, &g_host_err);
+  if (rc != KMC_OK) return rc;
+  const double dr = r_max / nbins;
+  std::vector<int64_t> E2((size_t)nbins + 1);
+  const int64_t EN = r_max * 1024.0 < (double)BO_BOX_MAX ? kmcb::corr_edge(nbins, dr) : 0;
+  if (EN < 1 || !(std::floor(p->box_x / r_max) >= 3.0) || !(std::floor(p->box_y / r_max) >= 3.0) || h.B[0] / EN < 3 ||
+      h.B[1] / EN < 3) {
+    g_host_err = "bond order: r_max must be at least 2^-10 A and at most a third of the box (3 cells along an axis)";
+    return KMC_ERR_ARG;
+  }
+  for (int m = 0; m <= nbins; ++m) {
+    const int64_t e = kmcb::corr_edge(m, dr);
+    E2[m] = e * e;
+  }
+  std::vector<int32_t> who;
+  std::vector<int64_t> pc((size_t)h.n, 0), ps((size_t)h.n, 0);
+  for (int i = 0; i < h.n; ++i) {
+    if (!h.sel[i] || h.nn[i] == 0) continue;
+    pc[i] = kmcb::normalise(h.C[i], h.nn[i]);
+    ps[i] = kmcb::normalise(h.S[i], h.nn[i]);
+    who.push_back(i);
+  }
+  std::fill(corr, corr + 2 * (size_t)nbins, (int64_t)0);
+  BoCells g;
+  g.build(h, who, (int)std::min<int64_t>(h.B[0] / EN, BO_NC_MAX), (int)std::min<int64_t>(h.B[1] / EN, BO_NC_MAX));
+  const double inv = 1.0 / (dr * 1024.0);
+  for (int i : who)
+    g.around(h, i, [&](int j) {
+      if (j <= i) return;
+      const int64_t DX = kmcb::fold(h.X[j] - h.X[i], h.B[0]), DY = kmcb::fold(h.Y[j] - h.Y[i], h.B[1]);
+      const int64_t D2 = DX * DX + DY * DY;
+      if (D2 >= E2[nbins]) return;
+      const int k = kmcb::corr_bin(E2.data(), nbins, D2, (int)(std::sqrt((double)D2) * inv));
+      if (k >= nbins) return;
+      corr[k] += pc[i] * pc[j] + ps[i] * ps[j];
+      corr[(size_t)nbins + k] += 1;
+    });
   return KMC_OK;
 }
 

@@ -33,6 +33,13 @@
 //                            protein (kmc_structure_factor, KMC_SK_ALL; 0 <= HMAX, KMAX <= 64),
 //                            appended like the census: one line per wave vector
 //                              step h k C_A S_A C_B S_B      (exact integers, terms in units of 2^-30)
+//           [--psi WHICH FOLD RCUT NBINS FILE]  every out_interval, the bond-orientational order
+//                            of species WHICH (A or B) over the neighbours within RCUT
+//                            (kmc_bond_order, KMC_BO_WITHIN, KMC_BO_ALL; 1 <= FOLD <= 12,
+//                            1 <= NBINS <= 1024), appended like the census: per non-empty bin
+//                              step row bin count      (row = min(neighbours, 15), bin of |psi|)
+//                            and one line
+//                              step sum n_sel n_with sum_nn sum_pc sum_ps sum_m
 //           [--dyn EVERY RMAX NBINS FILE]  displacement tracking (kmc_track_*): the origin is
 //                            the state the process starts or resumes from (the tracker is
 //                            not checkpointed: a resume starts a new origin, every line
@@ -93,7 +100,9 @@ int main(int argc, char** argv) {
   kmc_params p;
   kmc_params_default(&p);
   int device = 0;
-  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path;
+  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path, psi_path;
+  int psi_which = -1, psi_fold = 0, psi_nbins = 0;
+  double psi_rcut = 0.0;
   int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0, geom_max = 0, sq_hmax = 0, sq_kmax = 0;
   double rdf_rmax = 0.0, dyn_rmax = 0.0;
   int64_t dyn_every = 0;
@@ -147,6 +156,19 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--psi") {
+      const std::string w = next();
+      psi_which = w == "A" ? KMC_BO_A : w == "B" ? KMC_BO_B : -1;
+      psi_fold = atoi(next().c_str());
+      psi_rcut = atof(next().c_str());
+      psi_nbins = atoi(next().c_str());
+      psi_path = next();
+      if (psi_which < 0 || psi_fold < 1 || psi_fold > KMC_BO_MAX_FOLD || !(psi_rcut > 0.0) || psi_nbins < 1 ||
+          psi_nbins > 1024) {
+        fprintf(stderr, "kmc_run: bad --psi %s %d %g %d\n", w.c_str(), psi_fold, psi_rcut, psi_nbins);
+        return 2;
+      }
+    }
     else if (a == "--dyn") {
       dyn_every = atoll(next().c_str());
       dyn_rmax = atof(next().c_str());
@@ -195,6 +217,7 @@ int main(int argc, char** argv) {
     if (!dyn_path.empty()) truncate(dyn_path.c_str());
     if (!geom_path.empty()) truncate(geom_path.c_str());
     if (!sq_path.empty()) truncate(sq_path.c_str());
+    if (!psi_path.empty()) truncate(psi_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
   }
@@ -211,6 +234,7 @@ int main(int argc, char** argv) {
   std::vector<kmc_geom_bin> geom((size_t)geom_max + 1);
   const size_t sq_nq = (size_t)(sq_hmax + 1) * (2 * sq_kmax + 1);
   std::vector<int64_t> sq(sq_path.empty() ? 0 : 4 * sq_nq);
+  std::vector<int64_t> psi((size_t)KMC_BO_NN_ROWS * psi_nbins + 1);
   std::vector<int64_t> vh((size_t)KMC_TRACK_CLASSES * dyn_nbins + 1);
   if (!dyn_path.empty()) {
     rc = kmc_track_begin(s, 0.0);
@@ -301,6 +325,22 @@ int main(int argc, char** argv) {
           fprintf(f, "%lld %d %d %lld %lld %lld %lld\n", (long long)step, (int)(q / (2 * sq_kmax + 1)),
                   (int)(q % (2 * sq_kmax + 1)) - sq_kmax, (long long)sq[q], (long long)sq[sq_nq + q],
                   (long long)sq[2 * sq_nq + q], (long long)sq[3 * sq_nq + q]);
+        fclose(f);
+      }
+      if (!psi_path.empty()) {
+        kmc_bond_order_out bo;
+        rc = kmc_bond_order(s, psi_which, KMC_BO_WITHIN, psi_fold, psi_rcut, KMC_BO_ALL, psi_nbins, psi.data(), &bo,
+                            nullptr, nullptr, nullptr);
+        if (rc) return die(s, rc, "bond order");
+        f = fopen(psi_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, psi_path.c_str());
+        for (int r = 0; r < KMC_BO_NN_ROWS; ++r)
+          for (int b = 0; b < psi_nbins; ++b)
+            if (psi[(size_t)r * psi_nbins + b])
+              fprintf(f, "%lld %d %d %lld\n", (long long)step, r, b, (long long)psi[(size_t)r * psi_nbins + b]);
+        fprintf(f, "%lld sum %lld %lld %lld %lld %lld %lld\n", (long long)step, (long long)bo.n_sel,
+                (long long)bo.n_with, (long long)bo.sum_nn, (long long)bo.sum_pc, (long long)bo.sum_ps,
+                (long long)bo.sum_m);
         fclose(f);
       }
       if (!dyn_path.empty()) {

@@ -112,6 +112,13 @@ def load_library(path: Optional[str] = None):
     L.kmc_structure_factor.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.kmc_host_structure_factor.argtypes = [P(capi.Params), P(capi.StateView), C.c_int32, C.c_int32, C.c_int32,
                                             C.c_void_p, C.c_void_p]
+    bo = [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32]  # which, mode, fold, r_cut, select
+    bo_local = bo + [C.c_int32, C.c_void_p, P(capi.BondOrderOut), C.c_void_p, C.c_void_p, C.c_void_p]
+    bo_corr = bo + [C.c_double, C.c_int32, C.c_void_p]
+    L.kmc_bond_order.argtypes = [C.c_void_p] + bo_local
+    L.kmc_bond_order_corr.argtypes = [C.c_void_p] + bo_corr
+    L.kmc_host_bond_order.argtypes = [P(capi.Params), P(capi.StateView)] + bo_local
+    L.kmc_host_bond_order_corr.argtypes = [P(capi.Params), P(capi.StateView)] + bo_corr
     for f in ("kmc_host_math", "kmc_device_math"):
         getattr(L, f).argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
@@ -213,6 +220,50 @@ def host_structure_factor(params: capi.Params, hs: capi.HostState, hmax: int, km
                                                          capi.sk_select(select), sums.ctypes.data,
                                                          n_sel.ctypes.data))
     return sums, n_sel
+
+
+def _bo_args(which, fold, r_cut, mode, select):
+    """The five arguments both bond order calls share, as the library takes them (r_cut None: 0.0, which only the
+    linked mode accepts)."""
+    return (capi.bo_which(which), capi.bo_mode(mode), int(fold), 0.0 if r_cut is None else float(r_cut),
+            capi.sk_select(select))
+
+
+def _bo_call(f, head, n, which, fold, r_cut, mode, select, nbins, per_protein):
+    """One kmc_bond_order / kmc_host_bond_order call: (hist[16, nbins] int64, capi.BondOrderOut) and, with
+    per_protein, (C[n], S[n] int64, nn[n] int32) by the species' reference index; a bin count out of range gets the
+    smallest buffer (the library refuses the call before it writes)."""
+    ok = 1 <= int(nbins) <= capi.BO_HIST_BINS
+    hist = np.zeros((capi.BO_NN_ROWS, int(nbins) if ok else 1), dtype=np.int64)
+    out = capi.BondOrderOut()
+    Cs, Ss, nn = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    ptr = (lambda a: a.ctypes.data if per_protein and n else None)
+    rc = f(*head, *_bo_args(which, fold, r_cut, mode, select), int(nbins), hist.ctypes.data, C.byref(out), ptr(Cs),
+           ptr(Ss), ptr(nn))
+    return rc, ((hist, out, Cs, Ss, nn) if per_protein else (hist, out))
+
+
+def host_bond_order(params: capi.Params, hs: capi.HostState, which, fold: int, r_cut=None, mode="within",
+                    select="all", nbins: int = 64, per_protein: bool = False):
+    """Bond-orientational order of a host state, sequentially (kmc_host_bond_order): as Simulation.bond_order."""
+    v = hs.view()
+    n = params.n_a if capi.bo_which(which) == capi.BO_A else params.n_b
+    rc, res = _bo_call(load_library().kmc_host_bond_order, (C.byref(params), C.byref(v)), n, which, fold, r_cut, mode,
+                       select, nbins, per_protein)
+    _host_check(rc)
+    return res
+
+
+def host_bond_order_corr(params: capi.Params, hs: capi.HostState, which, fold: int, r_max: float, r_cut=None,
+                         mode="within", select="all", nbins: int = 64) -> np.ndarray:
+    """corr[2, nbins] int64 of a host state, sequentially (kmc_host_bond_order_corr): as
+    Simulation.bond_order_corr."""
+    v = hs.view()
+    corr = np.zeros((2, int(nbins) if 1 <= int(nbins) <= capi.BO_CORR_BINS else 1), dtype=np.int64)
+    _host_check(load_library().kmc_host_bond_order_corr(C.byref(params), C.byref(v),
+                                                        *_bo_args(which, fold, r_cut, mode, select), float(r_max),
+                                                        int(nbins), corr.ctypes.data))
+    return corr
 
 
 def host_dd_check(gid: np.ndarray, own: np.ndarray) -> int:
@@ -420,10 +471,37 @@ class Simulation:
                                                         sums.ctypes.data, n_sel.ctypes.data))
         return sums, n_sel
 
+    # ---- bond-orientational order of the current state (kmc_bondorder.hip)
+    def bond_order(self, which, fold: int, r_cut=None, mode="within", select="all", nbins: int = 64,
+                   per_protein: bool = False):
+        """The local fold-fold bond-orientational order of species which ("A" receptors, "B" ligands) —
+        kmc_bond_order: (hist[16, nbins] int64 of the selected proteins by (min(neighbours, 15), bin of |psi|),
+        capi.BondOrderOut global sums), and with per_protein also (C[n], S[n] int64, nn[n] int32) by the species'
+        reference index: the sums of cos / sin (n theta) in units of 2^-30 over a protein's neighbours, and their
+        number.  mode "within": the neighbours within r_cut; "linked" (ligands): the ligands reached over a
+        receptor and its cis partner, r_cut ignored.  select "all" or "bound".  Exact integers, additive over
+        replicas (analysis.reduce_counts); analysis.bond_order turns the summary into |Psi_n|."""
+        n = self.params.n_a if capi.bo_which(which) == capi.BO_A else self.params.n_b
+        rc, res = _bo_call(load_library().kmc_bond_order, (self._h,), n, which, fold, r_cut, mode, select, nbins,
+                           per_protein)
+        self._check(rc)
+        return res
+
+    def bond_order_corr(self, which, fold: int, r_max: float, r_cut=None, mode="within", select="all",
+                        nbins: int = 64) -> np.ndarray:
+        """corr[2, nbins] int64 — kmc_bond_order_corr: over the unordered pairs of the set's proteins that have a
+        neighbour, by lateral distance below r_max: corr[0] the sums of Re(psi_i conj psi_j) in units of 2^-30,
+        corr[1] the pair counts.  The other arguments as bond_order (the call runs the local pass itself).  Additive
+        over replicas (analysis.reduce_counts); analysis.bond_order_corr turns it into (r, G_n)."""
+        corr = np.zeros((2, int(nbins) if 1 <= int(nbins) <= capi.BO_CORR_BINS else 1), dtype=np.int64)
+        self._check(load_library().kmc_bond_order_corr(self._h, *_bo_args(which, fold, r_cut, mode, select),
+                                                       float(r_max), int(nbins), corr.ctypes.data))
+        return corr
+
     @property
     def analysis_ms(self) -> float:
         """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / unwrap / cluster_* /
-        structure_factor call."""
+        structure_factor / bond_order / bond_order_corr call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
     # ---- displacement tracking since a time origin (kmc_dynamics.hip; DESIGN.md §11)
