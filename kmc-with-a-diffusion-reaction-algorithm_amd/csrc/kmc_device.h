@@ -135,8 +135,11 @@ enum : uint32_t { S_ACC = 1, S_PEND = 2, S_REJ = 3 };  // unit fate this step (a
 // ---------------------------------------------------------------- layout
 // Paired structure-of-arrays: every element is a double2 holding two
 // coordinates of ONE protein, so a lane moves 16 bytes per access (one
-// dwordx4) and a wave 1 KiB contiguous.  Element (row r, slot i) is double2
-// number r·n + i (n = NA or NB).  Receptor rows (bead (j,k), 1-based):
+// dwordx4).  The rows are blocked by BEAD_BS = 64 slots: element (row r,
+// slot i) is double2 number ((i / 64)·rows + r)·64 + i mod 64, so the rows of
+// one wave's 64 slots form one contiguous run (rows × 1 KiB), and a buffer
+// holds a whole number of 64-slot blocks (bead_slots).  Receptor rows (bead
+// (j,k), 1-based):
 //   (j-1)·4 + (k-1)              (x, y) of bead (j,k)                rows 0..15
 //   16 + (j-1)/2·4 + (k-1), j odd (z of (j,k), z of (j+1,k))         rows 16..23
 // Ligand rows: (j-1)·2 + (k-1) (x, y), rows 0..7; 8 + (j-1)/2·2 + (k-1) the z
@@ -144,45 +147,15 @@ enum : uint32_t { S_ACC = 1, S_PEND = 2, S_REJ = 3 };  // unit fate this step (a
 // SoA `[(bead·3 + c)][n]`; k_gather_beads converts at the boundary.
 #define ROWS_A 24
 #define ROWS_B 12
-// BEAD_BLOCK 1: the rows are blocked by 64 slots instead — element (r, i) is
-// number ((i / 64)·rows + r)·64 + i mod 64, so the rows of one wave's 64
-// slots form one contiguous run (rows × 1 KiB) rather than `rows` streams n
-// elements apart; the buffers then hold a whole number of 64-slot blocks.
-#ifndef BEAD_BLOCK
-#define BEAD_BLOCK 1
-#endif
 #ifndef BEAD_BS  // slots per block (a power of two dividing 64; A/B builds: smaller blocks put a protein's rows
 #define BEAD_BS 64  // fewer cache lines apart for the gathers, the streams' rows fewer bytes long)
 #endif
-#ifndef ROW_PERM  // (A/B builds) blocked layout: the rows the gathers read first in each block
-#define ROW_PERM 0
-#endif
-__host__ __device__ __forceinline__ int bead_row(int r, int rows) {
-#if ROW_PERM
-  // receptor: [j][1] xy (0, 4, 8, 12) and their z pairs (16, 20) — the exact
-  // collision test — then the [3][k] rows of the reaction gates, then the rest;
-  // ligand: [j][1] xy (0, 2, 4, 6) and z (8, 10) first
-  constexpr unsigned char PA[24] = {0, 6, 7, 8, 1, 9, 10, 11, 2, 12, 13, 14, 3, 15, 16, 17, 4, 18, 19, 20, 5, 21, 22, 23};
-  constexpr unsigned char PB[12] = {0, 6, 1, 7, 2, 8, 3, 9, 4, 10, 5, 11};
-  return rows == 24 ? PA[r] : PB[r];
-#else
-  (void)rows;
-  return r;
-#endif
-}
 __host__ __device__ __forceinline__ size_t bead_elem(int i, int r, int n, int rows) {
-#if BEAD_BLOCK
-  (void)n;
-  return ((size_t)(i / BEAD_BS) * rows + bead_row(r, rows)) * BEAD_BS + (i % BEAD_BS);
-#else
-  (void)rows;
-  return (size_t)r * n + i;
-#endif
+  (void)n;  // (the blocked layout does not depend on the buffer's length)
+  return ((size_t)(i / BEAD_BS) * rows + r) * BEAD_BS + (i % BEAD_BS);
 }
 // slots a bead buffer of n proteins holds
-__host__ __device__ __forceinline__ size_t bead_slots(int n) {
-  return BEAD_BLOCK ? ((size_t)n + 63) / 64 * 64 : (size_t)n;
-}
+__host__ __device__ __forceinline__ size_t bead_slots(int n) { return ((size_t)n + 63) / 64 * 64; }
 __host__ __device__ __forceinline__ size_t bead_off_a(int i, int j, int k, int c, int NA) {
   const int row = c < 2 ? (j - 1) * 4 + (k - 1) : 16 + ((j - 1) >> 1) * 4 + (k - 1);
   const int half = c < 2 ? c : ((j - 1) & 1);

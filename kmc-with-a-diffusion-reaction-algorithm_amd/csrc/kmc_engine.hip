@@ -1185,18 +1185,9 @@ static int launch_step(kmc_sim* s, bool re_sort) {
   const int ntiles = s->ntiles;
   // collision candidates and reaction candidates, one staging of each tile
   TIMED(KI_PAIR_SCAN, (k_pair_scan<<<ntiles, PAIR_THREADS, 0, st>>>(K, d)));
-  // the tiles too dense for the pair scan's LDS, one per workgroup, then the
-  // exact tests of the candidates
-  TIMED(KI_COL_EXACT, {
-#if DENSE_KERNEL
-    // (a second stream for it, forked after the pair scan and joined before
-    // the rounds, cost 15 us per step at C3 for the 5 us launch it hides)
-    k_col_dense<<<64, T, 0, st>>>(K, d);
-    if (s->debug_sync && hipStreamSynchronize(st) != hipSuccess)
-      return fail(s, KMC_ERR_HIP, "KMC_DEBUG_SYNC: k_col_dense failed in step " + std::to_string(s->launch_base));
-#endif
-    k_col_exact<<<std::max(gX, 64), T, 0, st>>>(K, d);
-  });
+  // the tiles too dense for the pair scan's LDS, one per workgroup (at least
+  // 64 of them), then the exact tests of the candidates
+  TIMED(KI_COL_EXACT, (k_col_exact<<<std::max(gX, 64), T, 0, st>>>(K, d)));
   if (s->debug_sync) {
     const int rc = debug_check_lists(s);
     if (rc != KMC_OK) return rc;
@@ -1209,19 +1200,9 @@ static int launch_step(kmc_sim* s, bool re_sort) {
   });
   // (the revert cannot run beside the reactions: an association snaps the
   // receptor in R_new, and a receptor of a rejected unit must be reverted
-  // before that — DESIGN.md §8, the rejected REJ_SIDE variant)
+  // before that — DESIGN.md §8, the rejected second-stream revert)
   // the revert and the exact reaction tests (one launch, k_commit_rxn)
-#ifndef COMMIT_RXN  // (A/B builds: 0 = the revert, then the reaction tests, in two launches)
-#define COMMIT_RXN 1
-#endif
-#if COMMIT_RXN
   TIMED(KI_COMMIT, (k_commit_rxn<<<gX + (K.NA > 0 ? 1024 : 0), T, 0, st>>>(K, d, gX)));
-#else
-  TIMED(KI_COMMIT, {
-    k_commit_rxn<<<gX, T, 0, st>>>(K, d, gX);
-    if (K.NA > 0) k_commit_rxn<<<1024, T, 0, st>>>(K, d, 0);
-  });
-#endif
   if (K.NA > 0) TIMED(KI_MATCH, (k_match<<<1, 1024, 0, st>>>(K, d)));
   TIMED(KI_DISS_OBSERVE, {
     if (per == 4) k_diss_observe<4><<<gP, T, 0, st>>>(K, d);

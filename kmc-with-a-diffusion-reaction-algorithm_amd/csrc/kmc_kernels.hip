@@ -1954,9 +1954,8 @@ __device__ __forceinline__ void cx_row_beads(bool lig, int row, int& b0, int& b1
   b1 = (2 * h + 1) * nk + kk;
 }
 
-#ifndef CX_ROWMAJOR  // staged complexes' (member, row) loads and stores ordered row-major (A/B,
-#define CX_ROWMAJOR 0    // profiles/r05/complex/r6u_*: k_complex_heavy at C5 428 -> 447 us, C3 52.0 -> 53.7)
-#endif
+// The staged complexes' (member, row) loads and stores run member-major, a member's rows on consecutive lanes
+// (row-major measured slower, profiles/r05/complex/r6u_*: k_complex_heavy at C5 428 -> 447 us, C3 52.0 -> 53.7).
 #ifndef CXB_IT  // (A/B: 3 -> 6, every row of a 16-member complex in one round: C5 437 -> 426 us, profiles/r05/complex/r6d_*)
 #define CXB_IT 6
 #endif
@@ -1970,11 +1969,7 @@ __device__ __forceinline__ void cx_load_beads(const Dev& d, CxLds* L, int csize,
   int qi[IT];  // member | row << 8 | ligand << 16, or -1
 #pragma unroll
   for (int it = 0; it < IT; ++it) {
-#if CX_ROWMAJOR
-    const int e = e0 + lane + it * 64, row = e / csize, q = e - row * csize;
-#else
     const int e = e0 + lane + it * 64, q = e / ROWS_A, row = e - q * ROWS_A;
-#endif
     qi[it] = -1;
     if (q < csize && row < ROWS_A) {
       const int m = L->slot[q];
@@ -2010,11 +2005,7 @@ __device__ __forceinline__ void cx_load_beads(const Dev& d, CxLds* L, int csize,
 // order (cluster.log, main.cpp:2291-2305)
 __device__ __forceinline__ void cx_write_back(const Dev& d, CxLds* L, int* grow, int csize, int nB, int NA, int lane) {
   for (int e = lane; e < csize * ROWS_A; e += 64) {
-#if CX_ROWMAJOR
-    const int row = e / csize, q = e - row * csize, m = L->slot[q];
-#else
     const int q = e / ROWS_A, row = e - q * ROWS_A, m = L->slot[q];
-#endif
     const bool lig = m >= NA;
     if (lig && row >= ROWS_B) continue;
     int b0, b1;
@@ -2462,9 +2453,6 @@ __device__ __forceinline__ void move_member(const KParams& P, const Dev& d, int 
   if (!ext) atomicOr(&d.cx_ext[root - P.NA], 1u);
 }
 
-#ifndef CXCHECK_BATCH  // (A/B builds: 0 = one chain of loads per bond site)
-#define CXCHECK_BATCH 1
-#endif
 __global__ void __launch_bounds__(256) k_cx_check(KParams P, Dev d) {
   const int NA = P.NA, NB = P.NB;
   const uint32_t n = d.ctl->n_cx;
@@ -2477,7 +2465,6 @@ __global__ void __launch_bounds__(256) k_cx_check(KParams P, Dev d) {
     const uint32_t xb = d.cx_ext[desc.x & CXD_LB];  // (set by k_move_members, cleared here)
     if (xb) d.cx_ext[desc.x & CXD_LB] = 0u;
     bool heavy = nB != 1;
-#if CXCHECK_BATCH
     if (!heavy) {
       // lay-down and every bond's alignment tests (pure: evaluated for all
       // three sites at once, whatever the others gave), in three rounds of
@@ -2500,19 +2487,6 @@ __global__ void __launch_bounds__(256) k_cx_check(KParams P, Dev d) {
         heavy |= a1r[j] > 0 && (mis[j] || (a2r[j] != 0 && cm));
       }
     }
-#else
-    if (!heavy) {
-      const int lb = desc.x;
-      heavy = N.B(lb, 1, 2, 2) != (N.B(lb, 1, 1, 2) + P.rb);
-#pragma unroll
-      for (int j = 2; j <= 4; ++j) {
-        const int a1ref = B_NEI(d, lb, j);
-        if (a1ref == 0) continue;
-        const int a1 = a1ref - 1, a2ref = A_NEI3(d, a1);
-        heavy |= bond_misaligned(P, N, lb, j, a1) || (a2ref != 0 && cis_misaligned(P, N, a1, a2ref - 1));
-      }
-    }
-#endif
     if (heavy) {
       d.cx_heavy[atomicAdd(&d.ctl->n_heavy, 1u)] = make_int4(desc.x | CXD_MOVED, desc.y, desc.z, desc.w);
       continue;
@@ -2846,9 +2820,6 @@ __device__ __forceinline__ bool prefilter(bool mA, float mx, float my, float mzl
 // (v_pk_add_f32 / v_pk_mul_f32: two lanes of arithmetic per instruction; no
 // contraction, so every value is bit-identical to the scalar form): the
 // collision prefilter and the reaction prefilter share one dxy2.
-#ifndef PAIR_PK
-#define PAIR_PK 1
-#endif
 typedef float pk2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ bool prefilter_d(bool mA, float mzl, float mzh, bool qA, float4 r, float dxy2) {
   const float dz = r.z - mzl;
@@ -3204,7 +3175,6 @@ __device__ bool tile_load(const KParams& P, const Dev& d, const TileGeo& G, Tile
   const int nflat = NPART * hh * (hw * SUBC + 1) + 1;
   const SubCol SC = sub_cols(P, G);
   __shared__ int wtot[16];
-#ifndef HDR_WAVE
   {  // home segment heads, every load in flight before the stores; cell counters zeroed
     const int xlo = max(G.hx0, 0), xhi = min(G.hx0 + mw - 1, P.ncx - 1);
     constexpr int NH = (HSEG_MAX * (HOME_MAX + 1) + 255) / 256;
@@ -3226,22 +3196,6 @@ __device__ bool tile_load(const KParams& P, const Dev& d, const TileGeo& G, Tile
     }
     for (int idx = threadIdx.x; idx < nflat; idx += blockDim.x) T.cstart[idx] = 0;
   }
-#else
-  const int lane = __lane_id(), wv = threadIdx.x >> 6, nwv = blockDim.x >> 6;
-  {  // home segment heads (a wave per segment, a lane per column); cell counters zeroed
-    const int xlo = max(G.hx0, 0), xhi = min(G.hx0 + mw - 1, P.ncx - 1);
-    for (int seg = wv; seg < nhseg; seg += nwv) {
-      const int y = G.hy0 + (seg >> 1);
-      if (lane <= mw) {
-        int v = 0;
-        if (y >= 0 && y < P.ncy && xlo <= xhi)
-          v = d.hstart[cell_index(P, min(max(G.hx0 + lane, xlo), xhi + 1), y, seg & 1)];
-        T.u.h.hs[seg][lane] = v;
-      }
-    }
-    for (int idx = threadIdx.x; idx < nflat; idx += blockDim.x) T.cstart[idx] = 0;
-  }
-#endif
   __syncthreads();
   S(d, 0);
   if (threadIdx.x < 64) {  // home segment lengths -> entries before each segment
@@ -3417,21 +3371,26 @@ __device__ __forceinline__ void item_ranges(const KParams& P, const TileLds& T, 
 // range starts — so every lane checks a pair, the owner's record is a
 // broadcast LDS read and the neighbour records of consecutive lanes are mostly
 // consecutive.
-// Owner lookup (WALK_BITS): the lanes that have pairs are first moved to the
+// Owner lookup: the lanes that have pairs are first moved to the
 // front in lane order (ds_permute), so every owner's range is non-empty and
 // their starts are distinct; each owner sets the bit of its first pair in a
 // per-wave bitmap in LDS, and the owner of pair q is (starts <= q) − 1: one
 // broadcast read of the chunk's 64 bits and a popcount per lane, in place of
 // a six-step binary search of dependent lane shuffles.
+// The owner's range of a pair is the last of its six packed words that starts
+// at or before the pair (one unsigned max over the words instead measured no
+// gain, profiles/r05/ab_walk/r7a_*: k_pair_scan 112.3 -> 113.0 us at C3,
+// 1232 -> 1237 at C5).
 // chk(l, r) for every pair; all threads call (no barrier).
-#ifndef WALK_STRIDE  // (A/B builds: 0 = each wave takes 64 consecutive records)
-#define WALK_STRIDE 1
+#define PAIR_THREADS 256  // threads of a k_pair_scan workgroup (tile_walk's wave count)
+// -DWALK_STATS=1 (diagnostic build): the pairs the walks visit, summed over
+// the launch (read by KMC_DEBUG_COUNTS)
+#ifndef WALK_STATS
+#define WALK_STATS 0
 #endif
-#ifndef WALK_BITS  // (A/B builds: 0 = binary search over the lanes' prefix)
-#define WALK_BITS 1
-#endif
-#ifndef WALK_PERM  // (A/B builds: 0 = lane L of wave w takes record base + 4L + w)
-#define WALK_PERM 1
+#if WALK_STATS
+__device__ unsigned long long kmc_walk_pairs;
+__device__ unsigned long long kmc_walk_pairs_old;  // of them, the pairs of old-position (non-proposal) items
 #endif
 // Item record of lane `lane` of wave `wv` in the 256-record block at `base`
 // (4 waves).  The waves sample the whole block (the staged records are in bin
@@ -3444,23 +3403,8 @@ __device__ __forceinline__ void item_ranges(const KParams& P, const TileLds& T, 
 // (16 records = 128 B apart mod 256 B).  Records base + 4·lane + wv (the
 // round-robin order before) put a group's lanes 64 B apart: 4-way conflicts
 // on every owner read (SQ_LDS_BANK_CONFLICT, profiles/r05/ab_walk).
-#ifndef WALK_MAXSEL  // the owner's range of a pair chosen by one unsigned max over its packed words (A/B,
-#define WALK_MAXSEL 0    // profiles/r05/ab_walk/r7a_*: k_pair_scan 112.3 -> 113.0 us at C3, 1232 -> 1237 at C5)
-#endif
-#define PAIR_THREADS 256  // threads of a k_pair_scan workgroup (tile_walk's wave count)
-// -DWALK_STATS=1 (diagnostic build): the pairs the walks visit, summed over
-// the launch (read by KMC_DEBUG_COUNTS)
-#ifndef WALK_STATS
-#define WALK_STATS 0
-#endif
-#if WALK_STATS
-__device__ unsigned long long kmc_walk_pairs;
-__device__ unsigned long long kmc_walk_pairs_old;  // of them, the pairs of old-position (non-proposal) items
-#endif
 __device__ __forceinline__ int walk_item(int base, int lane, int wv, int nw) {
-#if WALK_PERM
   if (nw == 4) return base + 16 * ((5 * (lane >> 4) + 4 * wv) & 15) + (lane & 15);
-#endif
   return base + lane * nw + wv;
 }
 template <class Rng, class Chk>
@@ -3469,16 +3413,10 @@ __device__ __forceinline__ void tile_walk(const TileGeo& G, const TileLds& T, ui
   // records go to the waves spread over the block (walk_item): the staged
   // records are in bin order, so each wave samples the whole block and the
   // waves of a workgroup walk about the same number of pairs
-#if WALK_STRIDE
   constexpr int nw = PAIR_THREADS / 64;  // (the pair scan's only block size)
   const int wv = threadIdx.x >> 6;
-#endif
   for (int base = 0; base < n; base += blockDim.x) {
-#if WALK_STRIDE
     const int l = walk_item(base, lane, wv, nw);
-#else
-    const int l = base + threadIdx.x;
-#endif
     int r0[6], r1[6];
     bool item = false;
     if (l < n) {
@@ -3491,14 +3429,9 @@ __device__ __forceinline__ void tile_walk(const TileGeo& G, const TileLds& T, ui
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       const int len = item ? r1[k] - r0[k] : 0;
-#if WALK_MAXSEL
-      pk[k] = len > 0 ? (uint32_t)r0[k] | (uint32_t)tot << 16 : 0u;  // (an empty range never wins the max)
-#else
       pk[k] = (uint32_t)(item ? r0[k] : 0) | (uint32_t)tot << 16;
-#endif
       tot += len;
     }
-#if WALK_BITS
     const uint64_t Z = __ballot(tot > 0);
     if (Z == 0) continue;  // (uniform)
     {  // owners to the front: lane `dst` receives this lane's ranges and its lane index
@@ -3511,7 +3444,6 @@ __device__ __forceinline__ void tile_walk(const TileGeo& G, const TileLds& T, ui
     }
     const int olane = (int)((uint32_t)tot >> 24);
     tot &= 0xffffff;
-#endif
     int inc = tot;  // wave-level inclusive prefix (every lane of the wave is here)
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -3529,10 +3461,6 @@ __device__ __forceinline__ void tile_walk(const TileGeo& G, const TileLds& T, ui
       if (lane == 0) atomicAdd(&kmc_walk_pairs_old, (unsigned long long)old);
     }
 #endif
-#if !WALK_STRIDE
-    const int l0 = l - lane;
-#endif
-#if WALK_BITS
     // excl < 6 TCAP · 64 < 2^24: one word carries the owner's first pair and lane
     const int ew = excl | olane << 24;
     uint32_t* wb = wbits + (threadIdx.x >> 6) * WALK_WIN;
@@ -3552,52 +3480,15 @@ __device__ __forceinline__ void tile_walk(const TileGeo& G, const TileLds& T, ui
         const int q = j + lane, oa = o << 2;
         const int eo = __builtin_amdgcn_ds_bpermute(oa, ew);
         const int t = q - (eo & 0xffffff);
-#if WALK_MAXSEL
-        // the last non-empty range starting at or before pair t: its packed
-        // word (start | pairs before << 16) is the largest below (t + 1) << 16,
-        // and x - (t + 1) << 16 (mod 2^32) orders those above every other word
-        const uint32_t T1 = (uint32_t)(t + 1) << 16;
-        uint32_t mx = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)pk[0]) - T1;
-#pragma unroll
-        for (int k = 1; k < 6; ++k) mx = max(mx, (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)pk[k]) - T1);
-        const uint32_t sel = mx + T1;
-#else
         uint32_t sel = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)pk[0]);
 #pragma unroll
         for (int k = 1; k < 6; ++k) {
           const uint32_t v = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)pk[k]);
           if ((int)(v >> 16) <= t) sel = v;
         }
-#endif
-#if WALK_STRIDE
         if (q < wtot) chk(walk_item(base, (int)((uint32_t)eo >> 24), wv, nw), (int)(sel & 0xffffu) + t - (int)(sel >> 16));
-#else
-        if (q < wtot) chk(l0 + ((uint32_t)eo >> 24), (int)(sel & 0xffffu) + t - (int)(sel >> 16));
-#endif
       }
     }
-#else
-    for (int j = 0; j < wtot; j += 64) {
-      const int q = j + lane;
-      int o = 0;  // owner: the number of lanes whose inclusive prefix is <= q
-#pragma unroll
-      for (int s = 32; s; s >>= 1)
-        if (__shfl(inc, o + s - 1, 64) <= q) o += s;
-      o = min(o, 63);
-      const int t = q - __shfl(excl, o, 64);
-      uint32_t sel = __shfl(pk[0], o, 64);
-#pragma unroll
-      for (int k = 1; k < 6; ++k) {
-        const uint32_t v = __shfl(pk[k], o, 64);
-        if ((int)(v >> 16) <= t) sel = v;
-      }
-#if WALK_STRIDE
-      if (q < wtot) chk(walk_item(base, o, wv, nw), (int)(sel & 0xffffu) + t - (int)(sel >> 16));
-#else
-      if (q < wtot) chk(l0 + o, (int)(sel & 0xffffu) + t - (int)(sel >> 16));
-#endif
-    }
-#endif
   }
 }
 
@@ -3651,13 +3542,9 @@ __device__ __forceinline__ void pair_flush(const PairBuf& b, WgList& L, const SL
 #define REACH_AB 87.5f
 #define REACH_BB 131.0f
 #define REACH_RL 106.0f
-#define REACH_CIS 58.0f
 // cis search around the item's [3][3] site: the 16 Å site prefilter + 20.3 Å
 // from a receptor's site to its record point + 1.2 Å for float rounding
 #define REACH_CSITE 37.5f
-#ifndef CIS_SITE  // (A/B builds: 0 = the cis search around the record point, REACH_CIS)
-#define CIS_SITE 1
-#endif
 
 // ---------------------------------------------------------------- 4a. scan
 // Pass A: every proposal record (member m of unit u = its owner) is checked
@@ -3710,9 +3597,6 @@ __device__ __forceinline__ void mark_rej(const Dev& d, int u, uint32_t tag) {
   if (old != (tag | S_REJ)) sl_push(d.rej, make_int2(u, 0), &d.ctl->err);  // at most once per unit
 }
 
-#ifndef COL_AA_FAST  // receptor-receptor candidates load only the rows their test reads
-#define COL_AA_FAST 1  // (A/B, profiles/r04/ab_r4r: k_col_exact 43.4 -> 39.1 us at C3)
-#endif
 // Pass B: exact fp64 overlap test of each candidate (main.cpp:640-664,
 // 1798-1826).  A collision with a record whose relevance is already known
 // (own unit, or a later unit's old position) rejects u outright; one with an
@@ -3777,9 +3661,10 @@ __device__ __forceinline__ void col_exact_one(const KParams& P, const Dev& d, co
   bool hit;
   if (P.col_refine && !col_refine(P, A, B)) {
     hit = false;
-  } else if (COL_AA_FAST && m < P.NA && q < P.NA) {
+  } else if (m < P.NA && q < P.NA) {
     // receptor against receptor: domain [1][1] against domain [1][1] only
     // (exact_collide's first case), two rows of each instead of load_own's six
+    // (profiles/r04/ab_r4r: k_col_exact 43.4 -> 39.1 us at C3)
     const Beads& Q = isnew ? d.nxt : d.cur;
     const double2 mxy = d.nxt.Axy(m, 1, 1), mz = d.nxt.A2(m, 16), qxy = Q.Axy(q, 1, 1), qz = Q.A2(q, 16);
     const double dx = qxy.x - mxy.x, dy = qxy.y - mxy.y, dz = qz.x - mz.x;
@@ -3855,12 +3740,7 @@ __device__ __forceinline__ void rec_cell_exact(const KParams& P, const Dev& d, i
 // Brute force over a dense block (k_pair_scan could not stage it): every
 // record of the block against every record of the 3x3 cells around it —
 // collision candidates tested here at once, reaction candidates emitted.
-#ifdef DENSE_NOINLINE  // (A/B builds)
-__device__ __noinline__
-#else
-__device__ __forceinline__
-#endif
-void dense_block(const KParams& P, const Dev& d, int4 blk, uint32_t tag) {
+__device__ __forceinline__ void dense_block(const KParams& P, const Dev& d, int4 blk, uint32_t tag) {
   const TileGeo G = tile_geo(blk.x & 0xffff, blk.x >> 16, blk.y & 0xffff, blk.y >> 16);
   const int obkt = blk.z, nout = blk.w;
   dense_records(P, d, G, obkt, nout, threadIdx.x, blockDim.x, [&](int ri) {
@@ -3890,31 +3770,19 @@ void dense_block(const KParams& P, const Dev& d, int4 blk, uint32_t tag) {
   });
 }
 
-// The dense tiles: in k_col_exact's first workgroups (DENSE_KERNEL 0), or in
-// a kernel of their own.  The own kernel kept k_col_exact at 58 VGPRs against
-// the brute force's 107 (round 2); since the record refinement k_col_exact
-// holds ~100 anyway, and the separate launch (4.8 µs, empty at the benchmark
-// densities) is the larger cost: C3 34.1 -> 30.1 µs for the pair, C5 equal
-// (profiles/r05/tail/r6a_*).
-#ifndef DENSE_KERNEL
-#define DENSE_KERNEL 0
-#endif
-__global__ void k_col_dense(KParams P, Dev d) {
-  const uint32_t tag = (d.ctl->step & 0x3fffffffu) << 2;
-  const uint32_t nd = min(d.ctl->n_dense, d.dense_cap);
-  for (uint32_t b = blockIdx.x; b < nd; b += gridDim.x) dense_block(P, d, d.dense[b], tag);
-}
-
+// The dense tiles run in k_col_exact's first workgroups.  A kernel of their own
+// kept k_col_exact at 58 VGPRs against the brute force's 107 (round 2); since
+// the record refinement k_col_exact holds ~100 anyway, and the separate launch
+// (4.8 µs, empty at the benchmark densities) was the larger cost: C3 34.1 ->
+// 30.1 µs for the pair, C5 equal (profiles/r05/tail/r6a_*).
 #ifndef COLX_WAVES  // minimum waves per SIMD of k_col_exact (4: the 128-VGPR cap an unbounded kernel gets)
 #define COLX_WAVES 4
 #endif
 __global__ void __launch_bounds__(256, COLX_WAVES) k_col_exact(KParams P, Dev d) {
   const uint32_t tag = (d.ctl->step & 0x3fffffffu) << 2;
   __shared__ uint32_t pre[NSHARD + 1];
-#if !DENSE_KERNEL
   const uint32_t nd = min(d.ctl->n_dense, d.dense_cap);
   for (uint32_t b = blockIdx.x; b < nd; b += gridDim.x) dense_block(P, d, d.dense[b], tag);
-#endif
   const uint32_t n = sl_prefix(d.cand, pre);
   for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
     const int2 c = sl_at(d.cand, pre, t);
@@ -4063,14 +3931,6 @@ __device__ __forceinline__ void rej_copy(const KParams& P, const Dev& d, int m, 
 #ifndef REJ_LANES  // (A/B, profiles/r04/ab_r4x: 16 -> 32 lanes, k_rej_commit 21.2 -> 18.4 us at C3)
 #define REJ_LANES 32
 #endif
-#if defined(REJ_SIDE) && REJ_SIDE
-// (measured round 4 and removed: the revert beside k_rxn_exact .. k_finalize races with the association snaps
-// of k_match, which move receptors in R_new that a revert must restore first — DESIGN.md §8)
-#error "REJ_SIDE is wrong by design"
-#endif
-#ifndef REJ_ROWMAJOR  // the (member, row) copies of a unit's lanes ordered row-major
-#define REJ_ROWMAJOR 1
-#endif
 #ifndef REJ_UNROLL  // rejected units whose lookups a lane group has in flight at once
 #define REJ_UNROLL 1
 #endif
@@ -4114,14 +3974,10 @@ __device__ __forceinline__ void rej_commit(const KParams& P, const Dev& d, uint3
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       auto member = [&](int k) { return kind[u] == U_COMPLEX ? d.members[off[u] + k] : (k ? q[u] : sl[u]); };
-#if REJ_ROWMAJOR
       // row-major over the members: neighbouring lanes copy one row of
       // neighbouring members, which the grouped slot order puts in consecutive
       // slots — the same cache line of the row's 64-slot block
       for (int e = lane; e < nm[u] * ROWS_A; e += REJ_LANES) rej_copy(P, d, member(e % nm[u]), e / nm[u]);
-#else
-      for (int e = lane; e < nm[u] * ROWS_A; e += REJ_LANES) rej_copy(P, d, member(e / ROWS_A), e % ROWS_A);
-#endif
     }
   }
 }
@@ -4185,14 +4041,9 @@ __device__ __forceinline__ bool pair_scan_block(const KParams& P, const Dev& d, 
     float x0lo = mp.x - rc0, x0hi = mp.x + rc0, y0lo = mp.y - rc0, y0hi = mp.y + rc0;
     const bool cis = rx && !(me.x & RID_ST3);
     if (cis) {
-#if CIS_SITE
       const float2 ms = site[l];
       const float sxl = ms.x - REACH_CSITE, sxh = ms.x + REACH_CSITE, syl = ms.y - REACH_CSITE,
                   syh = ms.y + REACH_CSITE;
-#else
-      const float sxl = mp.x - REACH_CIS, sxh = mp.x + REACH_CIS, syl = mp.y - REACH_CIS,
-                  syh = mp.y + REACH_CIS;
-#endif
       x0lo = rc0 > 0.0f ? fminf(x0lo, sxl) : sxl;
       x0hi = rc0 > 0.0f ? fmaxf(x0hi, sxh) : sxh;
       y0lo = rc0 > 0.0f ? fminf(y0lo, syl) : syl;
@@ -4228,7 +4079,6 @@ __device__ __forceinline__ bool pair_scan_block(const KParams& P, const Dev& d, 
       [&](int il, int nl) {
         const int2 me = T.id[il], id = T.id[nl];
         const float4 mp = T.pos[il], rp = T.pos[nl];
-#if PAIR_PK
         // col_pair and rxn_pair (below), one packed xy difference for both
         const pk2 dd = (pk2){rp.x, rp.y} - (pk2){mp.x, mp.y};
         const pk2 d2v = dd * dd;
@@ -4246,10 +4096,6 @@ __device__ __forceinline__ bool pair_scan_block(const KParams& P, const Dev& d, 
         const bool cis_ok = !qB & !(me.x & RID_ST3) & !(id.x & RID_ST3) & (dxy2 < 57.0f * 57.0f) & (gap < 16.0f) &
                             (t2v.x + t2v.y < 16.0f * 16.0f);
         const bool rxp = rxn_item(me) & (q != m) & (rl_ok | cis_ok);
-#else
-        const bool colp = me.x < 0 && me.y >= 0 && col_pair(me, mp, id, rp);
-        const bool rxp = rxn_item(me) && rxn_pair(me, mp, site[il], id, rp, site[nl]);
-#endif
         push(colp, rxp, il, nl, id);
       });
   if (bad) atomicOr(&d.ctl->err, ERR_RESOLVE);
@@ -4267,9 +4113,6 @@ __device__ __forceinline__ bool pair_scan_block(const KParams& P, const Dev& d, 
 // stays free of that path's registers and call frame (measured: a fallback
 // inside costs it a third of its speed, through the lost occupancy or the
 // scratch frame).
-#ifndef PAIR_XCD  // tiles dealt to the XCDs in contiguous runs (A/B, profiles/r04/ab_r4w: the
-#define PAIR_XCD 1   // scan's HBM fetch 79 -> 37 MB per launch at C3, its time +1 us)
-#endif
 #ifndef PAIR_WAVES  // minimum waves per SIMD of the pair scan (A/B builds: tools/build_variants.py)
 #define PAIR_WAVES 5
 #endif
@@ -4279,15 +4122,13 @@ __global__ void __launch_bounds__(PAIR_THREADS, PAIR_WAVES) k_pair_scan(KParams 
   WgList& Lc = T.u.l.Lc;
   WgList& Lr = T.u.l.Lr;
   const int ntx = (P.ncx + P.tile - 1) / P.tile;
-#if PAIR_XCD
   // XCD-aware tile order: consecutive workgroups go to the 8 XCDs in turn, so
   // workgroup b takes tile k = b / 8 of XCD b % 8's contiguous run of tiles —
   // neighbouring tiles, which stage each other's halo records, share an L2
+  // (profiles/r04/ab_r4w: the scan's HBM fetch 79 -> 37 MB per launch at C3,
+  // its time +1 us)
   const int nt = (int)gridDim.x, q8 = nt / 8, r8 = nt % 8, xcd = (int)blockIdx.x % 8;
   const int tile = xcd * q8 + min(xcd, r8) + (int)blockIdx.x / 8;
-#else
-  const int tile = (int)blockIdx.x;
-#endif
   const int tx = tile % ntx, ty = tile / ntx;
   const int x0 = tx * P.tile, y0 = ty * P.tile, w = min(P.tile, P.ncx - x0), h = min(P.tile, P.ncy - y0);
   if (threadIdx.x == 0) {  // this tile's outlier bucket (read before tile_load's first barrier), then reset
@@ -4413,17 +4254,13 @@ __device__ __forceinline__ void rxn_exact(const KParams& P, const Dev& d, uint32
 }
 
 
-// The revert of the rejected units (workgroups [0, nrej)) beside the exact
+// The revert of the rejected units (nrej workgroups) beside the exact
 // reaction tests (the rest) in one launch: the tests read each record's final
 // position where it is (R of a rejected unit, which the revert copies into
 // R_new), so neither half waits for the other; both are done before k_match
 // snaps associated receptors in R_new.
-#ifndef COMMIT_MIX  // (A/B builds: 0 = the revert's workgroups first)
-#define COMMIT_MIX 1
-#endif
 __global__ void k_commit_rxn(KParams P, Dev d, int nrej) {
   const uint32_t b = blockIdx.x, nr = (uint32_t)nrej, nx = gridDim.x - nr;
-#if COMMIT_MIX
   // the two halves' workgroups alternate while both have some left, so both
   // are resident from the start (the dispatcher goes in workgroup order)
   const uint32_t m = min(nr, nx);
@@ -4435,10 +4272,6 @@ __global__ void k_commit_rxn(KParams P, Dev d, int nrej) {
   } else {
     rxn_exact(P, d, b - m, nx);
   }
-#else
-  if (b < nr) rej_commit(P, d, b, nr);
-  else rxn_exact(P, d, b - nr, nx);
-#endif
 }
 
 // ---------------------------------------------------------------- greedy
