@@ -224,7 +224,7 @@ int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int6
 int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t max_r, int32_t max_l,
                     int64_t* hist, kmc_census* out);
 /* Device milliseconds of the last kmc_components / kmc_oligomer_census /
- * kmc_pair_counts / kmc_track_* / kmc_unwrap / kmc_cluster_* / kmc_structure_factor /
+ * kmc_pair_counts / kmc_track_* / kmc_kin_* / kmc_unwrap / kmc_cluster_* / kmc_structure_factor /
  * kmc_bond_order / kmc_bond_order_corr call: HIP events on the handle's stream around
  * its kernels and clears (the result copies to the host excluded); 0 before
  * the first. */
@@ -318,6 +318,140 @@ int kmc_track_update(kmc_sim* s, kmc_track_info* info);
 int kmc_track_sample(kmc_sim* s, double r_max, int32_t nbins, kmc_track_sample_t* out, int64_t* vanhove);
 int kmc_track_displacements(kmc_sim* s, double* u, uint8_t* flags);
 int kmc_track_end(kmc_sim* s);
+
+/* Bond kinetics: the lifetime of every R–L and cis bond —
+ * those born after the recorder began included, which the tracker's survival
+ * counters cannot see —, the waiting time until a receptor that lost its
+ * ligand binds again, to the same ligand or to another, and the event counts
+ * and exposures behind the effective on- and off-rates.  Like the tracker the
+ * recorder is a stateful layer of its own, independent of it (both may be
+ * active at once): its calls read the CURRENT state, launch nothing inside
+ * kmc_step, leave the state, the step counter and kmc_get_clusters' validity
+ * untouched and are timed by kmc_analysis_ms; the caller places
+ * kmc_kin_update between kmc_step calls.  All arithmetic is integer: the
+ * device, kmc_host_kin_* and the tests agree by equality, and every output is
+ * a plain sum, so the outputs of replicas add.  One recorder per handle.
+ *
+ * Bonds are named at receptors, by reference index i = 1..n_a, links as
+ * reference indices (what kmc_get_state returns):
+ *   R–L bond of i   the pair (lig, site) = (res_nei[i][2], res_nei[i][4]); it
+ *                   is "the same bond" only while both are unchanged.
+ *   cis bond {i, j} recorded at its lower-index member (i < j = res_nei[i][3]).
+ *                   Its kind at an update is COMPLEX when res_nei[i][2] != 0 or
+ *                   res_nei[j][2] != 0, else MONO — the reference's two
+ *                   dissociation classes (cis_diss_rate / mono_cis_diss_rate).
+ * The recorder, per receptor (kmc_kin_view):
+ *   rl_lig, rl_site  int32  the current R–L bond (0, . : none)
+ *   rl_since         int64  step at which the current R–L bond was first seen
+ *   cis_with         int32  the current cis partner
+ *   cis_since        int64  step at which the current cis bond was first seen
+ *   last_lig         int32  ligand of the last ended R–L bond; 0: none since begin
+ *   free_since       int64  step at which that loss was seen
+ *   bits             uint8  KMC_KIN_RL_CENSORED: the R–L bond existed at begin
+ *                           (left-censored); KMC_KIN_CIS_CENSORED: the cis bond
+ *                           did; KMC_KIN_COMPLEX: the cis kind at the last
+ *                           update was complex.  A censored bit is cleared
+ *                           when the next bond of its sort is born.
+ *
+ *   kmc_kin_begin   the current links are stored; since = free_since = the
+ *                   current step; last_lig = 0; bits = censored where a bond
+ *                   exists, plus the kind bit; the occupancy is counted; every
+ *                   histogram row and counter is zeroed.  Scratch is the
+ *                   recorder's own: allocated by the first begin, freed by
+ *                   kmc_kin_end / kmc_destroy.
+ *   kmc_kin_update  at step t, with D = t - last_step, in this order:
+ *                   1. exp_k += D * occ_k (the occupancy of the previous
+ *                      update) for k = rl, mono, cx, free_receptor, free_site.
+ *                   2. per receptor i, with cur = its current (lig, site, cis):
+ *                      R–L ended (rl_lig != 0 and (lig, site) differs):
+ *                        L = t - rl_since into row 1 if censored, else row 0;
+ *                        rl_off++; last_lig = rl_lig; free_since = t; if
+ *                        cur.lig != 0 also rl_swap++.
+ *                      R–L born (cur.lig != 0 and (lig, site) differs):
+ *                        rl_on++; if last_lig != 0, W = t - free_since into
+ *                        row 5 when cur.lig == last_lig, else row 6;
+ *                        rl_since = t; the censored bit is cleared.
+ *                      cis ended (old = cis_with != 0, i < old, cur.cis != old):
+ *                        L = t - cis_since into row 4 if censored, else row 3
+ *                        if the kind bit says complex, else row 2;
+ *                        cis_off_cx++ or cis_off_mono++ by the kind bit
+ *                        (censored bonds included); if cur.cis != 0 also
+ *                        cis_swap++.
+ *                      cis born (cur.cis != 0 and cur.cis != old):
+ *                        cis_since = t; the censored bit is cleared; if
+ *                        i < cur.cis, cis_on++.
+ *                      Then the stored links are replaced, the kind bit is set
+ *                      from the current state and the occupancy counted:
+ *                      occ_rl receptors with lig != 0; occ_mono / occ_cx cis
+ *                      bonds at their lower member by kind; occ_free_receptor
+ *                      = n_a - occ_rl; occ_free_site = 3 n_b - occ_rl.
+ *                   A second update at the same step changes nothing but
+ *                   n_updates.  out (may be NULL) receives the counters as of
+ *                   this update (n_*_censored_alive are a sample's: 0 here).
+ *                   With an update after every step the lifetimes are exact.
+ *                   With one every k steps they are STROBOSCOPIC: a bond that
+ *                   breaks and forms again identically between two looks
+ *                   counts as unbroken, and lifetimes are multiples of k.
+ *   bin rule        of every lifetime and waiting time v >= 0: b = v below 16;
+ *                   else, with e the index of v's top bit,
+ *                     b = 16 + 8 (e - 4) + ((v >> (e - 3)) & 7),
+ *                   clamped to KMC_KIN_BINS - 1: eight bins per octave, exact
+ *                   below 16; v >= 2^34 falls into the last bin.
+ *   kmc_kin_sample  read-only over the recorder as of the last update: out, and
+ *                   hist (may be NULL) [KMC_KIN_HISTS][KMC_KIN_BINS]: rows 0-6
+ *                   as accumulated by the updates; row 7 the ages last_step -
+ *                   rl_since of the living non-censored R–L bonds, row 8 those
+ *                   of the living non-censored cis bonds at their lower member
+ *                   — the right-censored observations of a survival estimate.
+ *                   n_rl_censored_alive / n_cis_censored_alive count the
+ *                   living bonds that rows 7 / 8 leave out.
+ *   kmc_kin_get     copies the per-receptor arrays out (every pointer of the
+ *                   view is needed, n_a entries each): tests and diagnostics.
+ *   kmc_kin_end     drops the recorder and frees its scratch.
+ *   kmc_host_kin_*  the same, sequentially, from host state views, no device:
+ *                   the recorder is the caller's view, acc and hist7
+ *                   [7][KMC_KIN_BINS]; begin fills them from state v (origin
+ *                   v->step), update advances them to state v, sample writes
+ *                   out and hist9 [9][KMC_KIN_BINS] (may be NULL).
+ * KMC_ERR_ARG for a null argument, a handle without state, a decomposed window
+ * and a recorder that was not begun; kmc_set_state, kmc_load_*,
+ * kmc_init_random and kmc_dd_set_state drop the recorder.  KMC_ERR_STATE when
+ * a receptor's link leaves its range — res_nei[i][2] in {0} or (n_a, n_a +
+ * n_b], res_nei[i][3] in {0} or [1, n_a] and not i, res_nei[i][4] in [0, 4] —
+ * nothing is read through such a link, and the recorder is dropped. */
+#define KMC_KIN_BINS 256
+#define KMC_KIN_HISTS 9
+#define KMC_KIN_RL_CENSORED 1
+#define KMC_KIN_CIS_CENSORED 2
+#define KMC_KIN_COMPLEX 4
+typedef struct kmc_kin_out {
+  int64_t origin_step, last_step; /* step of kmc_kin_begin / of the last update */
+  int64_t n_updates;
+  int64_t rl_on, rl_off, rl_swap, cis_on, cis_off_mono, cis_off_cx, cis_swap; /* events since begin */
+  int64_t exp_rl, exp_mono, exp_cx, exp_free_receptor, exp_free_site;         /* bond-steps / free steps since begin */
+  int64_t occ_rl, occ_mono, occ_cx, occ_free_receptor, occ_free_site;         /* at the last update */
+  int64_t n_rl_censored_alive, n_cis_censored_alive;                          /* kmc_kin_sample only */
+} kmc_kin_out;
+typedef struct kmc_kin_view {
+  int32_t *rl_lig, *rl_site;
+  int64_t* rl_since;
+  int32_t* cis_with;
+  int64_t* cis_since;
+  int32_t* last_lig;
+  int64_t* free_since;
+  uint8_t* bits;
+} kmc_kin_view;
+int kmc_kin_begin(kmc_sim* s);
+int kmc_kin_update(kmc_sim* s, kmc_kin_out* out);
+int kmc_kin_sample(kmc_sim* s, kmc_kin_out* out, int64_t* hist);
+int kmc_kin_get(kmc_sim* s, const kmc_kin_view* view);
+int kmc_kin_end(kmc_sim* s);
+int kmc_host_kin_begin(const kmc_params* p, const kmc_state_view* v, const kmc_kin_view* view, kmc_kin_out* acc,
+                       int64_t* hist7);
+int kmc_host_kin_update(const kmc_params* p, const kmc_state_view* v, const kmc_kin_view* view, kmc_kin_out* acc,
+                        int64_t* hist7);
+int kmc_host_kin_sample(const kmc_params* p, const kmc_kin_view* view, const kmc_kin_out* acc, const int64_t* hist7,
+                        kmc_kin_out* out, int64_t* hist9);
 
 /* Cluster geometry: a periodic image for every protein, the
  * spanning (percolation) bits of every component, and the exact integer

@@ -5,11 +5,14 @@ radius of gyration by cluster size, the fractal fit and the cluster shapes from
 the cluster geometry (cluster_geometry / cluster_list), the partial static
 structure factors S(q) and their radial average from the integer sums of
 structure_factor, the global bond-orientational order and its correlation
-G_n(r) from the integers of bond_order / bond_order_corr, and the replica sums
-of integer histograms, float64 sums and geometry tables.
+G_n(r) from the integers of bond_order / bond_order_corr, the effective on- and
+off-rates, the rebinding fraction and the Kaplan–Meier survival of bond
+lifetimes from the bond kinetics recorder (kin_sample), and the replica sums of
+integer histograms, float64 sums and geometry tables.
 
 The counts and sums themselves come from libkmc (kmc_analysis.hip,
-kmc_dynamics.hip, kmc_geometry.hip, kmc_structure.hip, kmc_bondorder.hip);
+kmc_dynamics.hip, kmc_geometry.hip, kmc_structure.hip, kmc_bondorder.hip,
+kmc_kinetics.hip);
 nothing here touches a trajectory.
 """
 from __future__ import annotations
@@ -296,3 +299,63 @@ def bond_order_corr(corr, r_max: float):
     num, cnt = corr[0].astype(np.float64), corr[1].astype(np.float64)
     g = np.divide(num, cnt, out=np.full(nbins, np.nan), where=cnt > 0) / float(1 << 30)
     return (np.arange(nbins, dtype=np.float64) + 0.5) * (r_max / nbins), g
+
+
+# ---------------------------------------------------------------- bond kinetics
+def kin_bin_edges() -> np.ndarray:
+    """The lower edges (int64, in steps) of the KIN_BINS bins of every lifetime and
+    waiting time of the kinetics histogram: b below 16; else (8 + m) << (e - 3)
+    with e = 4 + (b - 16) // 8, m = (b - 16) % 8 — eight bins per octave.  The
+    last bin is open: it also takes every value from 2^34 on."""
+    b = np.arange(capi.KIN_BINS, dtype=np.int64)
+    e, m = 4 + (b - 16) // 8, (b - 16) % 8
+    return np.where(b < 16, b, (8 + m) << np.maximum(e - 3, 0))
+
+
+def kinetics_rates(out, time_step: float, hist=None) -> dict:
+    """The effective rates from a kin_sample / kin_update result (a capi.KinOut
+    or its as_dict()), float64, zeros where a denominator is zero:
+      rl_off, cis_off_mono, cis_off_cx   events per bond-step: rl_off / exp_rl,
+                                         cis_off_mono / exp_mono, cis_off_cx / exp_cx,
+      rl_on                              per free receptor-step: rl_on / exp_free_receptor,
+      *_per_ns                           the same four divided by time_step (ns),
+    and with hist (kin_sample's histogram) rebinding_fraction: of the receptors
+    that bound again after a loss, the share that took the same ligand back,
+    row 5 / (row 5 + row 6).  The inputs are additive over replicas
+    (reduce_counts) before this call."""
+    d = out.as_dict() if hasattr(out, "as_dict") else dict(out)
+
+    def ratio(num, den):
+        return float(num) / float(den) if den else 0.0
+
+    r = {
+        "rl_off": ratio(d["rl_off"], d["exp_rl"]),
+        "cis_off_mono": ratio(d["cis_off_mono"], d["exp_mono"]),
+        "cis_off_cx": ratio(d["cis_off_cx"], d["exp_cx"]),
+        "rl_on": ratio(d["rl_on"], d["exp_free_receptor"]),
+    }
+    for k in list(r):
+        r[k + "_per_ns"] = r[k] / float(time_step) if time_step else 0.0
+    if hist is not None:
+        h = np.asarray(hist)
+        same, other = int(h[5].sum()), int(h[6].sum())
+        r["rebinding_fraction"] = ratio(same, same + other)
+    return r
+
+
+def lifetime_survival(ended_row, alive_row):
+    """Kaplan–Meier survival of bond lifetimes over the kinetics bins: ended_row
+    the lifetimes of the bonds that ended (rows 0, 2 or 3 of the histogram),
+    alive_row the ages of those still alive (rows 7 or 8: right-censored).
+    With d_b the ended and n_b the ended plus alive entries in bins >= b,
+      S_b = prod_{b' <= b} (1 - d_b' / n_b')
+    (a bin nobody reached contributes the factor 1).  Returns (the bins' lower
+    edges, S): S_b estimates the share of bonds that outlive bin b."""
+    d = np.asarray(ended_row, dtype=np.float64)
+    a = np.asarray(alive_row, dtype=np.float64)
+    if d.shape != a.shape or d.ndim != 1:
+        raise ValueError("lifetime_survival: two rows of one length")
+    at_risk = np.cumsum((d + a)[::-1])[::-1]
+    factor = 1.0 - np.divide(d, at_risk, out=np.zeros_like(d), where=at_risk > 0)
+    edges = kin_bin_edges() if d.size == capi.KIN_BINS else np.arange(d.size, dtype=np.int64)
+    return edges, np.cumprod(factor)

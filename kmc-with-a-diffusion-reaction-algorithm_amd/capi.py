@@ -205,6 +205,62 @@ class TrackSample(C.Structure):
         return d
 
 
+KIN_BINS, KIN_HISTS = 256, 9          # KMC_KIN_BINS / KMC_KIN_HISTS
+KIN_RL_CENSORED, KIN_CIS_CENSORED, KIN_COMPLEX = 1, 2, 4  # KMC_KIN_* (bits of a receptor's record)
+# rows of the kinetics histogram
+KIN_ROWS = ("rl", "rl_censored", "cis_mono", "cis_cx", "cis_censored", "rebind_same", "rebind_other", "rl_alive",
+            "cis_alive")
+
+
+class KinOut(C.Structure):
+    """kmc_kin_out — steps, event counters, exposures and occupancy of the bond kinetics recorder."""
+
+    _fields_ = [(name, C.c_int64) for name in (
+        "origin_step", "last_step", "n_updates",
+        "rl_on", "rl_off", "rl_swap", "cis_on", "cis_off_mono", "cis_off_cx", "cis_swap",
+        "exp_rl", "exp_mono", "exp_cx", "exp_free_receptor", "exp_free_site",
+        "occ_rl", "occ_mono", "occ_cx", "occ_free_receptor", "occ_free_site",
+        "n_rl_censored_alive", "n_cis_censored_alive")]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class KinView(C.Structure):
+    """kmc_kin_view — caller-owned per-receptor arrays of the recorder."""
+
+    _fields_ = [
+        ("rl_lig", C.POINTER(C.c_int32)),
+        ("rl_site", C.POINTER(C.c_int32)),
+        ("rl_since", C.POINTER(C.c_int64)),
+        ("cis_with", C.POINTER(C.c_int32)),
+        ("cis_since", C.POINTER(C.c_int64)),
+        ("last_lig", C.POINTER(C.c_int32)),
+        ("free_since", C.POINTER(C.c_int64)),
+        ("bits", C.POINTER(C.c_uint8)),
+    ]
+
+
+class KinArrays:
+    """numpy-backed kmc_kin_view for n_a receptors: the eight arrays as attributes."""
+
+    DTYPES = dict(rl_lig=np.int32, rl_site=np.int32, rl_since=np.int64, cis_with=np.int32, cis_since=np.int64,
+                  last_lig=np.int32, free_since=np.int64, bits=np.uint8)
+
+    def __init__(self, n_a: int):
+        for name, dt in self.DTYPES.items():
+            setattr(self, name, np.zeros(n_a, dtype=dt))
+
+    def view(self) -> KinView:
+        v = KinView()
+        for name, ptr in KinView._fields_:
+            setattr(v, name, getattr(self, name).ctypes.data_as(ptr))
+        return v
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name in self.DTYPES}
+
+
 GEOM_MAX_SIZE = 1023                  # KMC_GEOM_MAX_SIZE (device table bins)
 SPAN_X, SPAN_Y = 1, 2                 # KMC_SPAN_X / KMC_SPAN_Y (spanning bits)
 

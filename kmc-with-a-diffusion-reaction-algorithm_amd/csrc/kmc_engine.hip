@@ -18,6 +18,7 @@
 #include "kmc_structure.hip"
 #include "kmc_bondorder.hip"
 #include "kmc_dynamics.hip"
+#include "kmc_kinetics.hip"
 
 using namespace kmcd;
 
@@ -191,6 +192,15 @@ struct kmc_sim {
   unsigned long long* trk_vh = nullptr;      // [TRK_CLASSES][TRK_BINS_MAX] van Hove bins
   double trk_max_jump = 0.0;
   int64_t trk_origin = 0, trk_last = 0, trk_updates = 0;
+  // bond kinetics (kmc_kinetics.hip): scratch of the first kmc_kin_begin, its
+  // own; kin_on: a recorder is running (a new state drops it)
+  bool kin_on = false;
+  Kin kin = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  KinAcc* kin_acc = nullptr;
+  unsigned long long* kin_hist = nullptr;  // [KIN_HISTS][KIN_BINS]: rows 0-6 since begin, 7 and 8 of the last sample
+  int64_t kin_origin = 0, kin_last = 0, kin_updates = 0;
+  int64_t kin_occ[3] = {0, 0, 0};          // rl, mono, complex at the last update
+  int64_t kin_exp[5] = {0, 0, 0, 0, 0};    // exposures since begin
 };
 
 namespace {
@@ -883,6 +893,7 @@ static int set_state_impl(kmc_sim* s, const kmc_state_view* v) {
   s->clusters_valid = false;
   s->snap_valid = false;
   s->trk_on = false;  // the tracker's origin described another state
+  s->kin_on = false;  // and so did the kinetics recorder's links
   return KMC_OK;
 }
 
@@ -2944,6 +2955,193 @@ int kmc_track_end(kmc_sim* s) {
   if (s->stream) HIPCHK(s, hipStreamSynchronize(s->stream));
   trk_free(s);
   s->trk_on = false;
+  return KMC_OK;
+}
+
+// ---------------------------------------------------------------- bond kinetics
+// kmc_kinetics.hip: the recorder is a layer of its own over the committed
+// state, independent of the tracker; its calls write only the kin_* buffers.
+
+static int kin_check(kmc_sim* s) {
+  const int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  if (!s->kin_on) return fail(s, KMC_ERR_ARG, "kinetics: not begun (kmc_kin_begin; a new state drops the recorder)");
+  return KMC_OK;
+}
+
+static void kin_free(kmc_sim* s) {
+  dfree(s, s->kin.rl_lig);
+  dfree(s, s->kin.rl_site);
+  dfree(s, s->kin.cis_with);
+  dfree(s, s->kin.last_lig);
+  dfree(s, s->kin.rl_since);
+  dfree(s, s->kin.cis_since);
+  dfree(s, s->kin.free_since);
+  dfree(s, s->kin.bits);
+  dfree(s, s->kin_hist);
+  dfree(s, s->kin_acc);
+}
+
+// the counters of the call that just ran; a link out of range drops the recorder
+static int kin_result(kmc_sim* s, KinAcc* a) {
+  HIPCHK(s, hipMemcpy(a, s->kin_acc, sizeof *a, hipMemcpyDeviceToHost));
+  if (a->err) {
+    s->kin_on = false;
+    return fail(s, KMC_ERR_STATE, "kinetics: a receptor's bond link leaves its range");
+  }
+  return KMC_OK;
+}
+
+static void kin_fill(const kmc_sim* s, const KinAcc& a, kmc_kin_out* out) {
+  std::memset(out, 0, sizeof *out);
+  out->origin_step = s->kin_origin;
+  out->last_step = s->kin_last;
+  out->n_updates = s->kin_updates;
+  out->rl_on = (int64_t)a.ev[kmck::KIN_EV_RL_ON];
+  out->rl_off = (int64_t)a.ev[kmck::KIN_EV_RL_OFF];
+  out->rl_swap = (int64_t)a.ev[kmck::KIN_EV_RL_SWAP];
+  out->cis_on = (int64_t)a.ev[kmck::KIN_EV_CIS_ON];
+  out->cis_off_mono = (int64_t)a.ev[kmck::KIN_EV_CIS_OFF_MONO];
+  out->cis_off_cx = (int64_t)a.ev[kmck::KIN_EV_CIS_OFF_CX];
+  out->cis_swap = (int64_t)a.ev[kmck::KIN_EV_CIS_SWAP];
+  out->exp_rl = s->kin_exp[0];
+  out->exp_mono = s->kin_exp[1];
+  out->exp_cx = s->kin_exp[2];
+  out->exp_free_receptor = s->kin_exp[3];
+  out->exp_free_site = s->kin_exp[4];
+  out->occ_rl = s->kin_occ[0];
+  out->occ_mono = s->kin_occ[1];
+  out->occ_cx = s->kin_occ[2];
+  out->occ_free_receptor = (int64_t)s->p.n_a - s->kin_occ[0];
+  out->occ_free_site = 3 * (int64_t)s->p.n_b - s->kin_occ[0];
+}
+
+int kmc_kin_begin(kmc_sim* s) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const int NA = s->K.NA;
+  if (!s->kin_acc) {
+    rc = KMC_OK;
+    rc |= dalloc(s, &s->kin.rl_lig, (size_t)NA);
+    rc |= dalloc(s, &s->kin.rl_site, (size_t)NA);
+    rc |= dalloc(s, &s->kin.cis_with, (size_t)NA);
+    rc |= dalloc(s, &s->kin.last_lig, (size_t)NA);
+    rc |= dalloc(s, &s->kin.rl_since, (size_t)NA);
+    rc |= dalloc(s, &s->kin.cis_since, (size_t)NA);
+    rc |= dalloc(s, &s->kin.free_since, (size_t)NA);
+    rc |= dalloc(s, &s->kin.bits, (size_t)NA);
+    rc |= dalloc(s, &s->kin_hist, (size_t)KIN_HISTS * KIN_BINS);
+    rc |= dalloc(s, &s->kin_acc, 1);
+    if (rc != KMC_OK) {
+      kin_free(s);
+      return fail(s, KMC_ERR_HIP, "kinetics: scratch allocation failed");
+    }
+  }
+  s->kin_on = false;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemsetAsync(s->kin_acc, 0, sizeof(KinAcc), s->stream));
+  HIPCHK(s, hipMemsetAsync(s->kin_hist, 0, sizeof(unsigned long long) * KIN_HISTS * KIN_BINS, s->stream));
+  if (NA > 0)
+    k_kin_begin<<<(unsigned)((NA + KIN_T - 1) / KIN_T), KIN_T, 0, s->stream>>>(s->K, s->d, s->kin,
+                                                                              (long long)s->step_done, s->kin_acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  KinAcc a;
+  rc = kin_result(s, &a);
+  if (rc != KMC_OK) return rc;
+  s->kin_on = true;
+  s->kin_origin = s->kin_last = s->step_done;
+  s->kin_updates = 0;
+  for (int k = 0; k < 3; ++k) s->kin_occ[k] = (int64_t)a.occ[k];
+  for (auto& e : s->kin_exp) e = 0;
+  return KMC_OK;
+}
+
+int kmc_kin_update(kmc_sim* s, kmc_kin_out* out) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = kin_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  const int NA = s->K.NA;
+  // the events persist since begin; the occupancy and the error flag are of this update
+  HIPCHK(s, hipMemsetAsync(s->kin_acc->occ, 0, sizeof(KinAcc) - offsetof(KinAcc, occ), s->stream));
+  if (NA > 0)
+    k_kin_update<<<(unsigned)((NA + KIN_T - 1) / KIN_T), KIN_T, 0, s->stream>>>(
+        s->K, s->d, s->kin, (long long)s->step_done, s->kin_hist, s->kin_acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  // the occupancy is the next update's exposure: read back at every update
+  KinAcc a;
+  rc = kin_result(s, &a);
+  if (rc != KMC_OK) return rc;
+  const int64_t dt = s->step_done - s->kin_last;
+  const int64_t prev[5] = {s->kin_occ[0], s->kin_occ[1], s->kin_occ[2], (int64_t)s->p.n_a - s->kin_occ[0],
+                           3 * (int64_t)s->p.n_b - s->kin_occ[0]};
+  for (int k = 0; k < 5; ++k) s->kin_exp[k] += dt * prev[k];
+  for (int k = 0; k < 3; ++k) s->kin_occ[k] = (int64_t)a.occ[k];
+  s->kin_last = s->step_done;
+  s->kin_updates += 1;
+  if (out) kin_fill(s, a, out);
+  return KMC_OK;
+}
+
+int kmc_kin_sample(kmc_sim* s, kmc_kin_out* out, int64_t* hist) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "kinetics sample: out is needed");
+  int rc = kin_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  const int NA = s->K.NA;
+  unsigned long long* rows = s->kin_hist + (size_t)KIN_ROWS_UPD * KIN_BINS;
+  HIPCHK(s, hipMemsetAsync(rows, 0, sizeof(unsigned long long) * 2 * KIN_BINS, s->stream));
+  HIPCHK(s, hipMemsetAsync(s->kin_acc->alive, 0, sizeof(KinAcc) - offsetof(KinAcc, alive), s->stream));
+  const int nblk = (NA + KIN_T - 1) / KIN_T;
+  if (nblk > 0)
+    k_kin_sample<<<(unsigned)std::min(nblk, AN_WG_MAX), KIN_T, 0, s->stream>>>(NA, s->kin, (long long)s->kin_last, nblk,
+                                                                              rows, s->kin_acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  KinAcc a;
+  rc = kin_result(s, &a);
+  if (rc != KMC_OK) return rc;
+  kin_fill(s, a, out);
+  out->n_rl_censored_alive = (int64_t)a.alive[0];
+  out->n_cis_censored_alive = (int64_t)a.alive[1];
+  if (hist)
+    HIPCHK(s, hipMemcpy(hist, s->kin_hist, sizeof(int64_t) * KIN_HISTS * KIN_BINS, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_kin_get(kmc_sim* s, const kmc_kin_view* v) {
+  if (!s) return KMC_ERR_ARG;
+  if (!v || !v->rl_lig || !v->rl_site || !v->rl_since || !v->cis_with || !v->cis_since || !v->last_lig ||
+      !v->free_since || !v->bits)
+    return fail(s, KMC_ERR_ARG, "kinetics get: the view and its eight arrays are needed");
+  const int rc = kin_check(s);
+  if (rc != KMC_OK) return rc;
+  const size_t NA = (size_t)s->K.NA;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  HIPCHK(s, hipMemcpy(v->rl_lig, s->kin.rl_lig, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->rl_site, s->kin.rl_site, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->rl_since, s->kin.rl_since, sizeof(int64_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->cis_with, s->kin.cis_with, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->cis_since, s->kin.cis_since, sizeof(int64_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->last_lig, s->kin.last_lig, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->free_since, s->kin.free_since, sizeof(int64_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->bits, s->kin.bits, NA, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_kin_end(kmc_sim* s) {
+  if (!s) return KMC_ERR_ARG;
+  if (s->stream) HIPCHK(s, hipStreamSynchronize(s->stream));
+  kin_free(s);
+  s->kin_on = false;
   return KMC_OK;
 }
 

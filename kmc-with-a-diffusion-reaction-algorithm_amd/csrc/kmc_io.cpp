@@ -22,6 +22,7 @@
 #include "../../include/kmc.h"
 #include "kmc_bondorder.h"
 #include "kmc_host.h"
+#include "kmc_kinetics.h"
 #include "kmc_math.h"
 #include "kmc_philox.h"
 #include "kmc_state_hash.h"
@@ -1131,6 +1132,161 @@ int kmc_host_bond_order_corr(const kmc_params* p, const kmc_state_view* v, int32
       corr[k] += pc[i] * pc[j] + ps[i] * ps[j];
       corr[(size_t)nbins + k] += 1;
     });
+  return KMC_OK;
+}
+
+// Bond kinetics (include/kmc.h): kmc_kin_*'s definitions on host
+// state views, one receptor after the other; the transition and the bin rule
+// are kmc_kinetics.h's, the ones the device evaluates.
+extern "C++" {
+namespace {
+
+bool kin_view_ok(const kmc_kin_view* w) {
+  return w && w->rl_lig && w->rl_site && w->rl_since && w->cis_with && w->cis_since && w->last_lig && w->free_since &&
+         w->bits;
+}
+
+// receptor i's (0-based) current links, checked as the device checks them
+bool kin_host_cur(const kmc_params* p, const kmc_state_view* v, int i, kmck::Cur* c) {
+  const int na = p->n_a, n = p->n_a + p->n_b;
+  const int32_t n2 = v->a_int[2 * (size_t)na + i], n4 = v->a_int[3 * (size_t)na + i], n3 = v->a_int[4 * (size_t)na + i];
+  c->lig = c->site = c->cis = 0;
+  c->cx = false;
+  if (n2 != 0 && (n2 <= na || n2 > n)) return false;
+  if (n3 != 0 && (n3 < 1 || n3 > na || n3 == i + 1)) return false;
+  if (n4 < 0 || n4 > 4) return false;
+  c->lig = n2;
+  c->site = n4;
+  c->cis = n3;
+  c->cx = n3 != 0 && (n2 != 0 || v->a_int[2 * (size_t)na + (n3 - 1)] != 0);
+  return true;
+}
+
+kmck::Rec kin_load(const kmc_kin_view* w, int i) {
+  kmck::Rec r;
+  r.rl_lig = w->rl_lig[i];
+  r.rl_site = w->rl_site[i];
+  r.cis_with = w->cis_with[i];
+  r.last_lig = w->last_lig[i];
+  r.rl_since = w->rl_since[i];
+  r.cis_since = w->cis_since[i];
+  r.free_since = w->free_since[i];
+  r.bits = w->bits[i];
+  return r;
+}
+
+void kin_store(const kmc_kin_view* w, int i, const kmck::Rec& r) {
+  w->rl_lig[i] = r.rl_lig;
+  w->rl_site[i] = r.rl_site;
+  w->cis_with[i] = r.cis_with;
+  w->last_lig[i] = r.last_lig;
+  w->rl_since[i] = r.rl_since;
+  w->cis_since[i] = r.cis_since;
+  w->free_since[i] = r.free_since;
+  w->bits[i] = r.bits;
+}
+
+void kin_set_occ(const kmc_params* p, kmc_kin_out* acc, const int64_t cnt[kmck::KIN_NCNT]) {
+  acc->occ_rl = cnt[kmck::KIN_OCC_RL];
+  acc->occ_mono = cnt[kmck::KIN_OCC_MONO];
+  acc->occ_cx = cnt[kmck::KIN_OCC_CX];
+  acc->occ_free_receptor = (int64_t)p->n_a - acc->occ_rl;
+  acc->occ_free_site = 3 * (int64_t)p->n_b - acc->occ_rl;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int kmc_host_kin_begin(const kmc_params* p, const kmc_state_view* v, const kmc_kin_view* view, kmc_kin_out* acc,
+                       int64_t* hist7) {
+  if (!p || !v || !v->a_int || !kin_view_ok(view) || !acc || !hist7) {
+    g_host_err = "kinetics: params, state, the view's eight arrays, acc and hist are needed";
+    return KMC_ERR_ARG;
+  }
+  int64_t cnt[kmck::KIN_NCNT] = {0};
+  for (int i = 0; i < p->n_a; ++i) {
+    kmck::Cur c;
+    if (!kin_host_cur(p, v, i, &c)) {
+      g_host_err = "kinetics: a receptor's bond link leaves its range";
+      return KMC_ERR_STATE;
+    }
+    kmck::Rec r;
+    const uint32_t m = kmck::begin(i + 1, v->step, c, r);
+    kin_store(view, i, r);
+    for (int b = 0; b < kmck::KIN_NCNT; ++b) cnt[b] += m >> b & 1u;
+  }
+  std::memset(acc, 0, sizeof *acc);
+  std::fill(hist7, hist7 + (size_t)KIN_ROWS_UPD * KIN_BINS, (int64_t)0);
+  acc->origin_step = acc->last_step = v->step;
+  kin_set_occ(p, acc, cnt);
+  return KMC_OK;
+}
+
+int kmc_host_kin_update(const kmc_params* p, const kmc_state_view* v, const kmc_kin_view* view, kmc_kin_out* acc,
+                        int64_t* hist7) {
+  if (!p || !v || !v->a_int || !kin_view_ok(view) || !acc || !hist7) {
+    g_host_err = "kinetics: params, state, the view's eight arrays, acc and hist are needed";
+    return KMC_ERR_ARG;
+  }
+  for (int i = 0; i < p->n_a; ++i) {  // checked first: a failed call leaves the recorder as it was
+    kmck::Cur c;
+    if (!kin_host_cur(p, v, i, &c)) {
+      g_host_err = "kinetics: a receptor's bond link leaves its range";
+      return KMC_ERR_STATE;
+    }
+  }
+  const int64_t t = v->step, dt = t - acc->last_step;
+  acc->exp_rl += dt * acc->occ_rl;
+  acc->exp_mono += dt * acc->occ_mono;
+  acc->exp_cx += dt * acc->occ_cx;
+  acc->exp_free_receptor += dt * acc->occ_free_receptor;
+  acc->exp_free_site += dt * acc->occ_free_site;
+  int64_t cnt[kmck::KIN_NCNT] = {0};
+  for (int i = 0; i < p->n_a; ++i) {
+    kmck::Cur c;
+    kin_host_cur(p, v, i, &c);
+    kmck::Rec r = kin_load(view, i);
+    int row[3], nh;
+    int64_t val[3];
+    const uint32_t m = kmck::transition(i + 1, t, c, r, row, val, &nh);
+    for (int k = 0; k < nh; ++k) hist7[(size_t)row[k] * KIN_BINS + kmck::bin(val[k])] += 1;
+    kin_store(view, i, r);
+    for (int b = 0; b < kmck::KIN_NCNT; ++b) cnt[b] += m >> b & 1u;
+  }
+  acc->rl_on += cnt[kmck::KIN_EV_RL_ON];
+  acc->rl_off += cnt[kmck::KIN_EV_RL_OFF];
+  acc->rl_swap += cnt[kmck::KIN_EV_RL_SWAP];
+  acc->cis_on += cnt[kmck::KIN_EV_CIS_ON];
+  acc->cis_off_mono += cnt[kmck::KIN_EV_CIS_OFF_MONO];
+  acc->cis_off_cx += cnt[kmck::KIN_EV_CIS_OFF_CX];
+  acc->cis_swap += cnt[kmck::KIN_EV_CIS_SWAP];
+  kin_set_occ(p, acc, cnt);
+  acc->last_step = t;
+  acc->n_updates += 1;
+  return KMC_OK;
+}
+
+int kmc_host_kin_sample(const kmc_params* p, const kmc_kin_view* view, const kmc_kin_out* acc, const int64_t* hist7,
+                        kmc_kin_out* out, int64_t* hist9) {
+  if (!p || !kin_view_ok(view) || !acc || !hist7 || !out) {
+    g_host_err = "kinetics sample: params, the view's eight arrays, acc, hist and out are needed";
+    return KMC_ERR_ARG;
+  }
+  const kmc_kin_out a = *acc;  // (out may be acc itself)
+  *out = a;
+  out->n_rl_censored_alive = out->n_cis_censored_alive = 0;
+  if (hist9) {
+    std::copy(hist7, hist7 + (size_t)KIN_ROWS_UPD * KIN_BINS, hist9);
+    std::fill(hist9 + (size_t)KIN_ROWS_UPD * KIN_BINS, hist9 + (size_t)KIN_HISTS * KIN_BINS, (int64_t)0);
+  }
+  for (int i = 0; i < p->n_a; ++i) {
+    const kmck::Rec r = kin_load(view, i);
+    const uint32_t m = kmck::alive(i + 1, r);
+    if (hist9 && (m & 1u)) hist9[(size_t)kmck::KIN_ROW_RL_ALIVE * KIN_BINS + kmck::bin(a.last_step - r.rl_since)] += 1;
+    if (hist9 && (m & 2u)) hist9[(size_t)kmck::KIN_ROW_CIS_ALIVE * KIN_BINS + kmck::bin(a.last_step - r.cis_since)] += 1;
+    out->n_rl_censored_alive += m >> 2 & 1u;
+    out->n_cis_censored_alive += m >> 3 & 1u;
+  }
   return KMC_OK;
 }
 

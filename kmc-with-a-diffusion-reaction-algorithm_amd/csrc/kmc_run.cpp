@@ -48,6 +48,17 @@
 //                              msd step origin class n n_clean sum_u2 sum_u2_clean
 //                              surv step origin rl0 rl_now rl_kept cis0 cis_now cis_kept
 //                              vh step class k count        (non-empty van Hove bins)
+//           [--kin EVERY FILE]  bond kinetics (kmc_kin_*): the recorder begins at the state the
+//                            process starts or resumes from (it is not checkpointed: a resume
+//                            starts a new origin, every kin line carries it); kmc_step runs in
+//                            pieces of at most EVERY steps with an update after each (EVERY = 1:
+//                            exact lifetimes); every out_interval FILE gets one line
+//                              kin step origin n_updates rl_on rl_off rl_swap cis_on cis_off_mono
+//                                  cis_off_cx cis_swap exp_rl exp_mono exp_cx exp_free_receptor
+//                                  exp_free_site occ_rl occ_mono occ_cx occ_free_receptor
+//                                  occ_free_site n_rl_censored_alive n_cis_censored_alive
+//                            and per non-empty bin of the histogram since that origin
+//                              life step row bin count
 #include <sys/stat.h>
 
 #include <cstdio>
@@ -100,12 +111,12 @@ int main(int argc, char** argv) {
   kmc_params p;
   kmc_params_default(&p);
   int device = 0;
-  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path, psi_path;
+  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path, psi_path, kin_path;
   int psi_which = -1, psi_fold = 0, psi_nbins = 0;
   double psi_rcut = 0.0;
   int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0, geom_max = 0, sq_hmax = 0, sq_kmax = 0;
   double rdf_rmax = 0.0, dyn_rmax = 0.0;
-  int64_t dyn_every = 0;
+  int64_t dyn_every = 0, kin_every = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -179,6 +190,14 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--kin") {
+      kin_every = atoll(next().c_str());
+      kin_path = next();
+      if (kin_every < 1) {
+        fprintf(stderr, "kmc_run: bad --kin %lld\n", (long long)kin_every);
+        return 2;
+      }
+    }
     else if (a == "--set") {
       std::string kv = next();
       size_t eq = kv.find('=');
@@ -218,6 +237,7 @@ int main(int argc, char** argv) {
     if (!geom_path.empty()) truncate(geom_path.c_str());
     if (!sq_path.empty()) truncate(sq_path.c_str());
     if (!psi_path.empty()) truncate(psi_path.c_str());
+    if (!kin_path.empty()) truncate(kin_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
   }
@@ -240,23 +260,43 @@ int main(int argc, char** argv) {
     rc = kmc_track_begin(s, 0.0);
     if (rc) return die(s, rc, "track begin");
   }
+  std::vector<int64_t> life(kin_path.empty() ? 0 : (size_t)KMC_KIN_HISTS * KMC_KIN_BINS);
+  if (!kin_path.empty()) {
+    rc = kmc_kin_begin(s);
+    if (rc) return die(s, rc, "kinetics begin");
+  }
   int64_t step = kmc_current_step(s);
   while (step < p.simu_step) {
     int64_t next_out = (step / p.out_interval + 1) * p.out_interval;
     int64_t end = next_out < p.simu_step ? next_out : p.simu_step;
     int64_t n = end - step;
     obs.resize((size_t)n);
-    if (dyn_path.empty()) {
+    if (dyn_path.empty() && kin_path.empty()) {
       rc = kmc_step(s, n, obs.data());
       if (rc) return die(s, rc, "kmc_step");
     } else {
+      // pieces end where the tracker's or the recorder's next update is due (each counts from the interval's start)
+      const int64_t far = n + 1;
+      int64_t dyn_left = dyn_path.empty() ? far : dyn_every, kin_left = kin_path.empty() ? far : kin_every;
       for (int64_t done = 0; done < n;) {
-        const int64_t m = n - done < dyn_every ? n - done : dyn_every;
+        int64_t m = n - done;
+        if (dyn_left < m) m = dyn_left;
+        if (kin_left < m) m = kin_left;
         rc = kmc_step(s, m, obs.data() + done);
         if (rc) return die(s, rc, "kmc_step");
-        rc = kmc_track_update(s, nullptr);
-        if (rc) return die(s, rc, "track update");
         done += m;
+        dyn_left -= m;
+        kin_left -= m;
+        if (!dyn_path.empty() && (dyn_left == 0 || done == n)) {
+          rc = kmc_track_update(s, nullptr);
+          if (rc) return die(s, rc, "track update");
+          dyn_left = dyn_every;
+        }
+        if (!kin_path.empty() && (kin_left == 0 || done == n)) {
+          rc = kmc_kin_update(s, nullptr);
+          if (rc) return die(s, rc, "kinetics update");
+          kin_left = kin_every;
+        }
       }
     }
     step = end;
@@ -360,6 +400,25 @@ int main(int argc, char** argv) {
           for (int k = 0; k < dyn_nbins; ++k)
             if (vh[(size_t)c * dyn_nbins + k])
               fprintf(f, "vh %lld %d %d %lld\n", (long long)step, c, k, (long long)vh[(size_t)c * dyn_nbins + k]);
+        fclose(f);
+      }
+      if (!kin_path.empty()) {
+        kmc_kin_out k;
+        rc = kmc_kin_sample(s, &k, life.data());
+        if (rc) return die(s, rc, "kinetics sample");
+        f = fopen(kin_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, kin_path.c_str());
+        const int64_t fields[] = {k.origin_step, k.n_updates, k.rl_on, k.rl_off, k.rl_swap, k.cis_on, k.cis_off_mono,
+                                  k.cis_off_cx, k.cis_swap, k.exp_rl, k.exp_mono, k.exp_cx, k.exp_free_receptor,
+                                  k.exp_free_site, k.occ_rl, k.occ_mono, k.occ_cx, k.occ_free_receptor,
+                                  k.occ_free_site, k.n_rl_censored_alive, k.n_cis_censored_alive};
+        fprintf(f, "kin %lld", (long long)step);
+        for (int64_t x : fields) fprintf(f, " %lld", (long long)x);
+        fputc('\n', f);
+        for (int r = 0; r < KMC_KIN_HISTS; ++r)
+          for (int b = 0; b < KMC_KIN_BINS; ++b)
+            if (life[(size_t)r * KMC_KIN_BINS + b])
+              fprintf(f, "life %lld %d %d %lld\n", (long long)step, r, b, (long long)life[(size_t)r * KMC_KIN_BINS + b]);
         fclose(f);
       }
     }

@@ -104,6 +104,15 @@ def load_library(path: Optional[str] = None):
     L.kmc_track_sample.argtypes = [C.c_void_p, C.c_double, C.c_int32, P(capi.TrackSample), C.c_void_p]
     L.kmc_track_displacements.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.kmc_track_end.argtypes = [C.c_void_p]
+    L.kmc_kin_begin.argtypes = [C.c_void_p]
+    L.kmc_kin_update.argtypes = [C.c_void_p, P(capi.KinOut)]
+    L.kmc_kin_sample.argtypes = [C.c_void_p, P(capi.KinOut), C.c_void_p]
+    L.kmc_kin_get.argtypes = [C.c_void_p, P(capi.KinView)]
+    L.kmc_kin_end.argtypes = [C.c_void_p]
+    L.kmc_host_kin_begin.argtypes = [P(capi.Params), P(capi.StateView), P(capi.KinView), P(capi.KinOut), C.c_void_p]
+    L.kmc_host_kin_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.KinView), P(capi.KinOut), C.c_void_p]
+    L.kmc_host_kin_sample.argtypes = [P(capi.Params), P(capi.KinView), P(capi.KinOut), C.c_void_p, P(capi.KinOut),
+                                      C.c_void_p]
     L.kmc_unwrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.kmc_cluster_geometry.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, P(capi.Geom)]
     L.kmc_cluster_list.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, P(C.c_int64)]
@@ -264,6 +273,39 @@ def host_bond_order_corr(params: capi.Params, hs: capi.HostState, which, fold: i
                                                         *_bo_args(which, fold, r_cut, mode, select), float(r_max),
                                                         int(nbins), corr.ctypes.data))
     return corr
+
+
+class HostKinetics:
+    """The bond kinetics recorder on host states, sequentially (kmc_host_kin_*): Simulation.kin_*'s counterpart
+    without a device.  The recorder begins at hs; update(hs) advances it to a later state of the trajectory."""
+
+    def __init__(self, params: capi.Params, hs: capi.HostState):
+        self.params = params
+        self.arrays = capi.KinArrays(params.n_a)
+        self.acc = capi.KinOut()
+        self.hist = np.zeros((capi.KIN_HISTS - 2, capi.KIN_BINS), dtype=np.int64)
+        v = hs.view()
+        _host_check(load_library().kmc_host_kin_begin(C.byref(params), C.byref(v), C.byref(self.arrays.view()),
+                                                      C.byref(self.acc), self.hist.ctypes.data))
+
+    def update(self, hs: capi.HostState) -> capi.KinOut:
+        """Advance the recorder to hs (kmc_host_kin_update); returns the counters as of this update."""
+        v = hs.view()
+        _host_check(load_library().kmc_host_kin_update(C.byref(self.params), C.byref(v),
+                                                       C.byref(self.arrays.view()), C.byref(self.acc),
+                                                       self.hist.ctypes.data))
+        out = capi.KinOut()
+        C.memmove(C.byref(out), C.byref(self.acc), C.sizeof(out))
+        return out
+
+    def sample(self):
+        """(capi.KinOut, hist[KIN_HISTS, KIN_BINS] int64) as of the last update — kmc_host_kin_sample."""
+        out = capi.KinOut()
+        hist = np.zeros((capi.KIN_HISTS, capi.KIN_BINS), dtype=np.int64)
+        _host_check(load_library().kmc_host_kin_sample(C.byref(self.params), C.byref(self.arrays.view()),
+                                                       C.byref(self.acc), self.hist.ctypes.data, C.byref(out),
+                                                       hist.ctypes.data))
+        return out, hist
 
 
 def host_dd_check(gid: np.ndarray, own: np.ndarray) -> int:
@@ -500,8 +542,8 @@ class Simulation:
 
     @property
     def analysis_ms(self) -> float:
-        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / unwrap / cluster_* /
-        structure_factor / bond_order / bond_order_corr call."""
+        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / unwrap /
+        cluster_* / structure_factor / bond_order / bond_order_corr call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
     # ---- displacement tracking since a time origin (kmc_dynamics.hip; DESIGN.md §11)
@@ -555,6 +597,49 @@ class Simulation:
                 since = 0
                 samples.append((self.current_step,) + self.track_sample(r_max, nbins))
         return recs, samples
+
+    # ---- bond kinetics since a begin (kmc_kinetics.hip)
+    def kin_begin(self) -> None:
+        """Start the bond kinetics recorder at the current state: the bonds that exist are left-censored."""
+        self._check(load_library().kmc_kin_begin(self._h))
+
+    def kin_update(self) -> capi.KinOut:
+        """Record the bonds that ended or were born since the last update; call it between step() calls — after
+        every step for exact lifetimes (every k steps: stroboscopic ones)."""
+        out = capi.KinOut()
+        self._check(load_library().kmc_kin_update(self._h, C.byref(out)))
+        return out
+
+    def kin_sample(self):
+        """(capi.KinOut, hist[KIN_HISTS, KIN_BINS] int64) of the recorder as of the last update — kmc_kin_sample;
+        analysis.kinetics_rates and analysis.lifetime_survival post-process them."""
+        out = capi.KinOut()
+        hist = np.zeros((capi.KIN_HISTS, capi.KIN_BINS), dtype=np.int64)
+        self._check(load_library().kmc_kin_sample(self._h, C.byref(out), hist.ctypes.data))
+        return out, hist
+
+    def kin_arrays(self) -> capi.KinArrays:
+        """The recorder's per-receptor arrays by reference index (kmc_kin_get): diagnostics and tests."""
+        a = capi.KinArrays(self.params.n_a)
+        self._check(load_library().kmc_kin_get(self._h, C.byref(a.view())))
+        return a
+
+    def kin_end(self) -> None:
+        self._check(load_library().kmc_kin_end(self._h))
+
+    def run_kinetics(self, nsteps: int, every: int = 1):
+        """Advance nsteps steps in pieces of at most `every` steps with a kin_update after each piece.  The
+        recorder must have been begun.  Returns (records[nsteps], the last update's capi.KinOut or None)."""
+        if nsteps < 0 or every < 1:
+            raise ValueError("run_kinetics: nsteps >= 0, every >= 1")
+        recs = np.zeros(nsteps, dtype=capi.OBS_DTYPE)
+        done, out = 0, None
+        while done < nsteps:
+            n = min(every, nsteps - done)
+            self.step(n, recs[done:done + n])
+            done += n
+            out = self.kin_update()
+        return recs, out
 
     @property
     def current_step(self) -> int:
