@@ -224,7 +224,7 @@ int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int6
 int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t max_r, int32_t max_l,
                     int64_t* hist, kmc_census* out);
 /* Device milliseconds of the last kmc_components / kmc_oligomer_census /
- * kmc_pair_counts / kmc_track_* / kmc_kin_* / kmc_unwrap / kmc_cluster_* / kmc_structure_factor /
+ * kmc_pair_counts / kmc_track_* / kmc_kin_* / kmc_cf_* / kmc_unwrap / kmc_cluster_* / kmc_structure_factor /
  * kmc_bond_order / kmc_bond_order_corr call: HIP events on the handle's stream around
  * its kernels and clears (the result copies to the host excluded); 0 before
  * the first. */
@@ -544,6 +544,138 @@ int kmc_cluster_geometry(kmc_sim* s, int32_t max_size, kmc_geom_bin* table, kmc_
 int kmc_cluster_list(kmc_sim* s, int32_t min_size, int64_t cap, kmc_cluster* rows, int64_t* n);
 int kmc_host_cluster_geometry(const kmc_params* p, const kmc_state_view* v, int32_t* label, int32_t* shift,
                               uint8_t* span, int32_t max_size, kmc_geom_bin* table, kmc_geom* out);
+
+/* Cluster growth kinetics: which clusters merged and which
+ * fell apart between two looks, by size — the size-resolved coagulation and
+ * fragmentation events ("cf") behind K(a, b) and F(a, b), how many pieces an
+ * event had, of what kind the pieces of a binary event were, and how often a
+ * new bond closed a ring instead of joining two clusters.  Like the kinetics
+ * recorder it is a stateful layer of its own, independent of it and of the
+ * tracker (all three may be active at once): its calls read the CURRENT state,
+ * launch nothing inside kmc_step, leave the state, the step counter and
+ * kmc_get_clusters' validity untouched and are timed by kmc_analysis_ms; the
+ * caller places kmc_cf_update between kmc_step calls.  All arithmetic is
+ * integer: the device, kmc_host_cf_* and the tests agree by equality, and
+ * every table and counter but n_cores, n_clusters, max_cluster and n_s is a
+ * plain sum, so the outputs of replicas add.  One recorder per handle.
+ *
+ * Graphs.  The vertices are the N proteins by reference index 1..N.  A bond
+ * is an unordered pair: a receptor's R–L bond {i, res_nei[i][2]} (the site is
+ * not part of it: the same ligand at another site is the same edge) and its
+ * cis bond {i, res_nei[i][3]}.  E0 is the set of bonds stored at the last look
+ * (begin, update or put), E1 that of the current state, K = E0 ∩ E1 the kept
+ * bonds.  The PREVIOUS clusters are the components of E0, the CURRENT clusters
+ * those of E1, the CORES those of K; a core lies inside exactly one previous
+ * and one current cluster.  A label is the component's smallest reference
+ * index (kmc_components').  The interval between two looks is read as "all
+ * breaks, then all bonds formed": previous clusters fall into their cores,
+ * cores join into current clusters.
+ *
+ * Events of one update.  With k0(P) the number of cores of previous cluster P
+ * and k1(C) that of current cluster C: P fragments iff k0(P) >= 2, C is the
+ * product of a merger iff k1(C) >= 2.  A size n has the index min(n, S), S
+ * the max_size of the begin (index S: "S or more"; index 0 is unused); the
+ * tables hold (S + 1)^2 bins [lo][hi] of which the upper triangle lo <= hi is
+ * used.  The kind of a piece follows from its (receptors, ligands): 0 a single
+ * receptor, 1 a single ligand, 2 a receptor-only pair, 3 anything else.
+ *   every fragmenting P   frag_pieces[min(k0, 8)] += 1, frag_parent[|P|] += 1
+ *                         (filed by the core whose root is P's label)
+ *   k0(P) == 2            also frag[a][b] += 1 for the two pieces' sizes a <= b
+ *                         and frag_kind[k_lo][k_hi] += 1 for their kinds (filed
+ *                         by the core whose root is not P's label)
+ *   every merged C        merge_pieces[min(k1, 8)], merge_product[|C|], and with
+ *   k1(C) == 2            merge[a][b], merge_kind[k_lo][k_hi]: the mirror image.
+ * Counters: formed_rl, formed_cis, broken_rl, broken_cis = |E1 \ E0| and
+ * |E0 \ E1| by sort since begin; n_cores and n_clusters of the last update;
+ * the change of the bond graph's cycle rank,
+ *   cycles_closed += formed - (n_cores - n_clusters_current)
+ *   cycles_opened += broken - (n_cores - n_clusters_previous)
+ * (formed, broken: of this update); max_cluster, the largest current cluster.
+ * Occupancy and exposure: n_s[S + 1] the current cluster-size histogram; with
+ * D = step - last_step and n the n_s of the previous look,
+ *   expo[s] += D n_s;  expo2[a][b] += D n_a n_b (a < b);
+ *   expo2[a][a] += D n_a (n_a - 1) / 2          (a kmc_i128 per bin)
+ * so that K(a, b) = merge[a][b] / expo2[a][b] and F(a, b) = frag[a][b] /
+ * expo[a + b] per pair (per cluster) and step.
+ *
+ *   kmc_cf_begin    2 <= max_size <= KMC_CF_MAX_SIZE.  The current bonds and
+ *                   clusters are stored, n_s counted, every table and counter
+ *                   zeroed.  Scratch is the recorder's own: allocated by the
+ *                   first begin, freed by kmc_cf_end / kmc_destroy.
+ *   kmc_cf_update   files the events between the last look and the current
+ *                   state as above; out (may be NULL) receives the counters.
+ *                   With an update after every step the events are exact up to
+ *                   simultaneous events inside one step; with one every k
+ *                   steps they are STROBOSCOPIC: a bond that broke and formed
+ *                   again between two looks is kept.  A second update at the
+ *                   same step changes nothing but n_updates (the state is the
+ *                   last look's: it is not read again).
+ *   kmc_cf_sample  read-only over the recorder as of the last look: out, and
+ *                   the tables (tables and each of its pointers may be NULL).
+ *   kmc_cf_get      copies the recorder's per-protein state out: the stored
+ *                   bonds rl_lig[n_a], cis_with[n_a] and the labels of the
+ *                   last look prev_label[n_a + n_b] (all three are needed).
+ *   kmc_cf_put      the mirror of get: loads a recorder state saved earlier or
+ *                   built by kmc_host_cf_*, as of step last_step <= the current
+ *                   step.  A recorder must have been begun (its max_size
+ *                   stays).  The previous clusters' counts and n_s are
+ *                   recounted, origin_step = last_step, every table and
+ *                   counter is zeroed: totals add on the caller's side, as
+ *                   those of replicas do.  It makes a recorder resumable
+ *                   across a saved state.  The labels must be those of the
+ *                   stored bonds' components; checked is that every label is
+ *                   in [1, N] and the smallest member of its class and every
+ *                   link in its range, else KMC_ERR_STATE (the recorder stays
+ *                   as it was).
+ *   kmc_cf_end      drops the recorder and frees its scratch.
+ *   kmc_host_cf_*   the same, sequentially (breadth-first walks), from host
+ *                   state views, no device: the recorder is the caller's view,
+ *                   acc and tables (every pointer needed); begin fills them
+ *                   from state v (origin v->step), update advances them to
+ *                   state v, sample copies acc to out and the tables to
+ *                   tables_out (may be NULL, and so may its pointers).
+ * KMC_ERR_ARG for a null argument, a handle without state, a decomposed window
+ * and a recorder that was not begun; kmc_set_state, kmc_load_*,
+ * kmc_init_random and kmc_dd_set_state drop the recorder.  KMC_ERR_STATE when
+ * a receptor's link leaves its range — res_nei[i][2] in {0} or (n_a, n_a +
+ * n_b], res_nei[i][3] in {0} or [1, n_a] and not i — or a link chain does not
+ * end: nothing is read through such a link, and the recorder is dropped. */
+#define KMC_CF_MAX_SIZE 63
+#define KMC_CF_PIECES 9
+#define KMC_CF_KINDS 4
+typedef struct kmc_cf_out {
+  int64_t origin_step, last_step; /* step of kmc_cf_begin (or put) / of the last look */
+  int64_t n_updates;
+  int64_t max_size;                                     /* S */
+  int64_t formed_rl, formed_cis, broken_rl, broken_cis; /* bonds since begin */
+  int64_t n_cores, n_clusters;                          /* of the last update (n_cores: 0 before the first) */
+  int64_t cycles_closed, cycles_opened;                 /* since begin */
+  int64_t max_cluster;                                  /* largest current cluster */
+} kmc_cf_out;
+typedef struct kmc_cf_view {
+  int32_t *rl_lig, *cis_with; /* [n_a] */
+  int32_t* prev_label;        /* [n_a + n_b] */
+} kmc_cf_view;
+typedef struct kmc_cf_tables {
+  int64_t *merge, *frag;                 /* [(S + 1)^2] */
+  int64_t *merge_kind, *frag_kind;       /* [KMC_CF_KINDS^2] */
+  int64_t *merge_pieces, *frag_pieces;   /* [KMC_CF_PIECES] */
+  int64_t *merge_product, *frag_parent;  /* [S + 1] */
+  int64_t *n_s, *expo;                   /* [S + 1] */
+  kmc_i128* expo2;                       /* [(S + 1)^2] */
+} kmc_cf_tables;
+int kmc_cf_begin(kmc_sim* s, int32_t max_size);
+int kmc_cf_update(kmc_sim* s, kmc_cf_out* out);
+int kmc_cf_sample(kmc_sim* s, kmc_cf_out* out, const kmc_cf_tables* tables);
+int kmc_cf_get(kmc_sim* s, const kmc_cf_view* view);
+int kmc_cf_put(kmc_sim* s, const kmc_cf_view* view, int64_t last_step);
+int kmc_cf_end(kmc_sim* s);
+int kmc_host_cf_begin(const kmc_params* p, const kmc_state_view* v, int32_t max_size, const kmc_cf_view* view,
+                      kmc_cf_out* acc, const kmc_cf_tables* tables);
+int kmc_host_cf_update(const kmc_params* p, const kmc_state_view* v, const kmc_cf_view* view, kmc_cf_out* acc,
+                       const kmc_cf_tables* tables);
+int kmc_host_cf_sample(const kmc_params* p, const kmc_cf_view* view, const kmc_cf_out* acc,
+                       const kmc_cf_tables* tables, kmc_cf_out* out, const kmc_cf_tables* tables_out);
 
 /* Static structure factor: per species the sums of every
  * selected protein's (cos, sin) of q . r at the wave vectors of the half plane,

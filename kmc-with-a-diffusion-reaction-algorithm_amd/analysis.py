@@ -7,12 +7,14 @@ structure factors S(q) and their radial average from the integer sums of
 structure_factor, the global bond-orientational order and its correlation
 G_n(r) from the integers of bond_order / bond_order_corr, the effective on- and
 off-rates, the rebinding fraction and the Kaplan–Meier survival of bond
-lifetimes from the bond kinetics recorder (kin_sample), and the replica sums of
-integer histograms, float64 sums and geometry tables.
+lifetimes from the bond kinetics recorder (kin_sample), the coagulation and
+fragmentation kernels K(a, b), F(a, b) and the growth modes from the cluster
+growth recorder (cf_sample), and the replica sums of integer histograms,
+float64 sums and geometry tables.
 
 The counts and sums themselves come from libkmc (kmc_analysis.hip,
 kmc_dynamics.hip, kmc_geometry.hip, kmc_structure.hip, kmc_bondorder.hip,
-kmc_kinetics.hip);
+kmc_kinetics.hip, kmc_coag.hip);
 nothing here touches a trajectory.
 """
 from __future__ import annotations
@@ -359,3 +361,65 @@ def lifetime_survival(ended_row, alive_row):
     factor = 1.0 - np.divide(d, at_risk, out=np.zeros_like(d), where=at_risk > 0)
     edges = kin_bin_edges() if d.size == capi.KIN_BINS else np.arange(d.size, dtype=np.int64)
     return edges, np.cumprod(factor)
+
+
+# ---------------------------------------------------------------- cluster growth kinetics
+def _cf_expo2(expo2) -> list:
+    """expo2 as rows of Python ints: from capi.I128_DTYPE records (the two words), or ints already."""
+    a = np.asarray(expo2) if not isinstance(expo2, list) else None
+    if a is not None and a.dtype.names:
+        return [[(int(w["hi"]) << 64) + int(w["lo"]) for w in row] for row in a]
+    return [[int(x) for x in row] for row in expo2]
+
+
+def coag_kernel(merge, expo2) -> np.ndarray:
+    """The coagulation kernel K[a][b] = merge[a][b] / expo2[a][b] from a cf_sample's tables: binary mergers of
+    a cluster of size a with one of size b per pair of such clusters and step, float64 [S+1, S+1], symmetric;
+    nan where no such pair was ever exposed.  expo2 is capi.CfTables.expo2 (the 128-bit words, divided as
+    Python ints and rounded once) or rows of ints.  The last index stands for every size from S on.  Sum the
+    tables of replicas (reduce_counts for merge, Python ints for expo2) before this call."""
+    m = np.asarray(merge)
+    e = _cf_expo2(expo2)
+    s1 = m.shape[0]
+    k = np.full((s1, s1), np.nan)
+    for a in range(1, s1):
+        for b in range(a, s1):
+            if e[a][b] > 0:
+                k[a, b] = k[b, a] = int(m[a, b]) / e[a][b]
+    return k
+
+
+def frag_kernel(frag, expo) -> np.ndarray:
+    """The fragmentation kernel F[a][b] = frag[a][b] / expo[a + b] for a + b < S: binary fragmentations of a
+    cluster of size a + b into sizes a and b per such cluster and step, float64 [S+1, S+1], symmetric; nan
+    where a + b >= S (the parent's size is not resolved) or no such cluster was ever exposed."""
+    f, x = np.asarray(frag), np.asarray(expo)
+    s1 = f.shape[0]
+    k = np.full((s1, s1), np.nan)
+    for a in range(1, s1):
+        for b in range(a, s1):
+            if a + b < s1 - 1 and x[a + b] > 0:
+                k[a, b] = k[b, a] = int(f[a, b]) / int(x[a + b])
+    return k
+
+
+def growth_modes(out, merge_kind) -> dict:
+    """How the clusters grew, from a cf_sample's counters (a capi.CfOut or its as_dict()) and merge_kind: of
+    the binary mergers the shares in which one side was a single receptor (receptor_addition), a single
+    ligand (ligand_addition; a receptor meeting a ligand counts as the receptor's addition), and in which
+    both sides were clusters of two or more (cluster_cluster); binary_mergers, their number; and the cycle
+    counts cycles_closed / cycles_opened with ring_fraction = cycles_closed / bonds formed.  Zeros where a
+    denominator is zero."""
+    d = out.as_dict() if hasattr(out, "as_dict") else dict(out)
+    k = np.asarray(merge_kind, dtype=np.int64)
+    total = int(np.triu(k).sum())
+    rec = int(k[0, :].sum())
+    lig = int(k[1, 1:].sum())
+    formed = d["formed_rl"] + d["formed_cis"]
+
+    def ratio(num, den):
+        return float(num) / float(den) if den else 0.0
+
+    return dict(binary_mergers=total, receptor_addition=ratio(rec, total), ligand_addition=ratio(lig, total),
+                cluster_cluster=ratio(total - rec - lig, total), cycles_closed=d["cycles_closed"],
+                cycles_opened=d["cycles_opened"], ring_fraction=ratio(d["cycles_closed"], formed))

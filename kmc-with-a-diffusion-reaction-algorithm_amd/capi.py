@@ -324,6 +324,106 @@ class Cluster(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+CF_MAX_SIZE, CF_PIECES, CF_KINDS = 63, 9, 4   # KMC_CF_MAX_SIZE / KMC_CF_PIECES / KMC_CF_KINDS
+# kinds of a piece of a binary merger / fragmentation
+CF_KIND_NAMES = ("receptor", "ligand", "receptor_pair", "other")
+
+
+class CfOut(C.Structure):
+    """kmc_cf_out — steps and counters of the cluster growth recorder."""
+
+    _fields_ = [(name, C.c_int64) for name in (
+        "origin_step", "last_step", "n_updates", "max_size",
+        "formed_rl", "formed_cis", "broken_rl", "broken_cis",
+        "n_cores", "n_clusters", "cycles_closed", "cycles_opened", "max_cluster")]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class CfView(C.Structure):
+    """kmc_cf_view — caller-owned per-protein arrays of the growth recorder."""
+
+    _fields_ = [
+        ("rl_lig", C.POINTER(C.c_int32)),
+        ("cis_with", C.POINTER(C.c_int32)),
+        ("prev_label", C.POINTER(C.c_int32)),
+    ]
+
+
+class CfArrays:
+    """numpy-backed kmc_cf_view: rl_lig[n_a], cis_with[n_a], prev_label[n_a + n_b] as attributes."""
+
+    NAMES = ("rl_lig", "cis_with", "prev_label")
+
+    def __init__(self, n_a: int, n_b: int):
+        self.rl_lig = np.zeros(n_a, dtype=np.int32)
+        self.cis_with = np.zeros(n_a, dtype=np.int32)
+        self.prev_label = np.zeros(n_a + n_b, dtype=np.int32)
+
+    def view(self) -> CfView:
+        v = CfView()
+        for name, ptr in CfView._fields_:
+            setattr(v, name, getattr(self, name).ctypes.data_as(ptr))
+        return v
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name in self.NAMES}
+
+
+class CfTablesView(C.Structure):
+    """kmc_cf_tables — caller-owned tables of the growth recorder."""
+
+    _fields_ = [(name, C.POINTER(C.c_int64)) for name in (
+        "merge", "frag", "merge_kind", "frag_kind", "merge_pieces", "frag_pieces", "merge_product", "frag_parent",
+        "n_s", "expo")] + [("expo2", C.POINTER(I128))]
+
+
+# kmc_i128 as a numpy record: its two words
+I128_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<i8")])
+assert I128_DTYPE.itemsize == C.sizeof(I128)
+
+
+class CfTables:
+    """numpy-backed kmc_cf_tables for the size clamp S: merge, frag [S+1, S+1] (upper triangle), merge_kind,
+    frag_kind [4, 4], merge_pieces, frag_pieces [9], merge_product, frag_parent, n_s, expo [S+1] int64, and
+    expo2 [S+1, S+1] as I128_DTYPE records (expo2_int(): Python ints)."""
+
+    INT64 = ("merge", "frag", "merge_kind", "frag_kind", "merge_pieces", "frag_pieces", "merge_product",
+             "frag_parent", "n_s", "expo")
+
+    def __init__(self, max_size: int):
+        s1 = int(max_size) + 1
+        self.max_size = int(max_size)
+        self.merge = np.zeros((s1, s1), dtype=np.int64)
+        self.frag = np.zeros((s1, s1), dtype=np.int64)
+        self.merge_kind = np.zeros((CF_KINDS, CF_KINDS), dtype=np.int64)
+        self.frag_kind = np.zeros((CF_KINDS, CF_KINDS), dtype=np.int64)
+        self.merge_pieces = np.zeros(CF_PIECES, dtype=np.int64)
+        self.frag_pieces = np.zeros(CF_PIECES, dtype=np.int64)
+        self.merge_product = np.zeros(s1, dtype=np.int64)
+        self.frag_parent = np.zeros(s1, dtype=np.int64)
+        self.n_s = np.zeros(s1, dtype=np.int64)
+        self.expo = np.zeros(s1, dtype=np.int64)
+        self.expo2 = np.zeros((s1, s1), dtype=I128_DTYPE)
+
+    def view(self) -> CfTablesView:
+        v = CfTablesView()
+        for name, ptr in CfTablesView._fields_:
+            setattr(v, name, getattr(self, name).ctypes.data_as(ptr))
+        return v
+
+    def expo2_int(self) -> list:
+        """expo2 as rows of Python ints (the 128-bit words whole)."""
+        return [[(int(w["hi"]) << 64) + int(w["lo"]) for w in row] for row in self.expo2]
+
+    def as_dict(self) -> dict:
+        """The int64 tables by name (what analysis.reduce_counts adds over replicas) and expo2 as Python ints."""
+        d = {name: getattr(self, name) for name in self.INT64}
+        d["expo2"] = self.expo2_int()
+        return d
+
+
 def geom_m(table) -> list:
     """The 128-bit sum of m of every bin of a GEOM_BIN_DTYPE table, as Python ints."""
     return [(int(hi) << 64) + int(lo) for lo, hi in zip(table["sum_m_lo"], table["sum_m_hi"])]

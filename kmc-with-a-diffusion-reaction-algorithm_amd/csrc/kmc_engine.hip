@@ -19,6 +19,7 @@
 #include "kmc_bondorder.hip"
 #include "kmc_dynamics.hip"
 #include "kmc_kinetics.hip"
+#include "kmc_coag.hip"
 
 using namespace kmcd;
 
@@ -201,6 +202,20 @@ struct kmc_sim {
   int64_t kin_origin = 0, kin_last = 0, kin_updates = 0;
   int64_t kin_occ[3] = {0, 0, 0};          // rl, mono, complex at the last update
   int64_t kin_exp[5] = {0, 0, 0, 0, 0};    // exposures since begin
+  // cluster growth kinetics (kmc_coag.hip): scratch of the first kmc_cf_begin,
+  // its own; cf_on: a recorder is running (a new state drops it)
+  bool cf_on = false;
+  Cf cf = {nullptr, nullptr, {nullptr, nullptr}, {nullptr, nullptr}, nullptr, nullptr, nullptr, nullptr, nullptr};
+  CfTab* cf_tab = nullptr;
+  CfAcc* cf_acc = nullptr;
+  int cf_cur = 0;                       // which of the two label / count sets is the last look's
+  int cf_S = 0;                         // max_size of the begin
+  int64_t cf_origin = 0, cf_last = 0, cf_updates = 0;
+  int64_t cf_ev[CF_NEV] = {0, 0, 0, 0}; // bonds formed / broken since begin, as of the last update
+  int64_t cf_cores = 0, cf_clusters = 0, cf_max = 0, cf_closed = 0, cf_opened = 0;
+  int64_t cf_ns[CF_MAX_SIZE + 1] = {0}; // n_s of the last look
+  int64_t cf_expo[CF_MAX_SIZE + 1] = {0};
+  std::vector<__int128> cf_expo2;       // [(S + 1)^2] since begin
 };
 
 namespace {
@@ -894,6 +909,7 @@ static int set_state_impl(kmc_sim* s, const kmc_state_view* v) {
   s->snap_valid = false;
   s->trk_on = false;  // the tracker's origin described another state
   s->kin_on = false;  // and so did the kinetics recorder's links
+  s->cf_on = false;   // and the growth recorder's bonds and clusters
   return KMC_OK;
 }
 
@@ -3142,6 +3158,301 @@ int kmc_kin_end(kmc_sim* s) {
   if (s->stream) HIPCHK(s, hipStreamSynchronize(s->stream));
   kin_free(s);
   s->kin_on = false;
+  return KMC_OK;
+}
+
+// ---------------------------------------------------------------- cluster growth kinetics
+// kmc_coag.hip: a layer of its own over the committed state, independent of
+// the tracker and of the kinetics recorder; its calls write only the cf_*
+// buffers and the analysis scratch an_components fills.
+
+static int cf_check(kmc_sim* s) {
+  const int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  if (!s->cf_on) return fail(s, KMC_ERR_ARG, "growth: not begun (kmc_cf_begin; a new state drops the recorder)");
+  return KMC_OK;
+}
+
+static void cf_free(kmc_sim* s) {
+  dfree(s, s->cf.rl_lig);
+  dfree(s, s->cf.cis_with);
+  for (int k = 0; k < 2; ++k) {
+    dfree(s, s->cf.label[k]);
+    dfree(s, s->cf.cnt[k]);
+  }
+  dfree(s, s->cf.parent);
+  dfree(s, s->cf.core);
+  dfree(s, s->cf.core_cnt);
+  dfree(s, s->cf.pieces_prev);
+  dfree(s, s->cf.pieces_cur);
+  dfree(s, s->cf_tab);
+  dfree(s, s->cf_acc);
+}
+
+// the counters of the call that just ran (the components' flag included); an
+// error drops the recorder
+static int cf_result(kmc_sim* s, bool components, CfAcc* a) {
+  HIPCHK(s, hipMemcpy(a, s->cf_acc, sizeof *a, hipMemcpyDeviceToHost));
+  AnOut o;
+  o.err = 0;
+  if (components) HIPCHK(s, hipMemcpy(&o, s->an_out, sizeof o, hipMemcpyDeviceToHost));
+  if (a->err || o.err) {
+    s->cf_on = false;
+    return fail(s, KMC_ERR_STATE, "growth: a bond link leaves its range or the link chains do not end");
+  }
+  return KMC_OK;
+}
+
+// the look that a begin, an update or a put just took becomes the last one
+static void cf_look(kmc_sim* s, const CfAcc& a) {
+  s->cf_clusters = (int64_t)a.n_clusters;
+  s->cf_max = (int64_t)a.max_cluster;
+  for (int k = 0; k <= CF_MAX_SIZE; ++k) s->cf_ns[k] = (int64_t)a.n_s[k];
+}
+
+// every table and counter since begin starts again at `origin`
+static int cf_reset(kmc_sim* s, int64_t origin) {
+  HIPCHK(s, hipMemsetAsync(s->cf_tab, 0, sizeof(CfTab), s->stream));
+  HIPCHK(s, hipMemsetAsync(s->cf_acc, 0, sizeof(CfAcc), s->stream));
+  s->cf_origin = s->cf_last = origin;
+  s->cf_updates = 0;
+  for (auto& e : s->cf_ev) e = 0;
+  s->cf_cores = s->cf_closed = s->cf_opened = 0;
+  for (auto& e : s->cf_expo) e = 0;
+  s->cf_expo2.assign((size_t)(s->cf_S + 1) * (s->cf_S + 1), (__int128)0);
+  return KMC_OK;
+}
+
+static void cf_fill(const kmc_sim* s, kmc_cf_out* out) {
+  std::memset(out, 0, sizeof *out);
+  out->origin_step = s->cf_origin;
+  out->last_step = s->cf_last;
+  out->n_updates = s->cf_updates;
+  out->max_size = s->cf_S;
+  out->formed_rl = s->cf_ev[CF_EV_FORMED_RL];
+  out->formed_cis = s->cf_ev[CF_EV_FORMED_CIS];
+  out->broken_rl = s->cf_ev[CF_EV_BROKEN_RL];
+  out->broken_cis = s->cf_ev[CF_EV_BROKEN_CIS];
+  out->n_cores = s->cf_cores;
+  out->n_clusters = s->cf_clusters;
+  out->cycles_closed = s->cf_closed;
+  out->cycles_opened = s->cf_opened;
+  out->max_cluster = s->cf_max;
+}
+
+// the components of the current state into the other label / count set, which
+// becomes the last look's
+static int cf_take_components(kmc_sim* s) {
+  const int rc = an_components(s);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  s->cf_cur ^= 1;
+  HIPCHK(s, hipMemcpyAsync(s->cf.label[s->cf_cur], s->an_label, sizeof(int32_t) * N, hipMemcpyDeviceToDevice,
+                           s->stream));
+  HIPCHK(s, hipMemcpyAsync(s->cf.cnt[s->cf_cur], s->an_cnt, sizeof(unsigned long long) * N, hipMemcpyDeviceToDevice,
+                           s->stream));
+  return KMC_OK;
+}
+
+int kmc_cf_begin(kmc_sim* s, int32_t max_size) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  if (max_size < CF_MIN_SIZE || max_size > CF_MAX_SIZE)
+    return fail(s, KMC_ERR_ARG, "growth begin: 2 <= max_size <= " + std::to_string(CF_MAX_SIZE));
+  const int NA = s->K.NA, N = s->K.N;
+  if (!s->cf_acc) {
+    rc = KMC_OK;
+    rc |= dalloc(s, &s->cf.rl_lig, (size_t)NA);
+    rc |= dalloc(s, &s->cf.cis_with, (size_t)NA);
+    for (int k = 0; k < 2; ++k) {
+      rc |= dalloc(s, &s->cf.label[k], (size_t)N);
+      rc |= dalloc(s, &s->cf.cnt[k], (size_t)N);
+    }
+    rc |= dalloc(s, &s->cf.parent, (size_t)N);
+    rc |= dalloc(s, &s->cf.core, (size_t)N);
+    rc |= dalloc(s, &s->cf.core_cnt, (size_t)N);
+    rc |= dalloc(s, &s->cf.pieces_prev, (size_t)N);
+    rc |= dalloc(s, &s->cf.pieces_cur, (size_t)N);
+    rc |= dalloc(s, &s->cf_tab, 1);
+    rc |= dalloc(s, &s->cf_acc, 1);
+    if (rc != KMC_OK) {
+      cf_free(s);
+      return fail(s, KMC_ERR_HIP, "growth: scratch allocation failed");
+    }
+  }
+  s->cf_on = false;
+  s->cf_S = max_size;
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = cf_reset(s, s->step_done);
+  if (rc == KMC_OK) rc = cf_take_components(s);
+  if (rc != KMC_OK) return rc;
+  if (NA > 0) k_cf_begin<<<(unsigned)((NA + CF_T - 1) / CF_T), CF_T, 0, s->stream>>>(s->K, s->d, s->cf, s->cf_acc);
+  if (N > 0)
+    k_cf_sizes<<<(unsigned)((N + CF_T - 1) / CF_T), CF_T, 0, s->stream>>>(s->cf.label[s->cf_cur], s->cf.cnt[s->cf_cur],
+                                                                           N, s->cf_S, s->cf_acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  CfAcc a;
+  rc = cf_result(s, true, &a);
+  if (rc != KMC_OK) return rc;
+  cf_look(s, a);
+  s->cf_on = true;
+  return KMC_OK;
+}
+
+int kmc_cf_update(kmc_sim* s, kmc_cf_out* out) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = cf_check(s);
+  if (rc != KMC_OK) return rc;
+  if (s->step_done == s->cf_last) {  // the state of the last look: nothing to file
+    s->cf_updates += 1;
+    if (out) cf_fill(s, out);
+    return KMC_OK;
+  }
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = cf_take_components(s);
+  if (rc != KMC_OK) return rc;
+  const int NA = s->K.NA, N = s->K.N, cur = s->cf_cur, prev = cur ^ 1;
+  // the bond counters persist since begin; the rest is of this update
+  HIPCHK(s, hipMemsetAsync(&s->cf_acc->n_cores, 0, sizeof(CfAcc) - offsetof(CfAcc, n_cores), s->stream));
+  const unsigned g = (unsigned)((N + CF_T - 1) / CF_T);
+  if (g) {
+    k_cf_init<<<g, CF_T, 0, s->stream>>>(s->cf, N);
+    if (NA > 0) k_cf_hook<<<(unsigned)((NA + CF_T - 1) / CF_T), CF_T, 0, s->stream>>>(s->K, s->d, s->cf, s->cf_acc);
+    k_cf_flatten<<<g, CF_T, 0, s->stream>>>(s->cf, s->cf.label[prev], s->cf.label[cur], NA, N, s->cf_acc);
+    k_cf_events<<<g, CF_T, 0, s->stream>>>(s->cf, s->cf.label[prev], s->cf.cnt[prev], s->cf.label[cur],
+                                           s->cf.cnt[cur], N, s->cf_S, s->cf_tab, s->cf_acc);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  CfAcc a;
+  rc = cf_result(s, true, &a);
+  if (rc != KMC_OK) return rc;
+  // exposures of the interval that ended, from the previous look's n_s
+  const int S = s->cf_S;
+  const int64_t dt = s->step_done - s->cf_last;
+  for (int x = 1; x <= S; ++x) {
+    const int64_t nx = s->cf_ns[x];
+    s->cf_expo[x] += dt * nx;
+    s->cf_expo2[(size_t)x * (S + 1) + x] += (__int128)dt * nx * (nx - 1) / 2;
+    for (int y = x + 1; y <= S; ++y) s->cf_expo2[(size_t)x * (S + 1) + y] += (__int128)dt * nx * s->cf_ns[y];
+  }
+  // the change of the cycle rank, from this update's bonds
+  int64_t ev[CF_NEV];
+  for (int k = 0; k < CF_NEV; ++k) ev[k] = (int64_t)a.ev[k] - s->cf_ev[k];
+  const int64_t formed = ev[CF_EV_FORMED_RL] + ev[CF_EV_FORMED_CIS], broken = ev[CF_EV_BROKEN_RL] + ev[CF_EV_BROKEN_CIS];
+  const int64_t cores = (int64_t)a.n_cores;
+  s->cf_closed += formed - (cores - (int64_t)a.n_clusters);
+  s->cf_opened += broken - (cores - s->cf_clusters);
+  for (int k = 0; k < CF_NEV; ++k) s->cf_ev[k] = (int64_t)a.ev[k];
+  s->cf_cores = cores;
+  cf_look(s, a);
+  s->cf_last = s->step_done;
+  s->cf_updates += 1;
+  if (out) cf_fill(s, out);
+  return KMC_OK;
+}
+
+int kmc_cf_sample(kmc_sim* s, kmc_cf_out* out, const kmc_cf_tables* t) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "growth sample: out is needed");
+  const int rc = cf_check(s);
+  if (rc != KMC_OK) return rc;
+  cf_fill(s, out);
+  if (!t) return KMC_OK;
+  const int S = s->cf_S;
+  const size_t n1 = (size_t)S + 1, n2 = n1 * n1;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  auto pull = [&](int64_t* dst, const unsigned long long* src, size_t n) -> hipError_t {
+    return dst ? hipMemcpy(dst, src, sizeof(int64_t) * n, hipMemcpyDeviceToHost) : hipSuccess;
+  };
+  HIPCHK(s, pull(t->merge, s->cf_tab->merge, n2));
+  HIPCHK(s, pull(t->frag, s->cf_tab->frag, n2));
+  HIPCHK(s, pull(t->merge_kind, s->cf_tab->merge_kind, CF_KINDS * CF_KINDS));
+  HIPCHK(s, pull(t->frag_kind, s->cf_tab->frag_kind, CF_KINDS * CF_KINDS));
+  HIPCHK(s, pull(t->merge_pieces, s->cf_tab->merge_pieces, CF_PIECES));
+  HIPCHK(s, pull(t->frag_pieces, s->cf_tab->frag_pieces, CF_PIECES));
+  HIPCHK(s, pull(t->merge_product, s->cf_tab->merge_product, n1));
+  HIPCHK(s, pull(t->frag_parent, s->cf_tab->frag_parent, n1));
+  if (t->n_s) std::copy(s->cf_ns, s->cf_ns + n1, t->n_s);
+  if (t->expo) std::copy(s->cf_expo, s->cf_expo + n1, t->expo);
+  if (t->expo2)
+    for (size_t b = 0; b < n2; ++b) {
+      t->expo2[b].lo = (uint64_t)(unsigned __int128)s->cf_expo2[b];
+      t->expo2[b].hi = (int64_t)(s->cf_expo2[b] >> 64);
+    }
+  return KMC_OK;
+}
+
+int kmc_cf_get(kmc_sim* s, const kmc_cf_view* v) {
+  if (!s) return KMC_ERR_ARG;
+  if (!v || !v->rl_lig || !v->cis_with || !v->prev_label)
+    return fail(s, KMC_ERR_ARG, "growth get: the view and its three arrays are needed");
+  const int rc = cf_check(s);
+  if (rc != KMC_OK) return rc;
+  const size_t NA = (size_t)s->K.NA, N = (size_t)s->K.N;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  HIPCHK(s, hipMemcpy(v->rl_lig, s->cf.rl_lig, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->cis_with, s->cf.cis_with, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->prev_label, s->cf.label[s->cf_cur], sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < N; ++i) v->prev_label[i] += 1;
+  return KMC_OK;
+}
+
+int kmc_cf_put(kmc_sim* s, const kmc_cf_view* v, int64_t last_step) {
+  if (!s) return KMC_ERR_ARG;
+  if (!v || !v->rl_lig || !v->cis_with || !v->prev_label)
+    return fail(s, KMC_ERR_ARG, "growth put: the view and its three arrays are needed");
+  int rc = cf_check(s);
+  if (rc != KMC_OK) return rc;
+  if (last_step > s->step_done) return fail(s, KMC_ERR_ARG, "growth put: last_step lies after the current step");
+  const int NA = s->K.NA, N = s->K.N;
+  for (int i = 0; i < NA; ++i) {
+    const int32_t l = v->rl_lig[i], c = v->cis_with[i];
+    if ((l != 0 && (l <= NA || l > N)) || (c != 0 && (c < 1 || c > NA || c == i + 1)))
+      return fail(s, KMC_ERR_STATE, "growth put: a stored bond of receptor " + std::to_string(i + 1) + " leaves its range");
+  }
+  std::vector<int32_t> lab((size_t)N);
+  for (int i = 0; i < N; ++i) {
+    const int32_t l = v->prev_label[i];
+    // a class' label is one of its members, labelled by itself, and no member lies below it
+    if (l < 1 || l > i + 1 || v->prev_label[l - 1] != l)
+      return fail(s, KMC_ERR_STATE, "growth put: the label of protein " + std::to_string(i + 1) +
+                                        " is out of range or not the smallest member of its class");
+    lab[(size_t)i] = l - 1;
+  }
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = cf_reset(s, last_step);
+  if (rc != KMC_OK) return rc;
+  const int cur = s->cf_cur;
+  hipStream_t st = s->stream;
+  HIPCHK(s, hipMemcpyAsync(s->cf.rl_lig, v->rl_lig, sizeof(int32_t) * (size_t)NA, hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemcpyAsync(s->cf.cis_with, v->cis_with, sizeof(int32_t) * (size_t)NA, hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemcpyAsync(s->cf.label[cur], lab.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemsetAsync(s->cf.cnt[cur], 0, sizeof(unsigned long long) * (size_t)N, st));
+  const unsigned g = (unsigned)((N + CF_T - 1) / CF_T);
+  if (g) {
+    k_an_count<<<g, AN_T, 0, st>>>(s->cf.label[cur], s->cf.cnt[cur], NA, N);
+    k_cf_sizes<<<g, CF_T, 0, st>>>(s->cf.label[cur], s->cf.cnt[cur], N, s->cf_S, s->cf_acc);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);  // (waits: lab is read by the copy until here)
+  if (rc != KMC_OK) return rc;
+  CfAcc a;
+  rc = cf_result(s, false, &a);
+  if (rc != KMC_OK) return rc;
+  cf_look(s, a);
+  return KMC_OK;
+}
+
+int kmc_cf_end(kmc_sim* s) {
+  if (!s) return KMC_ERR_ARG;
+  if (s->stream) HIPCHK(s, hipStreamSynchronize(s->stream));
+  cf_free(s);
+  s->cf_on = false;
   return KMC_OK;
 }
 

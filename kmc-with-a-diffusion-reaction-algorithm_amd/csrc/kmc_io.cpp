@@ -21,6 +21,7 @@
 
 #include "../../include/kmc.h"
 #include "kmc_bondorder.h"
+#include "kmc_coag.h"
 #include "kmc_host.h"
 #include "kmc_kinetics.h"
 #include "kmc_math.h"
@@ -1287,6 +1288,266 @@ int kmc_host_kin_sample(const kmc_params* p, const kmc_kin_view* view, const kmc
     out->n_rl_censored_alive += m >> 2 & 1u;
     out->n_cis_censored_alive += m >> 3 & 1u;
   }
+  return KMC_OK;
+}
+
+// Cluster growth kinetics (include/kmc.h): kmc_cf_*'s
+// definitions on host state views.  Where the device runs two lock-free
+// union-finds, the partitions here come from breadth-first walks over an
+// adjacency list (the walk's start, in index order, is the label); the filing
+// rule is kmc_coag.h's, the one the device evaluates.
+extern "C++" {
+namespace {
+
+typedef std::pair<int32_t, int32_t> CfEdge;
+
+bool cf_view_ok(const kmc_cf_view* w) { return w && w->rl_lig && w->cis_with && w->prev_label; }
+
+bool cf_tables_ok(const kmc_cf_tables* t) {
+  return t && t->merge && t->frag && t->merge_kind && t->frag_kind && t->merge_pieces && t->frag_pieces &&
+         t->merge_product && t->frag_parent && t->n_s && t->expo && t->expo2;
+}
+
+// receptor i's (0-based) current bonds, checked as the device checks them
+bool cf_host_cur(const kmc_params* p, const kmc_state_view* v, int i, int32_t* lig, int32_t* cis) {
+  const int na = p->n_a, n = p->n_a + p->n_b;
+  const int32_t n2 = v->a_int[2 * (size_t)na + i], n3 = v->a_int[4 * (size_t)na + i];
+  *lig = *cis = 0;
+  if (n2 != 0 && (n2 <= na || n2 > n)) return false;
+  if (n3 != 0 && (n3 < 1 || n3 > na || n3 == i + 1)) return false;
+  *lig = n2;
+  *cis = n3;
+  return true;
+}
+
+// components of n vertices under `edges` (0-based ends): label[i] = the
+// smallest member (0-based), cnt[label] = the packed (receptors, ligands)
+void cf_walk(int n, int na, const std::vector<CfEdge>& edges, std::vector<int32_t>& label,
+             std::vector<uint64_t>& cnt) {
+  std::vector<int32_t> start((size_t)n + 1, 0), adj(2 * edges.size()), queue;
+  for (const CfEdge& e : edges) {
+    start[(size_t)e.first + 1] += 1;
+    start[(size_t)e.second + 1] += 1;
+  }
+  for (int i = 0; i < n; ++i) start[(size_t)i + 1] += start[(size_t)i];
+  std::vector<int32_t> fill(start.begin(), start.end() - 1);
+  for (const CfEdge& e : edges) {
+    adj[(size_t)fill[(size_t)e.first]++] = e.second;
+    adj[(size_t)fill[(size_t)e.second]++] = e.first;
+  }
+  label.assign((size_t)n, -1);
+  cnt.assign((size_t)n, 0);
+  queue.reserve((size_t)n);
+  for (int r = 0; r < n; ++r) {
+    if (label[(size_t)r] >= 0) continue;
+    queue.clear();
+    queue.push_back(r);
+    label[(size_t)r] = r;
+    for (size_t h = 0; h < queue.size(); ++h) {
+      const int q = queue[h];
+      cnt[(size_t)r] += q < na ? 1ull : 1ull << 32;
+      for (int32_t k = start[(size_t)q]; k < start[(size_t)q + 1]; ++k)
+        if (label[(size_t)adj[(size_t)k]] < 0) {
+          label[(size_t)adj[(size_t)k]] = r;
+          queue.push_back(adj[(size_t)k]);
+        }
+    }
+  }
+}
+
+// the look at `label` / `cnt` becomes the last one: n_s, n_clusters, max_cluster
+void cf_host_look(int n, int S, const std::vector<int32_t>& label, const std::vector<uint64_t>& cnt, kmc_cf_out* acc,
+                  int64_t* n_s) {
+  std::fill(n_s, n_s + S + 1, (int64_t)0);
+  acc->n_clusters = acc->max_cluster = 0;
+  for (int i = 0; i < n; ++i) {
+    if (label[(size_t)i] != i) continue;
+    const int size = kmcc::size_of(cnt[(size_t)i]);
+    n_s[kmcc::clamp_size(size, S)] += 1;
+    acc->n_clusters += 1;
+    if (size > acc->max_cluster) acc->max_cluster = size;
+  }
+}
+
+}  // namespace
+}  // extern "C++"
+
+int kmc_host_cf_begin(const kmc_params* p, const kmc_state_view* v, int32_t max_size, const kmc_cf_view* view,
+                      kmc_cf_out* acc, const kmc_cf_tables* t) {
+  if (!p || !v || !v->a_int || !cf_view_ok(view) || !acc || !cf_tables_ok(t) || max_size < CF_MIN_SIZE ||
+      max_size > CF_MAX_SIZE) {
+    g_host_err = "growth: params, state, the view's three arrays, acc and every table are needed, 2 <= max_size <= 63";
+    return KMC_ERR_ARG;
+  }
+  const int na = p->n_a, n = p->n_a + p->n_b, S = max_size;
+  std::vector<CfEdge> e1;
+  for (int i = 0; i < na; ++i) {
+    int32_t lig, cis;
+    if (!cf_host_cur(p, v, i, &lig, &cis)) {
+      g_host_err = "growth: a receptor's bond link leaves its range";
+      return KMC_ERR_STATE;
+    }
+    if (lig) e1.push_back(CfEdge(i, lig - 1));
+    if (cis && i + 1 < cis) e1.push_back(CfEdge(i, cis - 1));
+  }
+  for (int i = 0; i < na; ++i) cf_host_cur(p, v, i, &view->rl_lig[i], &view->cis_with[i]);
+  std::vector<int32_t> label;
+  std::vector<uint64_t> cnt;
+  cf_walk(n, na, e1, label, cnt);
+  for (int i = 0; i < n; ++i) view->prev_label[i] = label[(size_t)i] + 1;
+  const size_t n1 = (size_t)S + 1, n2 = n1 * n1;
+  std::memset(acc, 0, sizeof *acc);
+  std::fill(t->merge, t->merge + n2, (int64_t)0);
+  std::fill(t->frag, t->frag + n2, (int64_t)0);
+  std::fill(t->merge_kind, t->merge_kind + CF_KINDS * CF_KINDS, (int64_t)0);
+  std::fill(t->frag_kind, t->frag_kind + CF_KINDS * CF_KINDS, (int64_t)0);
+  std::fill(t->merge_pieces, t->merge_pieces + CF_PIECES, (int64_t)0);
+  std::fill(t->frag_pieces, t->frag_pieces + CF_PIECES, (int64_t)0);
+  std::fill(t->merge_product, t->merge_product + n1, (int64_t)0);
+  std::fill(t->frag_parent, t->frag_parent + n1, (int64_t)0);
+  std::fill(t->expo, t->expo + n1, (int64_t)0);
+  std::memset(t->expo2, 0, sizeof(kmc_i128) * n2);
+  acc->origin_step = acc->last_step = v->step;
+  acc->max_size = S;
+  cf_host_look(n, S, label, cnt, acc, t->n_s);
+  return KMC_OK;
+}
+
+int kmc_host_cf_update(const kmc_params* p, const kmc_state_view* v, const kmc_cf_view* view, kmc_cf_out* acc,
+                       const kmc_cf_tables* t) {
+  if (!p || !v || !v->a_int || !cf_view_ok(view) || !acc || !cf_tables_ok(t) || acc->max_size < CF_MIN_SIZE ||
+      acc->max_size > CF_MAX_SIZE) {
+    g_host_err = "growth: params, state, the view's three arrays, a begun acc and every table are needed";
+    return KMC_ERR_ARG;
+  }
+  const int na = p->n_a, n = p->n_a + p->n_b, S = (int)acc->max_size;
+  if (v->step == acc->last_step) {  // the state of the last look: nothing to file
+    acc->n_updates += 1;
+    return KMC_OK;
+  }
+  // the current bonds E1 and the kept bonds K, with the bond counters of this update
+  std::vector<CfEdge> e1, kept;
+  int64_t ev[4] = {0, 0, 0, 0};  // formed_rl, formed_cis, broken_rl, broken_cis
+  for (int i = 0; i < na; ++i) {  // checked first: a failed call leaves the recorder as it was
+    int32_t lig, cis;
+    if (!cf_host_cur(p, v, i, &lig, &cis)) {
+      g_host_err = "growth: a receptor's bond link leaves its range";
+      return KMC_ERR_STATE;
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    const int32_t l = view->prev_label[i];
+    if (l < 1 || l > i + 1 || view->prev_label[l - 1] != l) {
+      g_host_err = "growth: the recorder's label of protein " + std::to_string(i + 1) + " is not its class' smallest member";
+      return KMC_ERR_STATE;
+    }
+  }
+  for (int i = 0; i < na; ++i) {
+    int32_t lig, cis;
+    cf_host_cur(p, v, i, &lig, &cis);
+    const int32_t old_lig = view->rl_lig[i], old_cis = view->cis_with[i], me = i + 1;
+    if (lig) e1.push_back(CfEdge(i, lig - 1));
+    if (cis && me < cis) e1.push_back(CfEdge(i, cis - 1));
+    if (lig != old_lig) {
+      ev[0] += lig != 0;
+      ev[2] += old_lig != 0;
+    } else if (lig) {
+      kept.push_back(CfEdge(i, lig - 1));
+    }
+    if (cis != old_cis) {
+      ev[1] += cis != 0 && me < cis;
+      ev[3] += old_cis != 0 && me < old_cis;
+    } else if (cis && me < cis) {
+      kept.push_back(CfEdge(i, cis - 1));
+    }
+    view->rl_lig[i] = lig;
+    view->cis_with[i] = cis;
+  }
+  std::vector<int32_t> cur, core, prev((size_t)n);
+  std::vector<uint64_t> cur_cnt, core_cnt, prev_cnt((size_t)n, 0);
+  cf_walk(n, na, e1, cur, cur_cnt);
+  cf_walk(n, na, kept, core, core_cnt);
+  for (int i = 0; i < n; ++i) {
+    prev[(size_t)i] = view->prev_label[i] - 1;
+    prev_cnt[(size_t)prev[(size_t)i]] += i < na ? 1ull : 1ull << 32;
+  }
+  // cores per previous and per current cluster
+  std::vector<int32_t> k0((size_t)n, 0), k1((size_t)n, 0);
+  int64_t n_cores = 0;
+  for (int i = 0; i < n; ++i)
+    if (core[(size_t)i] == i) {
+      k0[(size_t)prev[(size_t)i]] += 1;
+      k1[(size_t)cur[(size_t)i]] += 1;
+      n_cores += 1;
+    }
+  for (int i = 0; i < n; ++i) {
+    if (core[(size_t)i] != i) continue;
+    const int32_t pl = prev[(size_t)i], cl = cur[(size_t)i];
+    kmcc::Filing f = kmcc::file(i, core_cnt[(size_t)i], pl, prev_cnt[(size_t)pl], k0[(size_t)pl], S);
+    if (f.pieces >= 0) t->frag_pieces[f.pieces] += 1;
+    if (f.whole >= 0) t->frag_parent[f.whole] += 1;
+    if (f.pair >= 0) t->frag[f.pair] += 1;
+    if (f.kinds >= 0) t->frag_kind[f.kinds] += 1;
+    f = kmcc::file(i, core_cnt[(size_t)i], cl, cur_cnt[(size_t)cl], k1[(size_t)cl], S);
+    if (f.pieces >= 0) t->merge_pieces[f.pieces] += 1;
+    if (f.whole >= 0) t->merge_product[f.whole] += 1;
+    if (f.pair >= 0) t->merge[f.pair] += 1;
+    if (f.kinds >= 0) t->merge_kind[f.kinds] += 1;
+  }
+  // exposures of the interval that ended, from the previous look's n_s
+  typedef __int128 i128;
+  const int64_t dt = v->step - acc->last_step;
+  for (int x = 1; x <= S; ++x) {
+    const int64_t nx = t->n_s[x];
+    t->expo[x] += dt * nx;
+    for (int y = x; y <= S; ++y) {
+      kmc_i128* w = &t->expo2[(size_t)x * (S + 1) + y];
+      i128 e = ((i128)w->hi << 64) + (i128)w->lo;
+      e += y == x ? (i128)dt * nx * (nx - 1) / 2 : (i128)dt * nx * t->n_s[y];
+      w->lo = (uint64_t)(unsigned __int128)e;
+      w->hi = (int64_t)(e >> 64);
+    }
+  }
+  const int64_t clusters_prev = acc->n_clusters;
+  for (int i = 0; i < n; ++i) view->prev_label[i] = cur[(size_t)i] + 1;
+  cf_host_look(n, S, cur, cur_cnt, acc, t->n_s);
+  acc->formed_rl += ev[0];
+  acc->formed_cis += ev[1];
+  acc->broken_rl += ev[2];
+  acc->broken_cis += ev[3];
+  acc->n_cores = n_cores;
+  acc->cycles_closed += ev[0] + ev[1] - (n_cores - acc->n_clusters);
+  acc->cycles_opened += ev[2] + ev[3] - (n_cores - clusters_prev);
+  acc->last_step = v->step;
+  acc->n_updates += 1;
+  return KMC_OK;
+}
+
+int kmc_host_cf_sample(const kmc_params* p, const kmc_cf_view* view, const kmc_cf_out* acc, const kmc_cf_tables* t,
+                       kmc_cf_out* out, const kmc_cf_tables* to) {
+  if (!p || !cf_view_ok(view) || !acc || !cf_tables_ok(t) || !out || acc->max_size < CF_MIN_SIZE ||
+      acc->max_size > CF_MAX_SIZE) {
+    g_host_err = "growth sample: params, the view's three arrays, a begun acc, every table and out are needed";
+    return KMC_ERR_ARG;
+  }
+  const kmc_cf_out a = *acc;  // (out may be acc itself)
+  *out = a;
+  if (!to) return KMC_OK;
+  const size_t n1 = (size_t)a.max_size + 1, n2 = n1 * n1;
+  auto copy = [](int64_t* dst, const int64_t* src, size_t n) {
+    if (dst && dst != src) std::copy(src, src + n, dst);
+  };
+  copy(to->merge, t->merge, n2);
+  copy(to->frag, t->frag, n2);
+  copy(to->merge_kind, t->merge_kind, CF_KINDS * CF_KINDS);
+  copy(to->frag_kind, t->frag_kind, CF_KINDS * CF_KINDS);
+  copy(to->merge_pieces, t->merge_pieces, CF_PIECES);
+  copy(to->frag_pieces, t->frag_pieces, CF_PIECES);
+  copy(to->merge_product, t->merge_product, n1);
+  copy(to->frag_parent, t->frag_parent, n1);
+  copy(to->n_s, t->n_s, n1);
+  copy(to->expo, t->expo, n1);
+  if (to->expo2 && to->expo2 != t->expo2) std::copy(t->expo2, t->expo2 + n2, to->expo2);
   return KMC_OK;
 }
 

@@ -59,6 +59,16 @@
 //                                  occ_free_site n_rl_censored_alive n_cis_censored_alive
 //                            and per non-empty bin of the histogram since that origin
 //                              life step row bin count
+//           [--cf EVERY SMAX FILE]  cluster growth kinetics (kmc_cf_*, sizes clamped at SMAX): the
+//                            recorder begins where the process starts or resumes (a new origin,
+//                            as --kin's); an update after every piece of at most EVERY steps;
+//                            every out_interval FILE gets, since that origin,
+//                              cf step origin n_updates max_size formed_rl formed_cis broken_rl
+//                                 broken_cis n_cores n_clusters cycles_closed cycles_opened max_cluster
+//                              merge step a b count          (non-zero bins, a <= b)
+//                              frag step a b count
+//                              pieces step k mergers fragmentations       (non-zero rows)
+//                              sizes step s n_s expo merge_product frag_parent (non-zero rows)
 #include <sys/stat.h>
 
 #include <cstdio>
@@ -111,12 +121,13 @@ int main(int argc, char** argv) {
   kmc_params p;
   kmc_params_default(&p);
   int device = 0;
-  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path, psi_path, kin_path;
+  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path, psi_path, kin_path, cf_path;
   int psi_which = -1, psi_fold = 0, psi_nbins = 0;
   double psi_rcut = 0.0;
   int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0, geom_max = 0, sq_hmax = 0, sq_kmax = 0;
   double rdf_rmax = 0.0, dyn_rmax = 0.0;
-  int64_t dyn_every = 0, kin_every = 0;
+  int64_t dyn_every = 0, kin_every = 0, cf_every = 0;
+  int cf_smax = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -198,6 +209,15 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--cf") {
+      cf_every = atoll(next().c_str());
+      cf_smax = atoi(next().c_str());
+      cf_path = next();
+      if (cf_every < 1 || cf_smax < 2 || cf_smax > KMC_CF_MAX_SIZE) {
+        fprintf(stderr, "kmc_run: bad --cf %lld %d\n", (long long)cf_every, cf_smax);
+        return 2;
+      }
+    }
     else if (a == "--set") {
       std::string kv = next();
       size_t eq = kv.find('=');
@@ -238,6 +258,7 @@ int main(int argc, char** argv) {
     if (!sq_path.empty()) truncate(sq_path.c_str());
     if (!psi_path.empty()) truncate(psi_path.c_str());
     if (!kin_path.empty()) truncate(kin_path.c_str());
+    if (!cf_path.empty()) truncate(cf_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
   }
@@ -265,28 +286,35 @@ int main(int argc, char** argv) {
     rc = kmc_kin_begin(s);
     if (rc) return die(s, rc, "kinetics begin");
   }
+  if (!cf_path.empty()) {
+    rc = kmc_cf_begin(s, cf_smax);
+    if (rc) return die(s, rc, "growth begin");
+  }
   int64_t step = kmc_current_step(s);
   while (step < p.simu_step) {
     int64_t next_out = (step / p.out_interval + 1) * p.out_interval;
     int64_t end = next_out < p.simu_step ? next_out : p.simu_step;
     int64_t n = end - step;
     obs.resize((size_t)n);
-    if (dyn_path.empty() && kin_path.empty()) {
+    if (dyn_path.empty() && kin_path.empty() && cf_path.empty()) {
       rc = kmc_step(s, n, obs.data());
       if (rc) return die(s, rc, "kmc_step");
     } else {
       // pieces end where the tracker's or the recorder's next update is due (each counts from the interval's start)
       const int64_t far = n + 1;
       int64_t dyn_left = dyn_path.empty() ? far : dyn_every, kin_left = kin_path.empty() ? far : kin_every;
+      int64_t cf_left = cf_path.empty() ? far : cf_every;
       for (int64_t done = 0; done < n;) {
         int64_t m = n - done;
         if (dyn_left < m) m = dyn_left;
         if (kin_left < m) m = kin_left;
+        if (cf_left < m) m = cf_left;
         rc = kmc_step(s, m, obs.data() + done);
         if (rc) return die(s, rc, "kmc_step");
         done += m;
         dyn_left -= m;
         kin_left -= m;
+        cf_left -= m;
         if (!dyn_path.empty() && (dyn_left == 0 || done == n)) {
           rc = kmc_track_update(s, nullptr);
           if (rc) return die(s, rc, "track update");
@@ -296,6 +324,11 @@ int main(int argc, char** argv) {
           rc = kmc_kin_update(s, nullptr);
           if (rc) return die(s, rc, "kinetics update");
           kin_left = kin_every;
+        }
+        if (!cf_path.empty() && (cf_left == 0 || done == n)) {
+          rc = kmc_cf_update(s, nullptr);
+          if (rc) return die(s, rc, "growth update");
+          cf_left = cf_every;
         }
       }
     }
@@ -419,6 +452,48 @@ int main(int argc, char** argv) {
           for (int b = 0; b < KMC_KIN_BINS; ++b)
             if (life[(size_t)r * KMC_KIN_BINS + b])
               fprintf(f, "life %lld %d %d %lld\n", (long long)step, r, b, (long long)life[(size_t)r * KMC_KIN_BINS + b]);
+        fclose(f);
+      }
+      if (!cf_path.empty()) {
+        const size_t n1 = (size_t)cf_smax + 1;
+        std::vector<int64_t> merge(n1 * n1), frag(n1 * n1), mp(KMC_CF_PIECES), fp(KMC_CF_PIECES), prod(n1), par(n1),
+            ns(n1), expo(n1);
+        kmc_cf_tables t;
+        std::memset(&t, 0, sizeof t);
+        t.merge = merge.data();
+        t.frag = frag.data();
+        t.merge_pieces = mp.data();
+        t.frag_pieces = fp.data();
+        t.merge_product = prod.data();
+        t.frag_parent = par.data();
+        t.n_s = ns.data();
+        t.expo = expo.data();
+        kmc_cf_out k;
+        rc = kmc_cf_sample(s, &k, &t);
+        if (rc) return die(s, rc, "growth sample");
+        f = fopen(cf_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, cf_path.c_str());
+        const int64_t fields[] = {k.origin_step, k.n_updates, k.max_size, k.formed_rl, k.formed_cis, k.broken_rl,
+                                  k.broken_cis, k.n_cores, k.n_clusters, k.cycles_closed, k.cycles_opened,
+                                  k.max_cluster};
+        fprintf(f, "cf %lld", (long long)step);
+        for (int64_t x : fields) fprintf(f, " %lld", (long long)x);
+        fputc('\n', f);
+        for (int pass = 0; pass < 2; ++pass) {
+          const std::vector<int64_t>& tab = pass ? frag : merge;
+          for (size_t a = 1; a < n1; ++a)
+            for (size_t b = a; b < n1; ++b)
+              if (tab[a * n1 + b])
+                fprintf(f, "%s %lld %zu %zu %lld\n", pass ? "frag" : "merge", (long long)step, a, b,
+                        (long long)tab[a * n1 + b]);
+        }
+        for (int q = 0; q < KMC_CF_PIECES; ++q)
+          if (mp[(size_t)q] || fp[(size_t)q])
+            fprintf(f, "pieces %lld %d %lld %lld\n", (long long)step, q, (long long)mp[(size_t)q], (long long)fp[(size_t)q]);
+        for (size_t q = 1; q < n1; ++q)
+          if (ns[q] || expo[q] || prod[q] || par[q])
+            fprintf(f, "sizes %lld %zu %lld %lld %lld %lld\n", (long long)step, q, (long long)ns[q], (long long)expo[q],
+                    (long long)prod[q], (long long)par[q]);
         fclose(f);
       }
     }

@@ -113,6 +113,18 @@ def load_library(path: Optional[str] = None):
     L.kmc_host_kin_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.KinView), P(capi.KinOut), C.c_void_p]
     L.kmc_host_kin_sample.argtypes = [P(capi.Params), P(capi.KinView), P(capi.KinOut), C.c_void_p, P(capi.KinOut),
                                       C.c_void_p]
+    L.kmc_cf_begin.argtypes = [C.c_void_p, C.c_int32]
+    L.kmc_cf_update.argtypes = [C.c_void_p, P(capi.CfOut)]
+    L.kmc_cf_sample.argtypes = [C.c_void_p, P(capi.CfOut), P(capi.CfTablesView)]
+    L.kmc_cf_get.argtypes = [C.c_void_p, P(capi.CfView)]
+    L.kmc_cf_put.argtypes = [C.c_void_p, P(capi.CfView), C.c_int64]
+    L.kmc_cf_end.argtypes = [C.c_void_p]
+    L.kmc_host_cf_begin.argtypes = [P(capi.Params), P(capi.StateView), C.c_int32, P(capi.CfView), P(capi.CfOut),
+                                    P(capi.CfTablesView)]
+    L.kmc_host_cf_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.CfView), P(capi.CfOut),
+                                     P(capi.CfTablesView)]
+    L.kmc_host_cf_sample.argtypes = [P(capi.Params), P(capi.CfView), P(capi.CfOut), P(capi.CfTablesView),
+                                     P(capi.CfOut), P(capi.CfTablesView)]
     L.kmc_unwrap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.kmc_cluster_geometry.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, P(capi.Geom)]
     L.kmc_cluster_list.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, P(C.c_int64)]
@@ -306,6 +318,40 @@ class HostKinetics:
                                                        C.byref(self.acc), self.hist.ctypes.data, C.byref(out),
                                                        hist.ctypes.data))
         return out, hist
+
+
+class HostCoag:
+    """The cluster growth recorder on host states, sequentially (kmc_host_cf_*): Simulation.cf_*'s counterpart
+    without a device.  The recorder begins at hs; update(hs) advances it to a later state of the trajectory.
+    arrays (capi.CfArrays) is what Simulation.cf_put takes."""
+
+    def __init__(self, params: capi.Params, hs: capi.HostState, max_size: int):
+        self.params = params
+        self.arrays = capi.CfArrays(params.n_a, params.n_b)
+        self.acc = capi.CfOut()
+        self.tables = capi.CfTables(max_size) if 2 <= max_size <= capi.CF_MAX_SIZE else capi.CfTables(2)
+        v = hs.view()
+        _host_check(load_library().kmc_host_cf_begin(C.byref(params), C.byref(v), int(max_size),
+                                                     C.byref(self.arrays.view()), C.byref(self.acc),
+                                                     C.byref(self.tables.view())))
+
+    def update(self, hs: capi.HostState) -> capi.CfOut:
+        """Advance the recorder to hs (kmc_host_cf_update); returns the counters as of this update."""
+        v = hs.view()
+        _host_check(load_library().kmc_host_cf_update(C.byref(self.params), C.byref(v), C.byref(self.arrays.view()),
+                                                      C.byref(self.acc), C.byref(self.tables.view())))
+        out = capi.CfOut()
+        C.memmove(C.byref(out), C.byref(self.acc), C.sizeof(out))
+        return out
+
+    def sample(self):
+        """(capi.CfOut, capi.CfTables) as of the last look — kmc_host_cf_sample; the tables are a copy."""
+        out = capi.CfOut()
+        t = capi.CfTables(self.tables.max_size)
+        _host_check(load_library().kmc_host_cf_sample(C.byref(self.params), C.byref(self.arrays.view()),
+                                                      C.byref(self.acc), C.byref(self.tables.view()), C.byref(out),
+                                                      C.byref(t.view())))
+        return out, t
 
 
 def host_dd_check(gid: np.ndarray, own: np.ndarray) -> int:
@@ -542,7 +588,7 @@ class Simulation:
 
     @property
     def analysis_ms(self) -> float:
-        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / unwrap /
+        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / unwrap /
         cluster_* / structure_factor / bond_order / bond_order_corr call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
@@ -639,6 +685,63 @@ class Simulation:
             self.step(n, recs[done:done + n])
             done += n
             out = self.kin_update()
+        return recs, out
+
+
+    # ---- cluster growth kinetics since a begin (kmc_coag.hip)
+    def cf_begin(self, max_size: int = 16) -> None:
+        """Start the cluster growth recorder at the current state; sizes from max_size on share the last index."""
+        self._check(load_library().kmc_cf_begin(self._h, int(max_size)))
+
+    def cf_update(self) -> capi.CfOut:
+        """File the mergers and fragmentations since the last look; call it between step() calls — after every
+        step for events exact up to simultaneous ones (every k steps: stroboscopic ones)."""
+        out = capi.CfOut()
+        self._check(load_library().kmc_cf_update(self._h, C.byref(out)))
+        return out
+
+    def cf_sample(self):
+        """(capi.CfOut, capi.CfTables) of the recorder as of the last look — kmc_cf_sample; analysis.coag_kernel,
+        analysis.frag_kernel and analysis.growth_modes post-process them."""
+        out = capi.CfOut()
+        self._check(load_library().kmc_cf_sample(self._h, C.byref(out), None))
+        t = capi.CfTables(int(out.max_size))
+        self._check(load_library().kmc_cf_sample(self._h, C.byref(out), C.byref(t.view())))
+        return out, t
+
+    def cf_arrays(self) -> capi.CfArrays:
+        """The recorder's per-protein state by reference index (kmc_cf_get): the stored bonds and the labels of
+        the last look.  With the step of that look it is what cf_put takes."""
+        a = capi.CfArrays(self.params.n_a, self.params.n_b)
+        self._check(load_library().kmc_cf_get(self._h, C.byref(a.view())))
+        return a
+
+    def cf_put(self, arrays: capi.CfArrays, last_step: int) -> None:
+        """Load a recorder state saved by cf_arrays or built by HostCoag, as of step last_step (kmc_cf_put): the
+        tables and counters start again at zero."""
+        a = capi.CfArrays(self.params.n_a, self.params.n_b)
+        for name in a.NAMES:
+            src = np.ascontiguousarray(getattr(arrays, name), dtype=np.int32)
+            if src.shape != getattr(a, name).shape:
+                raise ValueError("cf_put: " + name + " has the wrong length")
+            setattr(a, name, src)
+        self._check(load_library().kmc_cf_put(self._h, C.byref(a.view()), int(last_step)))
+
+    def cf_end(self) -> None:
+        self._check(load_library().kmc_cf_end(self._h))
+
+    def run_coag(self, nsteps: int, every: int = 1):
+        """Advance nsteps steps in pieces of at most `every` steps with a cf_update after each piece.  The
+        recorder must have been begun.  Returns (records[nsteps], the last update's capi.CfOut or None)."""
+        if nsteps < 0 or every < 1:
+            raise ValueError("run_coag: nsteps >= 0, every >= 1")
+        recs = np.zeros(nsteps, dtype=capi.OBS_DTYPE)
+        done, out = 0, None
+        while done < nsteps:
+            n = min(every, nsteps - done)
+            self.step(n, recs[done:done + n])
+            done += n
+            out = self.cf_update()
         return recs, out
 
     @property
