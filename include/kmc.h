@@ -103,7 +103,19 @@ typedef struct kmc_sim kmc_sim;
 /* Reference defaults (main.cpp:39-99); out_interval 5000, seed 1, replica 0. */
 void kmc_params_default(kmc_params* p);
 
-/* Create a simulation on HIP device `device` (-1 = current). */
+/* Create a simulation on HIP device `device` (-1 = current).
+ *
+ * Parameters outside this envelope are refused with KMC_ERR_ARG, before any
+ * device is touched (inside it the engine is verified bit for bit against the
+ * CPU restatement of the reference, which applies the same rule):
+ *   - n_a >= 0, n_b >= 0, 1 <= n_a + n_b <= 2^24 (one species may be absent);
+ *   - every double field finite: NaN and +-inf are refused everywhere;
+ *   - box_x, box_y, box_z, time_step, pai, ra_radius, rb_radius,
+ *     bond_dist_cutoff, cis_dist_cutoff, bond_thetapd_cutoff,
+ *     bond_thetaot_cutoff, cis_thetaot_cutoff > 0;
+ *   - ra_radius <= 20, rb_radius <= 30, bond_dist_cutoff <= 18,
+ *     cis_dist_cutoff <= 15 (the reference's values, accepted exactly);
+ *   - every D, rot_D and rate >= 0 (0 switches the move or reaction off). */
 int kmc_create(const kmc_params* p, int device, kmc_sim** out);
 int kmc_destroy(kmc_sim* s);
 const char* kmc_last_error(const kmc_sim* s);
@@ -855,8 +867,12 @@ int kmc_host_write_parameter_log(const kmc_params* p, const char* path);
 int kmc_host_append_gro(const kmc_params* p, const kmc_state_view* v, const char* path);
 int kmc_host_append_cluster_log(const kmc_params* p, int64_t step, const int32_t* row_len, const int32_t* members,
                                 const char* path);
-/* bond-link consistency + rigid-body extent bound; KMC_OK or an error code */
+/* the parameter envelope (kmc_create above), then bond-link consistency +
+ * rigid-body extent bound; KMC_OK or an error code */
 int kmc_host_validate(const kmc_params* p, const kmc_state_view* v);
+/* the parameter envelope alone, exactly what kmc_create accepts: KMC_OK or
+ * KMC_ERR_ARG (kmc_host_last_error names the field) */
+int kmc_host_check_params(const kmc_params* p);
 /* the arguments kmc_dd_set_state checks first: gid[0..n) increasing and in
  * [0, INT32_MAX), own[i] 0 or 1; KMC_OK or KMC_ERR_ARG */
 int kmc_host_dd_check(int32_t n, const int32_t* gid, const uint8_t* own);

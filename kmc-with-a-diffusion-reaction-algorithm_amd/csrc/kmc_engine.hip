@@ -12,6 +12,7 @@
 
 #include "../../include/kmc.h"
 #include "kmc_host.h"
+#include "kmc_params_check.h"
 #include "kmc_kernels.hip"
 #include "kmc_analysis.hip"
 #include "kmc_geometry.hip"
@@ -352,8 +353,15 @@ static int choose_tile(double rho) {
 int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
   if (!p || !out) return KMC_ERR_ARG;
   *out = nullptr;
-  if (p->n_a < 0 || p->n_b < 0 || p->n_a + p->n_b <= 0 || (int64_t)p->n_a + p->n_b > (1 << 24))
-    return KMC_ERR_ARG;
+  // The parameter envelope (kmc_params_check.h), checked
+  // before any device is touched.  The neighbour search's cell size and float
+  // prefilter radii are derived for the reference's radii and cutoffs
+  // (DESIGN.md §cell list): those four are refused above the reference's
+  // values, and smaller positive values only shrink every reach.  Every double
+  // must be finite (a NaN passes no comparison there); box, time step, pai,
+  // radii and cutoffs positive; D, rot_D and rates not negative.  A species
+  // may be absent (n_a == 0 or n_b == 0): every launch sized by it is skipped.
+  if (kmcp::check_params(p)) return KMC_ERR_ARG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return KMC_ERR_NODEVICE;
   kmc_sim* s = new kmc_sim();
@@ -375,13 +383,6 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
   if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
     kmc_destroy(s);
     return KMC_ERR_HIP;
-  }
-  // the neighbour search's cell size and float prefilter radii are derived
-  // for the reference's radii and cutoffs (DESIGN.md §cell list); smaller
-  // values only shrink every reach
-  if (p->ra_radius > 20.0 || p->rb_radius > 30.0 || p->bond_dist_cutoff > 18.0 || p->cis_dist_cutoff > 15.0) {
-    kmc_destroy(s);
-    return KMC_ERR_ARG;
   }
   KParams& K = s->K;
   const int NA = p->n_a, NB = p->n_b, N = NA + NB;
@@ -1549,6 +1550,7 @@ int kmc_get_clusters(kmc_sim* s, int32_t* row_len, int32_t* members) {
         if (((uint8_t)(e >> ULOG_SHIFT) == U_COMPLEX) == (pass == 1))
           kind[e & ((1 << ULOG_SHIFT) - 1)] = (uint8_t)(e >> ULOG_SHIFT);
   }
+  if (NB == 0) return KMC_OK;  // no ligand, no row (and no zero-byte copy into an empty vector)
   HIPCHK(s, hipMemcpy(off.data(), s->d.cx_off, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
   HIPCHK(s, hipMemcpy(size.data(), s->d.cx_size, sizeof(int32_t) * NB, hipMemcpyDeviceToHost));
   std::vector<int32_t> shuf(s->d.mcap);

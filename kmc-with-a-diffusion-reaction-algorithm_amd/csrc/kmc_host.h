@@ -24,6 +24,7 @@ int kmc_host_init_random(const kmc_params* p, kmc_state_view* v);
 int kmc_host_save_state(const kmc_params* p, const kmc_state_view* v, const char* path);
 int kmc_host_load_state(const kmc_params* p, const char* path, kmc_state_view* v);
 int kmc_host_validate(const kmc_params* p, const kmc_state_view* v);
+int kmc_host_check_params(const kmc_params* p);
 int kmc_host_dd_check(int32_t n, const int32_t* gid, const uint8_t* own);
 int kmc_host_math(int op, const double* x, const double* y, double* out, int64_t n);
 }

@@ -25,6 +25,7 @@
 #include "kmc_host.h"
 #include "kmc_kinetics.h"
 #include "kmc_math.h"
+#include "kmc_params_check.h"
 #include "kmc_philox.h"
 #include "kmc_state_hash.h"
 #include "kmc_structure.h"
@@ -155,6 +156,10 @@ int write_cpt(const kmc_params* p, const kmc_state_view* v, const char* path, st
 // bond-link consistency (what every reference step maintains) and the
 // extent bound of the 130 Å cell list (kmc_kernels.hip)
 int validate(const kmc_params* p, const kmc_state_view* v, std::string* err) {
+  if (const char* bad = kmcp::check_params(p)) {
+    *err = std::string("parameter outside the accepted envelope: ") + bad;
+    return KMC_ERR_ARG;
+  }
   const int na = p->n_a, nb = p->n_b, n = na + nb;
   char msg[256];
   for (int i = 0; i < na; ++i) {
@@ -667,6 +672,12 @@ int kmc_host_load_state(const kmc_params* p, const char* path, kmc_state_view* v
   return kmch_host::load_state(p, path, v, &g_host_err);
 }
 int kmc_host_validate(const kmc_params* p, const kmc_state_view* v) { return kmch_host::validate(p, v, &g_host_err); }
+int kmc_host_check_params(const kmc_params* p) {
+  const char* bad = kmcp::check_params(p);
+  if (!bad) return KMC_OK;
+  g_host_err = std::string("parameter outside the accepted envelope: ") + bad;
+  return KMC_ERR_ARG;
+}
 int kmc_host_dd_check(int32_t n, const int32_t* gid, const uint8_t* own) {
   return kmch_host::dd_check(n, gid, own, &g_host_err);
 }

@@ -67,6 +67,7 @@ def load_library(path: Optional[str] = None):
     L.kmc_host_write_cpt.argtypes = [P(capi.Params), P(capi.StateView), C.c_char_p]
     L.kmc_host_init_random.argtypes = [P(capi.Params), P(capi.StateView)]
     L.kmc_host_validate.argtypes = [P(capi.Params), P(capi.StateView)]
+    L.kmc_host_check_params.argtypes = [P(capi.Params)]
     L.kmc_host_dd_check.argtypes = [C.c_int32, C.c_void_p, C.c_void_p]
     L.kmc_host_save_state.argtypes = [P(capi.Params), P(capi.StateView), C.c_char_p]
     L.kmc_host_load_state.argtypes = [P(capi.Params), C.c_char_p, P(capi.StateView)]
@@ -194,6 +195,11 @@ def host_load_state(params: capi.Params, path: str) -> capi.HostState:
 def host_validate(params: capi.Params, hs: capi.HostState) -> int:
     v = hs.view()
     return int(load_library().kmc_host_validate(C.byref(params), C.byref(v)))
+
+
+def host_check_params(params: capi.Params) -> int:
+    """The parameter envelope kmc_create accepts (include/kmc.h): KMC_OK or KMC_ERR_ARG."""
+    return int(load_library().kmc_host_check_params(C.byref(params)))
 
 
 def host_census(params: capi.Params, hs: capi.HostState, max_r: int, max_l: int):
@@ -484,10 +490,11 @@ class Simulation:
 
     def clusters(self):
         """BFS member rows of the last step: (row_len[n_b], members) — kmc_get_clusters."""
-        row = np.zeros(self.params.n_b, dtype=np.int32)
-        mem = np.zeros(self.params.n_a + self.params.n_b, dtype=np.int32)
+        n_b = self.params.n_b
+        row = np.zeros(max(1, n_b), dtype=np.int32)  # (never an empty buffer: the library refuses a null pointer)
+        mem = np.zeros(self.params.n_a + n_b, dtype=np.int32)
         self._check(load_library().kmc_get_clusters(self._h, row.ctypes.data, mem.ctypes.data))
-        return row, mem[: int(row.sum())]
+        return row[:n_b], mem[: int(row[:n_b].sum())]
 
     # ---- structure analysis of the current state (kmc_analysis.hip; works before any step)
     def components(self) -> np.ndarray:

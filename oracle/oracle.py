@@ -292,6 +292,14 @@ REF_GLOBALS = {
     "bond_rot_D": "bond_rot_D",
     "ass_rate": "Ass_Rate",
     "diss_rate": "Diss_Rate",
+    "ra_radius": "RB_A_radius",
+    "rb_radius": "RB_B_radius",
+    "pai": "pai",
+    "bond_dist_cutoff": "bond_dist_cutoff",
+    "bond_thetapd_cutoff": "bond_thetapd_cutoff",
+    "bond_thetaot_cutoff": "bond_thetaot_cutoff",
+    "cis_thetaot_cutoff": "cis_thetaot_cutoff",
+    "cis_dist_cutoff": "cis_dist_cutoff",
 }
 
 

@@ -12,8 +12,9 @@
 //  2. sin, cos, sincos, atan2, acos resolve to kmc_math.h instead of glibc
 //     (removes the -O2 sincos-fusion ulp drift, SURVEY.md §0.2 fact 5, and
 //     makes the arithmetic identical to the oracle and the GPU engine).
-//  3. Runtime-settable reference globals (simu_step, box, rates — all plain
-//     globals at main.cpp:39-99) are overridden from $KMC_REF_SET before
+//  3. Runtime-settable reference globals (simu_step, box, time step, mobilities,
+//     rates, radii, pai, distance and angle cutoffs — all plain globals at
+//     main.cpp:39-99) are overridden from $KMC_REF_SET before
 //     main() runs.  The #define'd sizes (150 receptors + 50 ligands,
 //     main.cpp:47-69) cannot change without editing the source, so golden
 //     runs use that size and vary box, rates and step count instead.
@@ -49,6 +50,8 @@ extern double time_step, cell_range_x, cell_range_y, cell_range_z;
 extern double RB_A_D, RB_A_rot_D, RB_B_D, RB_B_rot_D;
 extern double mono_cis_Ass_Rate, mono_cis_Diss_Rate, cis_D, cis_rot_D, cis_Ass_Rate, cis_Diss_Rate;
 extern double bond_D, bond_rot_D, Ass_Rate, Diss_Rate;
+extern double RB_A_radius, RB_B_radius, pai, bond_dist_cutoff, bond_thetapd_cutoff, bond_thetaot_cutoff,
+    cis_thetaot_cutoff, cis_dist_cutoff;
 extern double R_x[REF_N + 1][5][5], R_y[REF_N + 1][5][5], R_z[REF_N + 1][5][5];
 extern int protein_status[REF_N + 1][5];
 extern int res_nei[REF_N + 1][7];
@@ -88,6 +91,14 @@ void set_global(const std::string& k, const std::string& v) {
   else if (k == "bond_rot_D") bond_rot_D = d;
   else if (k == "Ass_Rate") Ass_Rate = d;
   else if (k == "Diss_Rate") Diss_Rate = d;
+  else if (k == "RB_A_radius") RB_A_radius = d;
+  else if (k == "RB_B_radius") RB_B_radius = d;
+  else if (k == "pai") pai = d;
+  else if (k == "bond_dist_cutoff") bond_dist_cutoff = d;
+  else if (k == "bond_thetapd_cutoff") bond_thetapd_cutoff = d;
+  else if (k == "bond_thetaot_cutoff") bond_thetaot_cutoff = d;
+  else if (k == "cis_thetaot_cutoff") cis_thetaot_cutoff = d;
+  else if (k == "cis_dist_cutoff") cis_dist_cutoff = d;
   else {
     fprintf(stderr, "ref_interpose: unknown global %s\n", k.c_str());
     exit(2);

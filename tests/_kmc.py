@@ -52,3 +52,88 @@ def state_from_dump(raw: np.ndarray, n_a: int, n_b: int) -> "capi.HostState":
 
 def params(**kw):
     return capi.default_params(**kw)
+
+
+def scenario_params(name, **kw):
+    """kmc_params of a golden scenario (tests/golden/scenarios.json) with overrides."""
+    sc = scenarios()[name]
+    return capi.default_params(**{**dict(n_a=sc["n_a"], n_b=sc["n_b"]), **sc["params"], **kw})
+
+
+def golden_state(name, step):
+    """(state the reference dumped at `step` of scenario `name`, its trace row index)."""
+    g = golden(name)
+    sc = scenarios()[name]
+    st = state_from_dump(g[f"state_{step}"], sc["n_a"], sc["n_b"])
+    return st, int(np.flatnonzero(g["step"] == step)[0])
+
+
+# what a window must exercise to count as covering the step's code paths
+# (Oracle.stats keys; multi-ligand alignment and its repeat need more ligands
+# per complex than 150 + 50 proteins form at these densities)
+COVERAGE = ("free_a", "dimer", "free_b", "complex", "laydown", "reject", "rl", "mono", "cis", "rld", "md",
+            "snap_bond", "snap_cis")
+
+# the parameter set that makes outliers without a debug knob: a 400 ns step
+# moves a ligand up to amp_b = 2 sqrt(rb_D ts / 6) = 44 Å and a receptor up to
+# 16 Å a step and axis (default D); every rate x time_step stays below 1
+STRIDE = dict(time_step=400.0, ass_rate=0.002, mono_cis_ass_rate=0.001, cis_ass_rate=0.002,
+              diss_rate=0.00002, mono_cis_diss_rate=0.0002, cis_diss_rate=0.00005)
+
+
+def stats_delta(before, after):
+    return {k: after[k] - before[k] for k in after}
+
+
+def run_pair(p, nbmode=O.NB_BRUTE, init_state=None):
+    """(oracle, GPU simulation) holding the same state: the oracle's keyed placement or init_state."""
+    o = O.Oracle(p, rng_mode=O.RNG_KEYED, nbmode=nbmode)
+    if init_state is None:
+        o.init_placement()
+        st = o.get_state()
+    else:
+        st = init_state
+        o.set_state(st)
+    sim = engine.Simulation(p)
+    sim.set_state(st)
+    assert sim.get_state().equal(st)
+    return o, sim
+
+
+def compare_stepwise(p, steps, nbmode=O.NB_BRUTE, init_state=None, oracle_run=None):
+    """Step the GPU engine one step at a time against the oracle: every
+    bond.dat record and full-state hash equal, else fail with the first
+    differing step, the records, counters and the first differing entries.
+    oracle_run = (obs, hashes) of a trajectory computed earlier from the same
+    state (shared between tests); returns the oracle (None with oracle_run)."""
+    import pytest
+
+    if oracle_run is None:
+        o, sim = run_pair(p, nbmode, init_state)
+        obs_o, hashes = o.step(steps)
+    else:
+        o = None
+        obs_o, hashes = oracle_run
+        assert len(obs_o) >= steps and init_state is not None
+        sim = engine.Simulation(p)
+        sim.set_state(init_state)
+        assert sim.get_state().equal(init_state)
+    for s in range(steps):
+        rec = sim.step(1)
+        hs = sim.get_state()
+        h = engine.state_hash(p, hs)
+        if h != int(hashes[s]) or rec[0] != obs_o[s]:
+            sim.close()
+            o2 = O.Oracle(p, rng_mode=O.RNG_KEYED, nbmode=nbmode)
+            if init_state is None:
+                o2.init_placement()
+            else:
+                o2.set_state(init_state)
+            o2.step(s + 1, want_hashes=False)
+            ref = o2.get_state()
+            diff = [(name, np.argwhere(getattr(hs, name) != getattr(ref, name))[:5].tolist())
+                    for name in ("ra", "rb", "a_int", "b_int") if not np.array_equal(getattr(hs, name), getattr(ref, name))]
+            pytest.fail(f"step {s + 1}: hash {h:x} != {int(hashes[s]):x}; obs gpu={rec[0]} oracle={obs_o[s]}; "
+                        f"counters {hs.counters} vs {ref.counters}; diff {diff}")
+    sim.close()
+    return o

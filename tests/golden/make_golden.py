@@ -14,6 +14,9 @@ reference computed, and the files the reference wrote:
   <scenario>_bond.dat   bond.dat written by the reference
   scenarios.json        parameters of every scenario
 
+`small`, `fast` and `pai` run the reference away from its default radii,
+cutoffs, angle windows, pai, time step and mobilities.
+
 Usage: python tests/golden/make_golden.py [scenario ...]
 """
 from __future__ import annotations
@@ -46,6 +49,62 @@ DENSE = dict(
     cis_diss_rate=0.00005,
 )
 
+# off-default physics (every field below has a global in main.cpp:39-99 that
+# oracle/ref_interpose.cpp sets).  The rates of each are chosen so that the
+# window of 1200 steps after the step-3000 dump holds every event kind of
+# tests/_kmc.py COVERAGE (asserted in tests/test_oracle_golden.py).
+# shrunken geometry, other angle windows, a rectangular box
+SMALL = dict(
+    DENSE,
+    box_x=900.0,
+    box_y=700.0,
+    box_z=160.0,
+    ra_radius=14.5,
+    rb_radius=23.25,
+    bond_dist_cutoff=12.5,
+    cis_dist_cutoff=11.0,
+    bond_thetapd_cutoff=30.0,
+    bond_thetaot_cutoff=60.0,
+    cis_thetaot_cutoff=25.0,
+    ass_rate=0.09,
+    diss_rate=0.0005,
+    mono_cis_diss_rate=0.002,
+    cis_diss_rate=0.001,
+)
+# a long step and other mobilities
+FAST = dict(
+    DENSE,
+    time_step=37.0,
+    ra_D=2.5,
+    rb_D=11.0,
+    ra_rot_D=0.03,
+    rb_rot_D=0.011,
+    cis_D=1.25,
+    cis_rot_D=0.009,
+    bond_D=0.9,
+    bond_rot_D=0.008,
+    ass_rate=0.02,
+    box_x=800.0,
+    box_y=1100.0,
+    diss_rate=0.0005,
+    mono_cis_diss_rate=0.001,
+    cis_diss_rate=0.0005,
+)
+# another truncation of pi, wider angle windows
+PAI = dict(
+    DENSE,
+    pai=3.14159265,
+    bond_thetapd_cutoff=60.0,
+    cis_thetaot_cutoff=20.0,
+    ass_rate=0.09,
+    diss_rate=0.001,
+    mono_cis_diss_rate=0.002,
+    cis_diss_rate=0.001,
+)
+# trace rows kept and states dumped by each of them: a window from the
+# placement, the late window the GPU tests start from, the last step
+OFF_DEFAULT = dict(steps=6000, dump=[3000, 6000], keep=[(0, 500), (3000, 3500), (5999, 6000)], aux=False)
+
 SCENARIOS = {
     # reference defaults (main.cpp:39-99): free diffusion + collisions
     "default": dict(t0=20251015, steps=3000, params={}, dump=[3000], keep="all"),
@@ -72,6 +131,9 @@ SCENARIOS = {
         input_cpt=("dense", 5000),
         cpt_at=[10000],
     ),
+    "small": dict(t0=4243, params=SMALL, **OFF_DEFAULT),
+    "fast": dict(t0=77, params=FAST, **OFF_DEFAULT),
+    "pai": dict(t0=1234, params=PAI, **OFF_DEFAULT),
 }
 
 
@@ -138,10 +200,11 @@ def run_scenario(name, sc):
         with gzip.GzipFile(os.path.join(HERE, f"{name}_{s}.cpt.gz"), "wb", mtime=0) as f:
             f.write(data)
     bond = os.path.join(tmp, "bond.dat")
-    if os.path.exists(bond) and os.path.getsize(bond):
+    aux = sc.get("aux", True)  # the files the reference wrote (the off-default scenarios keep the trace only)
+    if aux and os.path.exists(bond) and os.path.getsize(bond):
         shutil.copy(bond, os.path.join(HERE, f"{name}_bond.dat"))
     # the reference's other outputs (main.cpp:178-205, 2258-2305)
-    for fn in ("parameter.log", "test.gro", "cluster.log"):
+    for fn in ("parameter.log", "test.gro", "cluster.log") if aux else ():
         src = os.path.join(tmp, fn)
         if os.path.exists(src) and os.path.getsize(src):
             with open(src, "rb") as f, gzip.GzipFile(os.path.join(HERE, f"{name}_{fn}.gz"), "wb", mtime=0) as g:

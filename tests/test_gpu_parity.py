@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from _kmc import DENSE, O, capi, engine, params
+from _kmc import compare_stepwise as _compare_stepwise
 
 pytestmark = pytest.mark.gpu
 
@@ -29,39 +30,6 @@ def test_device_math_bitexact(op):
     d = engine.math(OPS[op], x, y, device=True)
     bad = np.flatnonzero(h.view(np.uint64) != d.view(np.uint64))
     assert bad.size == 0, f"{op}: {bad.size} mismatches, first x={x[bad[0]]!r} host={h[bad[0]]!r} dev={d[bad[0]]!r}"
-
-
-def _run_pair(p, steps, nbmode=O.NB_BRUTE, init_state=None):
-    o = O.Oracle(p, rng_mode=O.RNG_KEYED, nbmode=nbmode)
-    if init_state is None:
-        o.init_placement()
-        st = o.get_state()
-    else:
-        st = init_state
-        o.set_state(st)
-    sim = engine.Simulation(p)
-    sim.set_state(st)
-    assert sim.get_state().equal(st)
-    return o, sim
-
-
-def _compare_stepwise(p, steps, nbmode=O.NB_BRUTE, init_state=None):
-    o, sim = _run_pair(p, steps, nbmode, init_state)
-    obs_o, hashes = o.step(steps)
-    for s in range(steps):
-        rec = sim.step(1)
-        hs = sim.get_state()
-        h = engine.state_hash(p, hs)
-        if h != int(hashes[s]) or rec[0] != obs_o[s]:
-            o2, _ = _run_pair(p, 0, nbmode, init_state)
-            o2.step(s + 1, want_hashes=False)
-            ref = o2.get_state()
-            diff = [(name, np.argwhere(getattr(hs, name) != getattr(ref, name))[:5].tolist())
-                    for name in ("ra", "rb", "a_int", "b_int") if not np.array_equal(getattr(hs, name), getattr(ref, name))]
-            pytest.fail(f"step {s + 1}: hash {h:x} != {int(hashes[s]):x}; obs gpu={rec[0]} oracle={obs_o[s]}; "
-                        f"counters {hs.counters} vs {ref.counters}; diff {diff}")
-    sim.close()
-    return o
 
 
 def test_default_box_200_steps():

@@ -107,6 +107,80 @@ def test_validate_rejects_inconsistent_links():
     assert engine.host_validate(p, bad) == -8
 
 
+# The parameter envelope (include/kmc.h, kmc_create): kmc_host_check_params is
+# the function kmc_create calls first, kmc_host_validate and the oracle's
+# oracle_create apply it too (tests/test_gpu_params.py checks kmc_create itself).
+ENV_DOUBLES = [n for n, t in capi.Params._fields_ if t is C.c_double]
+ENV_BOUNDED = {"ra_radius": 20.0, "rb_radius": 30.0, "bond_dist_cutoff": 18.0, "cis_dist_cutoff": 15.0}
+ENV_POSITIVE = ["box_x", "box_y", "box_z", "time_step", "pai", "ra_radius", "rb_radius", "bond_dist_cutoff",
+                "cis_dist_cutoff", "bond_thetapd_cutoff", "bond_thetaot_cutoff", "cis_thetaot_cutoff"]
+
+
+def _envelope(want, **kw):
+    """check_params, validate and oracle_create agree with `want` (True: accepted)."""
+    p = params(n_a=3, n_b=2, **{**dict(box_x=400.0, box_y=300.0, box_z=250.0), **kw})
+    rc = engine.host_check_params(p)
+    assert rc == (capi.KMC_OK if want else capi.ERR_ARG), (kw, rc)
+    rc = engine.host_validate(p, capi.HostState(p.n_a, p.n_b))  # (no bonds: a consistent state)
+    if want:
+        assert rc != capi.ERR_ARG, kw
+        O.Oracle(p)
+    else:
+        assert rc == capi.ERR_ARG, kw
+        with pytest.raises(O.OracleError, match="envelope"):
+            O.Oracle(p)
+
+
+def test_envelope_lists_cover_every_double_field():
+    assert len(ENV_DOUBLES) == 26 and set(ENV_POSITIVE) <= set(ENV_DOUBLES) and set(ENV_BOUNDED) <= set(ENV_POSITIVE)
+    _envelope(True)
+    assert engine.host_check_params(params()) == capi.KMC_OK  # the reference's own values
+
+
+@pytest.mark.parametrize("field", list(ENV_BOUNDED))
+def test_envelope_bounds_are_inclusive(field):
+    b = ENV_BOUNDED[field]
+    _envelope(True, **{field: b})
+    _envelope(True, **{field: float(np.nextafter(b, 0.0))})
+    _envelope(False, **{field: float(np.nextafter(b, np.inf))})
+
+
+@pytest.mark.parametrize("field", ENV_DOUBLES)
+def test_envelope_refuses_non_finite_and_negative(field):
+    for bad in (float("nan"), float("inf"), float("-inf"), -1.0, -5e-324):
+        _envelope(False, **{field: bad})
+    if field in ENV_POSITIVE:
+        _envelope(False, **{field: 0.0})
+        _envelope(False, **{field: -0.0})
+    else:
+        _envelope(True, **{field: 0.0})  # a D, rot_D or rate of 0 switches the move or reaction off
+
+
+def test_envelope_population_sizes():
+    for n_a, n_b, want in [(0, 0, False), (-1, 5, False), (5, -1, False), (1, 0, True), (0, 1, True),
+                           (1 << 24, 0, True), ((1 << 24) + 1, 0, False), (1 << 23, (1 << 23) + 1, False)]:
+        p = params(n_a=n_a, n_b=n_b)
+        assert engine.host_check_params(p) == (capi.KMC_OK if want else capi.ERR_ARG), (n_a, n_b)
+
+
+@pytest.mark.parametrize("n_a,n_b", [(40, 0), (0, 20), (1, 0), (0, 1), (1, 1), (2, 1)])
+def test_oracle_steps_degenerate_populations(n_a, n_b):
+    # one species or one protein: placement (oracle = library), 200 steps, brute = cells
+    p = params(n_a=n_a, n_b=n_b, seed=5, box_x=400.0, box_y=300.0, box_z=250.0)
+    st = engine.host_init_random(p)
+    a = O.Oracle(p, nbmode=O.NB_BRUTE)
+    a.init_placement()
+    assert a.get_state().equal(st)
+    b = O.Oracle(p, nbmode=O.NB_CELLS)
+    b.set_state(st)
+    oa, ha = a.step(200)
+    ob, hb = b.step(200)
+    assert np.array_equal(ha, hb) and np.array_equal(oa, ob)
+    assert engine.host_validate(p, a.get_state()) == capi.KMC_OK
+    row, mem = a.clusters()
+    assert len(row) == n_b
+
+
 def test_bond_line_format():
     p = params()
     rec = np.zeros(1, dtype=capi.OBS_DTYPE)[0]

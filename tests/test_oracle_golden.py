@@ -14,7 +14,7 @@ import shutil
 import numpy as np
 import pytest
 
-from _kmc import GOLDEN, O, capi, engine, golden, scenarios, state_from_dump
+from _kmc import COVERAGE, GOLDEN, O, capi, engine, golden, scenarios, state_from_dump, stats_delta
 
 SC = scenarios()
 
@@ -100,6 +100,87 @@ def test_dense_window_covers_every_code_path():
     ev = o.stats()
     for k in ("free_a", "dimer", "free_b", "complex", "multi", "reject", "rl", "snap_bond", "snap_cis"):
         assert ev[k] > 0, k
+
+
+# Off-default physics (make_golden.py SMALL, FAST, PAI): radii, distance and
+# angle cutoffs, pai, time step and mobilities away from main.cpp's values,
+# set in the unmodified reference through oracle/ref_interpose.cpp.
+OFF_DEFAULT = ["small", "fast", "pai"]
+LATE, LATE_WINDOW = 3000, 1200  # the dump and the window tests/test_gpu_params.py runs on the GPU
+
+
+@pytest.mark.parametrize("name", OFF_DEFAULT)
+def test_off_default_parameters_differ_from_reference_defaults(name):
+    d, p = capi.default_params(), _params(name)
+    changed = {k for k in SC[name]["params"] if getattr(p, k) != getattr(d, k)}
+    assert changed >= {"small": {"ra_radius", "rb_radius", "bond_dist_cutoff", "cis_dist_cutoff", "bond_thetapd_cutoff",
+                                 "bond_thetaot_cutoff", "cis_thetaot_cutoff", "box_x", "box_y", "box_z"},
+                       "fast": {"time_step", "ra_D", "rb_D", "ra_rot_D", "rb_rot_D", "cis_D", "cis_rot_D", "bond_D",
+                                "bond_rot_D"},
+                       "pai": {"pai", "bond_thetapd_cutoff", "cis_thetaot_cutoff"}}[name]
+    assert set(SC[name]["params"]) <= set(O.REF_GLOBALS), "a parameter the reference run could not be given"
+
+
+@pytest.mark.parametrize("name", OFF_DEFAULT)
+def test_off_default_placement_matches_reference(name):
+    g = golden(name)
+    o = O.Oracle(_params(name), rng_mode=O.RNG_STREAM, stream_t0=SC[name]["t0"])
+    o.init_placement()
+    assert g["step"][0] == 0
+    assert o.hash() == int(g["hash"][0])
+    assert o.stream_position == (int(g["clock"][0]), int(g["rand_calls"][0]))
+
+
+def _late_oracle(name, start):
+    g = golden(name)
+    p = _params(name)
+    st = state_from_dump(g[f"state_{start}"], p.n_a, p.n_b)
+    i = _rows(g)[start]
+    assert engine.state_hash(p, st) == int(g["hash"][i])
+    o = O.Oracle(p, rng_mode=O.RNG_STREAM, stream_t0=SC[name]["t0"])
+    o.set_state(st)
+    o.set_stream(int(g["clock"][i]), int(g["rand_calls"][i]))
+    return g, o
+
+
+@pytest.mark.parametrize("name", OFF_DEFAULT)
+def test_off_default_window_from_placement(name):
+    g = golden(name)
+    o = O.Oracle(_params(name), rng_mode=O.RNG_STREAM, stream_t0=SC[name]["t0"])
+    o.init_placement()
+    obs, h = o.step(500)
+    assert _check_rows(g, obs, h, 1) == 500
+    end = _rows(g)[500]
+    assert o.stream_position == (int(g["clock"][end]), int(g["rand_calls"][end]))
+
+
+@pytest.mark.parametrize("name", OFF_DEFAULT)
+def test_off_default_late_window_covers_every_code_path(name):
+    """The window the GPU tests run, from the step-3000 dump: its first 500
+    steps row by row, then every 50th, the stream position at its end — and
+    the coverage condition: every event kind occurs in it (the GPU tests
+    assert it again on the keyed oracle's own trajectory from the same dump)."""
+    g, o = _late_oracle(name, LATE)
+    before = o.stats()
+    obs, h = o.step(LATE_WINDOW)
+    assert _check_rows(g, obs, h, LATE + 1) == 500 + (LATE_WINDOW - 500) // 50
+    end = _rows(g)[LATE + LATE_WINDOW]
+    assert o.stream_position == (int(g["clock"][end]), int(g["rand_calls"][end]))
+    ev = stats_delta(before, o.stats())
+    print(name, ev)
+    for k in COVERAGE:
+        assert ev[k] > 0, (k, ev)
+
+
+def test_off_default_final_dump_equals_trace():
+    for name in OFF_DEFAULT:
+        g = golden(name)
+        p = _params(name)
+        last = SC[name]["steps"]
+        st = state_from_dump(g[f"state_{last}"], p.n_a, p.n_b)
+        assert st.step == last and engine.state_hash(p, st) == int(g["hash"][_rows(g)[last]])
+        assert engine.host_validate(p, st) == capi.KMC_OK
+        assert int(st.counters[0]) > 0
 
 
 def test_resume_from_reference_checkpoint(tmp_path):

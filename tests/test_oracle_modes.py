@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _kmc import DENSE, O, capi, engine, params
+from _kmc import DENSE, O, STRIDE, capi, engine, params, scenario_params
 
 
 def test_brute_equals_cells_dense():
@@ -16,6 +16,22 @@ def test_brute_equals_cells_dense():
     oa, ha = a.step(400)
     ob, hb = b.step(400)
     assert np.array_equal(ha, hb) and np.array_equal(oa, ob)
+
+
+@pytest.mark.parametrize("name", ["small", "fast", "pai", "stride"])
+def test_brute_equals_cells_off_default(name):
+    # the mid-size GPU tests of tests/test_gpu_params.py rely on the cell-list oracle at these
+    # parameters: its cells and reaches must not assume the default radii, cutoffs or step length
+    p = params(seed=13, **{**DENSE, **STRIDE}) if name == "stride" else scenario_params(name, seed=13)
+    a = O.Oracle(p, nbmode=O.NB_BRUTE)
+    b = O.Oracle(p, nbmode=O.NB_CELLS)
+    a.init_placement()
+    b.init_placement()
+    oa, ha = a.step(400)
+    ob, hb = b.step(400)
+    assert np.array_equal(ha, hb) and np.array_equal(oa, ob)
+    ev = a.stats()
+    assert ev["reject"] > 0 and ev["mono"] + ev["rl"] > 0, ev
 
 
 @pytest.mark.parametrize("n_a,n_b,L", [(150, 50, 5773.0), (150, 50, 1000.0), (900, 400, 3000.0)])
