@@ -7,10 +7,59 @@
 //
 // Included by kmc_engine.hip after kmc_kernels.hip (one translation unit, the
 // library's flags: -ffp-contract=off keeps d2 below two roundings per product
-// and sum, as the host reference computes it).
+// and sum, as the host reference computes it); the host side of the calls is
+// kmc_observe.hip §analysis.
 #include "kmc_device.h"
+#include "kmc_observe.h"
 
 namespace kmcd {
+
+// ------------------------------------------------------------ bond links
+// The readers of the committed state's protein links every later layer shares
+// (here, not in kmc_device.h: Dev and its accessors are kmc_kernels.hip's).
+// The <= 3 links of slot p as they are stored (slot + 1, 0: none): a receptor's
+// nei2 and nei3 (l[2] = 0), a ligand's nei2..4.  Nothing is checked: every
+// caller has a range policy of its own.
+__device__ __forceinline__ void prot_links(const KParams& P, const Dev& d, int p, int32_t l[3]) {
+  const int NA = P.NA, NB = P.NB;
+  if (p < NA) {
+    l[0] = A_NEI2(d, p);
+    l[1] = A_NEI3(d, p);
+    l[2] = 0;
+  } else {
+    for (int j = 2; j <= 4; ++j) l[j - 2] = B_NEI(d, p - NA, j);
+  }
+}
+
+// The bonds of receptor i (0-based reference index) as reference indices + 1
+// (0: none): its slot through slot_of, nei2 and nei3 there, range-checked, then
+// translated through id_of and checked again.  With `site` / `cx` (the kinetics
+// recorder's) nei4 is read and range-checked with the other two, and whether the
+// cis pair is part of a complex is read at the partner's slot.  False when a
+// slot or a link leaves its range: nothing is read through it then.
+__device__ __forceinline__ bool receptor_bonds(const KParams& P, const Dev& d, int i, int32_t& lig, int32_t& cis,
+                                               int32_t* site = nullptr, bool* cx = nullptr) {
+  const int NA = P.NA, N = P.N;
+  lig = cis = 0;
+  const int slot = d.slot_of[i];
+  if ((unsigned)slot >= (unsigned)NA) return false;
+  const int32_t v2 = A_NEI2(d, slot), v4 = site ? A_NEI4(d, slot) : 0, v3 = A_NEI3(d, slot);
+  if (v2 != 0 && (v2 <= NA || v2 > N)) return false;
+  if (v3 != 0 && (v3 < 1 || v3 > NA)) return false;
+  if (v4 < 0 || v4 > 4) return false;
+  bool ok = true;
+  if (site) *site = v4;
+  if (v2 != 0) {
+    lig = d.id_of[v2 - 1] + 1;
+    ok = lig > NA && lig <= N;
+  }
+  if (v3 != 0) {
+    cis = d.id_of[v3 - 1] + 1;
+    if (cx) *cx = v2 != 0 || A_NEI2(d, v3 - 1) != 0;  // the partner's nei2 at the partner's slot
+    ok = ok && cis >= 1 && cis <= NA && cis != i + 1;
+  }
+  return ok;
+}
 
 // device-side results of one analysis call
 struct AnOut {
@@ -25,6 +74,18 @@ struct AnOut {
 #define AN_HIST_MAX 4096   // census bins / pair bins held in LDS
 #define AN_CHUNK 512       // points per staged chunk of the pair kernel (KMC_DEBUG_PAIR_CHUNK lowers it)
 #define AN_NC_MAX 2048     // cells per axis of the pair binning (wider cells stay correct)
+
+// host side: scratch of the first analysis call, none before it
+struct AnState {
+  int32_t *parent = nullptr, *label = nullptr;
+  unsigned long long *cnt = nullptr, *hist = nullptr;  // [N] packed member counts by root; [AN_HIST_MAX] bins
+  AnOut* out = nullptr;
+  int32_t *cell = nullptr, *rank = nullptr;  // [N] pair binning: cell and rank of each point
+  CellBins bins;
+  double2* pts = nullptr;   // [N] (x, y) sorted by cell
+  double* edges = nullptr;  // [AN_HIST_MAX + 1] squared bin edges
+  int chunk = AN_CHUNK;     // KMC_DEBUG_PAIR_CHUNK: smaller staged chunks (the chunked path at test size)
+};
 
 __device__ __forceinline__ int32_t an_ld(const int32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -73,17 +134,12 @@ __device__ __forceinline__ void an_unite(int32_t* parent, int a, int b, int N, u
 // one vertex (slot p) per thread: unite with its <= 3 neighbours
 __global__ void __launch_bounds__(AN_T) k_an_hook(KParams P, Dev d, int32_t* parent, AnOut* out) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  const int NA = P.NA, NB = P.NB, N = P.N;
+  const int N = P.N;
   if (p >= N) return;
-  int nb[3], n = 0;
-  if (p < NA) {
-    nb[n++] = A_NEI2(d, p);
-    nb[n++] = A_NEI3(d, p);
-  } else {
-    for (int j = 2; j <= 4; ++j) nb[n++] = d.b_int[(size_t)(4 + j - 1) * NB + (p - NA)];
-  }
+  int32_t nb[3];
+  prot_links(P, d, p, nb);
   const int me = d.id_of[p];
-  for (int e = 0; e < n; ++e) {
+  for (int e = 0, n = p < P.NA ? 2 : 3; e < n; ++e) {
     if (nb[e] == 0) continue;
     if (nb[e] < 1 || nb[e] > N) {
       atomicOr(&out->err, 1u);

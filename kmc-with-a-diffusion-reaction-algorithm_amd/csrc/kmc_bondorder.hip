@@ -8,9 +8,11 @@
 //
 // Included by kmc_engine.hip after kmc_structure.hip (one translation unit, the
 // library's flags: -ffp-contract=off, so a term is what include/kmc.h writes
-// down and nothing else).
+// down and nothing else); the host side of the calls is kmc_observe.hip
+// §bond-orientational order.
 #include "kmc_bondorder.h"
 #include "kmc_device.h"
+#include "kmc_observe.h"
 
 namespace kmcd {
 
@@ -33,6 +35,19 @@ struct BoOut {
   unsigned long long sum[6];  // n_sel, n_with, sum_nn, sum_pc, sum_ps, sum_m
   uint32_t err;               // 1: a link or an index left its range; 2: more than BO_NN_MAX neighbours
   uint32_t pad;
+};
+
+// host side: scratch of the first bond order call, its own
+struct BoState {
+  int32_t *cell = nullptr, *rank = nullptr, *ref = nullptr, *nn = nullptr;  // [max(NA, NB)]
+  CellBins bins;
+  longlong2* pts = nullptr;                            // [max(NA, NB)] integer coordinates sorted by cell
+  int2 *pcs = nullptr, *pcs_sorted = nullptr;          // (pc, ps) by reference index / sorted by cell
+  unsigned long long *C = nullptr, *S = nullptr;       // [max(NA, NB)] sums by reference index
+  unsigned long long *hist = nullptr, *corr = nullptr; // [BO_NN_ROWS][BO_HIST_BINS]; [2][BO_CORR_BINS]
+  int64_t* E2 = nullptr;                               // [BO_CORR_BINS + 1] squared integer bin edges
+  BoOut* out = nullptr;
+  int chunk = BO_CHUNK;  // KMC_DEBUG_BO_CHUNK: smaller staged chunks of the correlation (the chunked path at test size)
 };
 
 // orders the wave's own LDS traffic (its lanes run in lockstep; nothing here is shared between waves)
@@ -126,40 +141,8 @@ __device__ __forceinline__ void bo_run(const BoArgs& a, const int32_t* __restric
   *j1 = cstart[ry * a.ncx + c1 + 1];  // <= ncx * ncy: cstart has one entry more than cells
 }
 
-// variant (a): one lane per centre walks its candidates and evaluates a hit's term on the spot
-__global__ void __launch_bounds__(BO_T) k_bo_local_lane(BoArgs a, const int32_t* __restrict__ cstart,
-                                                        const longlong2* __restrict__ pts,
-                                                        const int32_t* __restrict__ refs, unsigned long long* C,
-                                                        unsigned long long* S, int32_t* nn) {
-  const int nsel = cstart[a.ncx * a.ncy];  // the scan's last entry: the binned points (<= n)
-  for (int i = blockIdx.x * BO_T + threadIdx.x; i < nsel; i += gridDim.x * BO_T) {
-    const longlong2 me = pts[i];
-    const int cx = kmcb::cell_of(kmcb::wrap(me.x, a.BX), a.ncx, a.BX), cy = kmcb::cell_of(kmcb::wrap(me.y, a.BY), a.ncy, a.BY);
-    long long sc = 0, ss = 0;
-    int N = 0;
-    for (int r = 0; r < 6; ++r) {
-      int j, j1;
-      bo_run(a, cstart, cx, cy, r, &j, &j1);
-      for (; j < j1; ++j) {  // j < nsel
-        const longlong2 q = pts[j];
-        const long long DX = kmcb::fold(q.x - me.x, a.BX), DY = kmcb::fold(q.y - me.y, a.BY);
-        const long long D2 = DX * DX + DY * DY;
-        if (D2 <= 0 || D2 > a.RC2) continue;
-        int64_t tc, ts;
-        kmcb::term(a.fold, DX, DY, &tc, &ts);
-        sc += tc;
-        ss += ts;
-        ++N;
-      }
-    }
-    const int ref = refs[i];  // < n
-    C[ref] = (unsigned long long)sc;
-    S[ref] = (unsigned long long)ss;
-    nn[ref] = N;
-  }
-}
-
-// variant (b): a wave owns 64 consecutive centres of the sorted order.  Each
+// A wave owns 64 consecutive centres of the sorted order (one lane per centre
+// evaluating its own hits on the spot measured 1.25-1.4x slower: DESIGN.md §14).  Each
 // lane walks its own centre's candidates through the integer filter; the hits
 // are compacted into the wave's LDS queue (ballot + prefix count) and, whenever
 // 64 are queued, all 64 lanes evaluate one term each and add it to the

@@ -13,9 +13,12 @@
 // its current cluster.  Integers only; every loop is bounded and an exhausted
 // bound or a link out of range raises CfAcc::err.
 //
-// Included by kmc_engine.hip after kmc_kinetics.hip.
+// Included by kmc_engine.hip after kmc_kinetics.hip (and kmc_analysis.hip,
+// whose receptor_bonds and an_unite it calls); the host side of the calls is
+// kmc_observe.hip §cluster growth kinetics.
 #include "kmc_coag.h"
 #include "kmc_device.h"
+#include "kmc_observe.h"
 
 namespace kmcd {
 
@@ -50,35 +53,29 @@ struct CfAcc {
   unsigned int pad;
 };
 
-// the current bonds of receptor i (0-based reference index) as reference
-// indices — kin_cur's reads and range checks; false when a slot or a link
-// leaves its range (nothing is read through it then)
-__device__ __forceinline__ bool cf_cur(const KParams& P, const Dev& d, int i, int32_t& lig, int32_t& cis) {
-  const int NA = P.NA, N = P.N;
-  lig = cis = 0;
-  const int slot = d.slot_of[i];
-  if ((unsigned)slot >= (unsigned)NA) return false;
-  const int32_t v2 = A_NEI2(d, slot), v3 = A_NEI3(d, slot);
-  if (v2 != 0 && (v2 <= NA || v2 > N)) return false;
-  if (v3 != 0 && (v3 < 1 || v3 > NA)) return false;
-  bool ok = true;
-  if (v2 != 0) {
-    lig = d.id_of[v2 - 1] + 1;
-    ok = lig > NA && lig <= N;
-  }
-  if (v3 != 0) {
-    cis = d.id_of[v3 - 1] + 1;
-    ok = ok && cis >= 1 && cis <= NA && cis != i + 1;
-  }
-  return ok;
-}
+// host side: scratch of the first kmc_cf_begin, its own; rec.on: a recorder is
+// running (a new state drops it)
+struct CfState {
+  Recorder rec;
+  Scratch scratch;
+  Cf dev = {nullptr, nullptr, {nullptr, nullptr}, {nullptr, nullptr}, nullptr, nullptr, nullptr, nullptr, nullptr};
+  CfTab* tab = nullptr;
+  CfAcc* acc = nullptr;
+  int cur = 0;                       // which of the two label / count sets is the last look's
+  int S = 0;                         // max_size of the begin
+  int64_t ev[CF_NEV] = {0, 0, 0, 0}; // bonds formed / broken since begin, as of the last update
+  int64_t cores = 0, clusters = 0, max = 0, closed = 0, opened = 0;
+  int64_t ns[CF_MAX_SIZE + 1] = {0}; // n_s of the last look
+  int64_t expo[CF_MAX_SIZE + 1] = {0};
+  std::vector<__int128> expo2;       // [(S + 1)^2] since begin
+};
 
 // begin: the current bonds become the stored ones
 __global__ void __launch_bounds__(CF_T) k_cf_begin(KParams P, Dev d, Cf F, CfAcc* acc) {
   const int i = blockIdx.x * CF_T + threadIdx.x;
   if (i >= P.NA) return;
-  int32_t lig, cis;
-  if (!cf_cur(P, d, i, lig, cis)) {
+  int32_t lig, cis;  // the current bonds as reference indices
+  if (!receptor_bonds(P, d, i, lig, cis)) {
     atomicOr(&acc->err, 1u);
     lig = cis = 0;
   }
@@ -108,8 +105,8 @@ __global__ void __launch_bounds__(CF_T) k_cf_hook(KParams P, Dev d, Cf F, CfAcc*
   uint32_t m = 0;
   bool bad = false;
   if (i < P.NA) {
-    int32_t lig, cis;
-    bad = !cf_cur(P, d, i, lig, cis);
+    int32_t lig, cis;  // the current bonds as reference indices
+    bad = !receptor_bonds(P, d, i, lig, cis);
     if (!bad) {  // (a call that met a bad link fails and drops the recorder)
       const int32_t old_lig = F.rl_lig[i], old_cis = F.cis_with[i], me = i + 1;
       if (lig != old_lig) {

@@ -10,10 +10,12 @@
 // bytes per protein stream in order and only the protein's current position
 // (one 16-byte access) and links are gathered through slot_of.
 //
-// Included by kmc_engine.hip after kmc_analysis.hip (one translation unit, the
+// Included by kmc_engine.hip after kmc_bondorder.hip (one translation unit, the
 // library's flags: -ffp-contract=off keeps every product and sum below its own
-// rounding, as the numpy reference computes them).
+// rounding, as the numpy reference computes them); the host side of the calls
+// is kmc_observe.hip §displacement tracking.
 #include "kmc_device.h"
+#include "kmc_observe.h"
 
 namespace kmcd {
 
@@ -44,7 +46,23 @@ struct TrkOut {
   unsigned long long cnt[TRK_NCNT];
 };
 
-// the links of the protein in slot `slot` as the tracker names them
+// host side: scratch of the first kmc_track_begin, none before it; rec.on: an
+// origin is set (a new state drops it)
+struct TrkState {
+  Recorder rec;
+  Scratch scratch;
+  Trk dev = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  TrkAcc* acc = nullptr;
+  TrkOut* out = nullptr;
+  double* part[2] = {nullptr, nullptr};  // the reduction tree's levels, ping-pong
+  double* edges = nullptr;               // [TRK_BINS_MAX + 1] squared bin edges
+  unsigned long long* vh = nullptr;      // [TRK_CLASSES][TRK_BINS_MAX] van Hove bins
+  double max_jump = 0.0;
+};
+
+// the links of the protein in slot `slot` as the tracker names them (a link out
+// of range counts as none).  Its own reads: on top of prot_links it is a line
+// longer (a receptor's entries go around nei4) and the tracker's kernels move
 __device__ __forceinline__ void trk_links(const KParams& P, const Dev& d, int slot, int32_t l[3]) {
   const int NA = P.NA, NB = P.NB, N = P.N;
   auto ref = [&](int v) { return v >= 1 && v <= N ? d.id_of[v - 1] + 1 : 0; };

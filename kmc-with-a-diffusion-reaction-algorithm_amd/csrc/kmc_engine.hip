@@ -1,8 +1,10 @@
 // kmc_engine.hip — C-ABI of libkmc (include/kmc.h): device memory, the
-// per-step launch sequence, state transfer.  One handle per GPU.
+// per-step launch sequence, state transfer.  One handle per GPU.  The
+// read-only analysis calls are kmc_observe.hip's, included below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -40,7 +42,9 @@ static const char* const KNAMES[KI_N] = {
 #define CX_STREAM_N (4 << 20)
 #endif
 
-struct kmc_sim {
+// hidden: the handle is opaque in include/kmc.h; without the attribute its implicit destructor, too large to be
+// inlined with the layers' structs as members, would become a weak export of the library
+struct __attribute__((visibility("hidden"))) kmc_sim {
   kmc_params p;
   KParams K;
   Dev d;
@@ -89,7 +93,7 @@ struct kmc_sim {
   int32_t *a_tmp = nullptr, *b_tmp = nullptr, *id_tmp = nullptr;
   int32_t* rs_cnt = nullptr;     // [256][tiles] digit counts of the radix sort -> first output positions
   int32_t* rs_tot = nullptr;     // [256] digit totals of a radix pass
-  int32_t* scan_part = nullptr;  // tile sums of dev_scan
+  int32_t* scan_part = nullptr;  // tile sums of home_build's scan
   int32_t* hcnt = nullptr;   // [ncell+1] home cell counts (home_build)
   // per-kernel timing: a ring of TRING steps of event pairs, read back lazily
   uint64_t tmask = 0;
@@ -144,79 +148,17 @@ struct kmc_sim {
   bool dd_step_pending = false;     // kmc_dd_step: pack + jumpers after the step's kernels
   unsigned char* dd_step_dst = nullptr;
   double dd_step_S = 0.0;
-  // structure analysis (kmc_analysis.hip): scratch of the first analysis call,
-  // none before it
-  int32_t *an_parent = nullptr, *an_label = nullptr;
-  unsigned long long *an_cnt = nullptr, *an_hist = nullptr;  // [N] packed member counts by root; [AN_HIST_MAX] bins
-  AnOut* an_out = nullptr;
-  int32_t *an_cell = nullptr, *an_rank = nullptr;              // [N] pair binning: cell and rank of each point
-  int32_t *an_ccnt = nullptr, *an_cstart = nullptr, *an_part = nullptr;  // [an_ccap] cell counts, their scan, tile sums
-  size_t an_ccap = 0;
-  double2* an_pts = nullptr;   // [N] (x, y) sorted by cell
-  double* an_edges = nullptr;  // [AN_HIST_MAX + 1] squared bin edges
-  int an_chunk = AN_CHUNK;     // KMC_DEBUG_PAIR_CHUNK: smaller staged chunks (the chunked path at test size)
-  // cluster geometry (kmc_geometry.hip): scratch of the first geometry call, its
-  // own (an interleaved kmc_components / census / track_* call touches none of it)
-  unsigned long long *geo_word = nullptr, *geo_cnt = nullptr;  // [N] (parent, rel) words; packed member counts by root
-  unsigned long long *geo_acc = nullptr, *geo_table = nullptr; // [N][GEO_ACC] moments by root; [GEO_MAX_SIZE + 1][GEO_BIN] bins
-  longlong2* geo_X = nullptr;                                  // [N] integer coordinates
-  int32_t* geo_label = nullptr;
-  int2* geo_off = nullptr;       // [N] image shift against the root
-  uint32_t* geo_span = nullptr;  // [N] spanning bits by root
-  GeoOut* geo_out = nullptr;
-  kmc_cluster* geo_rows = nullptr;  // [geo_rows_cap] kmc_cluster_list's rows
-  size_t geo_rows_cap = 0;
-  // structure factor (kmc_structure.hip): [4][SK_NQ_MAX] sums, then the two selection counts; its own, whatever N
-  unsigned long long* sk_sums = nullptr;
-  // bond-orientational order (kmc_bondorder.hip): scratch of the first bond order call, its own
-  int32_t *bo_cell = nullptr, *bo_rank = nullptr, *bo_ref = nullptr, *bo_nn = nullptr;  // [max(NA, NB)]
-  int32_t *bo_ccnt = nullptr, *bo_cstart = nullptr, *bo_part = nullptr;  // [bo_ccap] cell counts, their scan, tile sums
-  size_t bo_ccap = 0;
-  longlong2* bo_pts = nullptr;                                 // [max(NA, NB)] integer coordinates sorted by cell
-  int2 *bo_pcs = nullptr, *bo_pcs_sorted = nullptr;            // (pc, ps) by reference index / sorted by cell
-  unsigned long long *bo_C = nullptr, *bo_S = nullptr;         // [max(NA, NB)] sums by reference index
-  unsigned long long *bo_hist = nullptr, *bo_corr = nullptr;   // [BO_NN_ROWS][BO_HIST_BINS]; [2][BO_CORR_BINS]
-  int64_t* bo_E2 = nullptr;                                    // [BO_CORR_BINS + 1] squared integer bin edges
-  BoOut* bo_out = nullptr;
-  int bo_chunk = BO_CHUNK;  // KMC_DEBUG_BO_CHUNK: smaller staged chunks of the correlation (the chunked path at test size)
-  int bo_variant = 1;       // KMC_BO_VARIANT: 0 one lane per centre, 1 the wave's hit queue
+  // the read-only layers over the committed state (kmc_observe.hip): each owns
+  // its state, declared next to its kernels; none is touched by a step
+  AnState an;
+  GeoState geo;
+  SkState sk;
+  BoState bo;
+  TrkState trk;
+  KinState kin;
+  CfState cf;
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   double an_ms = 0.0;
-  // displacement tracking (kmc_dynamics.hip): scratch of the first
-  // kmc_track_begin, none before it; trk_on: an origin is set (a new state
-  // drops it)
-  bool trk_on = false;
-  Trk trk = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  TrkAcc* trk_acc = nullptr;
-  TrkOut* trk_out = nullptr;
-  double *trk_part[2] = {nullptr, nullptr};  // the reduction tree's levels, ping-pong
-  double* trk_edges = nullptr;               // [TRK_BINS_MAX + 1] squared bin edges
-  unsigned long long* trk_vh = nullptr;      // [TRK_CLASSES][TRK_BINS_MAX] van Hove bins
-  double trk_max_jump = 0.0;
-  int64_t trk_origin = 0, trk_last = 0, trk_updates = 0;
-  // bond kinetics (kmc_kinetics.hip): scratch of the first kmc_kin_begin, its
-  // own; kin_on: a recorder is running (a new state drops it)
-  bool kin_on = false;
-  Kin kin = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  KinAcc* kin_acc = nullptr;
-  unsigned long long* kin_hist = nullptr;  // [KIN_HISTS][KIN_BINS]: rows 0-6 since begin, 7 and 8 of the last sample
-  int64_t kin_origin = 0, kin_last = 0, kin_updates = 0;
-  int64_t kin_occ[3] = {0, 0, 0};          // rl, mono, complex at the last update
-  int64_t kin_exp[5] = {0, 0, 0, 0, 0};    // exposures since begin
-  // cluster growth kinetics (kmc_coag.hip): scratch of the first kmc_cf_begin,
-  // its own; cf_on: a recorder is running (a new state drops it)
-  bool cf_on = false;
-  Cf cf = {nullptr, nullptr, {nullptr, nullptr}, {nullptr, nullptr}, nullptr, nullptr, nullptr, nullptr, nullptr};
-  CfTab* cf_tab = nullptr;
-  CfAcc* cf_acc = nullptr;
-  int cf_cur = 0;                       // which of the two label / count sets is the last look's
-  int cf_S = 0;                         // max_size of the begin
-  int64_t cf_origin = 0, cf_last = 0, cf_updates = 0;
-  int64_t cf_ev[CF_NEV] = {0, 0, 0, 0}; // bonds formed / broken since begin, as of the last update
-  int64_t cf_cores = 0, cf_clusters = 0, cf_max = 0, cf_closed = 0, cf_opened = 0;
-  int64_t cf_ns[CF_MAX_SIZE + 1] = {0}; // n_s of the last look
-  int64_t cf_expo[CF_MAX_SIZE + 1] = {0};
-  std::vector<__int128> cf_expo2;       // [(S + 1)^2] since begin
 };
 
 namespace {
@@ -330,8 +272,9 @@ double sqrt_threshold(double c) {
   return t;
 }
 
-
 }  // namespace
+
+#include "kmc_observe.hip"
 
 extern "C" {
 
@@ -345,9 +288,7 @@ const char* kmc_last_error(const kmc_sim* s) { return s ? s->err.c_str() : "null
 static int choose_tile(double rho) {
   int t = TILE_MAX;
   while (t > 4 && (t * t * rho > 205.0 || (t + 2) * (t + 2) * 2.0 * rho > 0.75 * TCAP)) --t;
-  const char* te = getenv("KMC_TILE");
-  if (te && *te) t = std::max(2, std::min(TILE_MAX, atoi(te)));
-  return t;
+  return (int)int_getenv("KMC_TILE", t, 2, TILE_MAX);
 }
 
 int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
@@ -429,10 +370,7 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
   K.ref_bb = (float)((2 * p->rb_radius + 2.5) * (2 * p->rb_radius + 2.5));
   K.ref_ab = (float)((p->ra_radius + p->rb_radius + 0.3 + 2.5) * (p->ra_radius + p->rb_radius + 0.3 + 2.5));
   K.ref_rl = (float)((p->bond_dist_cutoff + 3.0) * (p->bond_dist_cutoff + 3.0));
-  {
-    const char* cr = getenv("KMC_COL_REFINE");
-    K.col_refine = !(cr && *cr == '0');
-  }
+  K.col_refine = unless_getenv("KMC_COL_REFINE");
   K.key = kmcr::make_key(p->seed, p->replica);
 
   s->ncell = 2 * K.ncx * K.ncy;  // (row, kind, column) record cells
@@ -468,10 +406,8 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
   rc |= dalloc(s, &d.cx_ext, NB);
   d.mcap = (uint32_t)(3 * (size_t)N);
   K.cx_limit = d.mcap / 2;
-  {
-    const char* cl = getenv("KMC_DEBUG_CX_LIMIT");  // debug: rebuild every complex far earlier
-    if (cl && *cl) K.cx_limit = (uint32_t)std::max(0, std::min((int)K.cx_limit, atoi(cl)));
-  }
+  // debug: rebuild every complex far earlier
+  K.cx_limit = (uint32_t)int_getenv("KMC_DEBUG_CX_LIMIT", K.cx_limit, 0, (int)K.cx_limit);
   rc |= dalloc(s, &d.members, d.mcap);
   rc |= dalloc(s, &d.shuf, d.mcap);
   rc |= dalloc(s, &d.mrec, d.mcap);
@@ -499,10 +435,7 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
   rc |= dalloc(s, &d.home, N);
   rc |= dalloc(s, &d.rec, (size_t)2 * N);
   rc |= dalloc(s, &d.shard_cnt, (size_t)5 * NSHARD);
-  {
-    const char* cs = getenv("KMC_DEBUG_CAP_SHIFT");  // debug: start with lists 2^k times too small
-    s->grow = cs && *cs ? -std::max(0, std::min(20, atoi(cs))) : 0;
-  }
+  s->grow = -(int)int_getenv("KMC_DEBUG_CAP_SHIFT", 0, 0, 20);  // debug: start with lists 2^k times too small
   rc |= alloc_lists(s);
   rc |= dalloc(s, &d.pq_units, N);
   rc |= dalloc(s, &d.obs_part, (size_t)8 * ((N + 255) / 256));
@@ -517,67 +450,42 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
     kmc_destroy(s);
     return KMC_ERR_HIP;
   }
-  const char* po = getenv("KMC_DEBUG_POISON");
-  s->poison = po && *po == '1';
-  const char* dc = getenv("KMC_DEBUG_COUNTS");
-  s->debug_counts = dc && *dc == '1';
-  K.dbg_counts = s->debug_counts;
-  const char* dsy = getenv("KMC_DEBUG_SYNC");
-  s->debug_sync = dsy && *dsy == '1';
-  const char* pc = getenv("KMC_DEBUG_PAIR_CHUNK");  // debug: kmc_pair_counts stages fewer points at a time
-  if (pc && *pc) s->an_chunk = std::max(1, std::min(AN_CHUNK, atoi(pc)));
-  const char* bc = getenv("KMC_DEBUG_BO_CHUNK");  // debug: kmc_bond_order_corr stages fewer points at a time
-  if (bc && *bc) s->bo_chunk = std::max(1, std::min(BO_CHUNK, atoi(bc)));
-  const char* bv = getenv("KMC_BO_VARIANT");  // the cutoff pass of kmc_bond_order: 0 lane per centre, 1 hit queue
-  if (bv && *bv) s->bo_variant = *bv == '0' ? 0 : 1;
+  s->poison = flag_getenv("KMC_DEBUG_POISON");
+  K.dbg_counts = s->debug_counts = flag_getenv("KMC_DEBUG_COUNTS");
+  s->debug_sync = flag_getenv("KMC_DEBUG_SYNC");
+  observe_knobs(s);
   // debug: lower the LDS tile capacity so that tiles take the global path
-  const char* tc = getenv("KMC_DEBUG_TCAP");
-  K.tcap = TCAP;
-  if (tc && *tc) K.tcap = std::max(0, std::min(TCAP, atoi(tc)));
+  K.tcap = (int)int_getenv("KMC_DEBUG_TCAP", TCAP, 0, TCAP);
   // debug: smaller per-tile outlier buckets, so that tiles fall back to the whole outlier list
-  const char* oc = getenv("KMC_DEBUG_TOUT_CAP");
-  K.tout_cap = TOUT_CAP;
-  if (oc && *oc) K.tout_cap = std::max(0, std::min(TOUT_CAP, atoi(oc)));
+  K.tout_cap = (int)int_getenv("KMC_DEBUG_TOUT_CAP", TOUT_CAP, 0, TOUT_CAP);
   // tile side of the LDS scans (mean density of the box)
   {
     K.tile = choose_tile((double)N * K.cs * K.cs / std::max(1.0, p->box_x * p->box_y));
-    const char* fb = getenv("KMC_FULL_BFS");
-    s->always_full = fb && *fb == '1';
-    const char* ds = getenv("KMC_DEBUG_SCAN_STAGE");
-    K.dbg_stage = ds && *ds ? atoi(ds) : 0;
-    const char* cxs = getenv("KMC_CX_SERIAL");
-    K.cx_serial = cxs && *cxs == '1';
-    const char* gr = getenv("KMC_GRAPH");
-    s->use_graphs = gr && *gr == '1';
+    s->always_full = flag_getenv("KMC_FULL_BFS");
+    K.dbg_stage = (int)int_getenv("KMC_DEBUG_SCAN_STAGE", 0, INT_MIN, INT_MAX);
+    K.cx_serial = flag_getenv("KMC_CX_SERIAL");
+    s->use_graphs = flag_getenv("KMC_GRAPH");
     // the complexes' checks and heavy path on a second stream beside the free
     // units from CX_STREAM_N proteins (mode 3; C5: 3.90 (none) / 3.85 (the
     // whole chain beside them, mode 1) -> 3.67 ms/step; C3: 0.452 / 0.455 /
     // 0.468, the latency chains slowed by the free units' HBM stream more
     // than they hide: profiles/r06/ab_cx_stream3_*); KMC_CX_STREAM=0..3 forces a mode
-    const char* cs = getenv("KMC_CX_STREAM");
-    s->cx_stream = (cs && *cs) ? std::max(0, std::min(3, atoi(cs))) : ((int64_t)N >= CX_STREAM_N ? 3 : 0);
+    s->cx_stream = (int)int_getenv("KMC_CX_STREAM", (int64_t)N >= CX_STREAM_N ? 3 : 0, 0, 3);
     // the step's head off the serial chain: on the single-stream
     // path by default; KMC_STEP_CHAIN=0: k_classify every step, as the side-stream
     // modes and a decomposed window
-    const char* sc = getenv("KMC_STEP_CHAIN");
-    K.step_chain = !(sc && *sc == '0') && s->cx_stream == 0 && NB > 0 && (int64_t)N < (1ll << ULOG_SHIFT);
-    const char* dcl = getenv("KMC_DEBUG_CLASSIFY");
-    K.dbg_classify = dcl && *dcl == '1';
-    const char* cpw = getenv("KMC_CX_PARAMS_WG");
-    s->cx_params_wg = cpw && *cpw ? std::max(0, atoi(cpw)) : 0;
-    const char* ht = getenv("KMC_DEBUG_HTAG");  // debug: fewer tagged home entries (the searched lookup)
-    K.htag_max = HTAG_MAX;
-    if (ht && *ht) K.htag_max = std::max(0, std::min(HTAG_MAX, atoi(ht)));
-    const char* dca = getenv("KMC_DEBUG_CAND");
-    K.dbg_cand = dca && *dca == '1';
-    const char* dr = getenv("KMC_DEBUG_RECS");
-    K.dbg_recs = dr && *dr == '1';
+    K.step_chain = unless_getenv("KMC_STEP_CHAIN") && s->cx_stream == 0 && NB > 0 && (int64_t)N < (1ll << ULOG_SHIFT);
+    K.dbg_classify = flag_getenv("KMC_DEBUG_CLASSIFY");
+    s->cx_params_wg = (int)int_getenv("KMC_CX_PARAMS_WG", 0, 0, INT_MAX);
+    // debug: fewer tagged home entries (the searched lookup)
+    K.htag_max = (int)int_getenv("KMC_DEBUG_HTAG", HTAG_MAX, 0, HTAG_MAX);
+    K.dbg_cand = flag_getenv("KMC_DEBUG_CAND");
+    K.dbg_recs = flag_getenv("KMC_DEBUG_RECS");
     if (K.dbg_recs && dalloc(s, &d.rec_step, 2 * (size_t)N) != KMC_OK) {
       kmc_destroy(s);
       return KMC_ERR_HIP;
     }
-    const char* sp = getenv("KMC_SNAP_SPAN");
-    if (sp && *sp) s->snap_span = std::max<int64_t>(0, atoll(sp));
+    s->snap_span = int_getenv("KMC_SNAP_SPAN", s->snap_span, 0, INT64_MAX);
   }
   {
     const uint64_t kmax = (uint64_t)K.ncx * K.ncy;  // row-major cell keys (k_slot_keys)
@@ -587,10 +495,8 @@ int kmc_create(const kmc_params* p, int device, kmc_sim** out) {
       kmc_destroy(s);
       return KMC_ERR_ARG;
     }
-    const char* re = getenv("KMC_RESORT");
-    if (re && *re) s->resort_every = atoll(re);
-    const char* gs = getenv("KMC_GROUP_SORT");
-    if (gs && *gs) s->group_sort = std::max(0, std::min(2, atoi(gs)));
+    s->resort_every = int_getenv("KMC_RESORT", s->resort_every, INT64_MIN, INT64_MAX);
+    s->group_sort = (int)int_getenv("KMC_GROUP_SORT", s->group_sort, 0, 2);
     // per-tile outlier buckets of the pair scan (counters zero between steps)
     s->ntiles = ((K.ncx + K.tile - 1) / K.tile) * ((K.ncy + K.tile - 1) / K.tile);
     if (dalloc(s, &s->d.tout, (size_t)s->ntiles * TOUT_CAP) != KMC_OK ||
@@ -657,14 +563,6 @@ __global__ void k_iota(int32_t* a, int32_t* b, int n) {
   if (i < n) a[i] = b[i] = i;
 }
 
-// Exclusive scan of n counts (in may be out): tile sums, their scan, the tiles.
-static void dev_scan(kmc_sim* s, const int32_t* in, int32_t* out, int n, hipStream_t st) {
-  const int nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-  k_scan_part<<<nb, 256, 0, st>>>(in, n, s->scan_part);
-  k_scan_top<<<1, 256, 0, st>>>(s->scan_part, nb);
-  k_scan_down<<<nb, 256, 0, st>>>(in, out, n, s->scan_part);
-}
-
 // Stable LSD radix sort of the N packed slot keys (skeys, svals) over their
 // low nbits, 8 bits a pass; returns the buffer holding the sorted values.
 static int32_t* radix_sort(kmc_sim* s, int nbits, hipStream_t st, uint64_t** keys_out) {
@@ -712,7 +610,7 @@ static int home_build(kmc_sim* s) {
   const int N = K.N, T = 256;
   HIPCHK(s, hipMemsetAsync(s->hcnt, 0, sizeof(int32_t) * (size_t)(s->ncell + 1), st));
   k_home_count<<<(N + T - 1) / T, T, 0, st>>>(K, d, s->hcnt);
-  dev_scan(s, s->hcnt, d.hstart, s->ncell + 1, st);
+  bins_scan(s, s->hcnt, d.hstart, s->ncell + 1, s->scan_part);
   if (s->debug_sync) {  // debug: hstart the exclusive scan of the counts
     const size_t n = (size_t)s->ncell + 1;
     std::vector<int32_t> c(n), h(n);
@@ -856,10 +754,7 @@ static bool sites_ok(const kmc_params* p, const kmc_state_view* v) {
 static int set_state_impl(kmc_sim* s, const kmc_state_view* v) {
   int rc = kmch_host::validate(&s->p, v, &s->err);
   if (rc != KMC_OK) return rc;
-  {
-    const char* rr = getenv("KMC_RXN_REFINE");
-    s->K.rxn_refine = !(rr && *rr == '0') && sites_ok(&s->p, v);
-  }
+  s->K.rxn_refine = unless_getenv("KMC_RXN_REFINE") && sites_ok(&s->p, v);
   const int NA = s->p.n_a, NB = s->p.n_b;
   Dev& d = s->d;
   // beads arrive in the host layout: into the scratch buffers, converted to
@@ -908,9 +803,9 @@ static int set_state_impl(kmc_sim* s, const kmc_state_view* v) {
   s->need_full = true;
   s->clusters_valid = false;
   s->snap_valid = false;
-  s->trk_on = false;  // the tracker's origin described another state
-  s->kin_on = false;  // and so did the kinetics recorder's links
-  s->cf_on = false;   // and the growth recorder's bonds and clusters
+  s->trk.rec.on = false;  // the tracker's origin described another state
+  s->kin.rec.on = false;  // and so did the kinetics recorder's links
+  s->cf.rec.on = false;   // and the growth recorder's bonds and clusters
   return KMC_OK;
 }
 
@@ -1085,8 +980,7 @@ static int side_stream(kmc_sim* s) {
   // workgroup slots by the free units' stream they ran 2-5x slower): its
   // stream gets the device's highest priority unless KMC_CX_STREAM_PRIO=0
   int lo = 0, hi = 0;
-  const char* pr = getenv("KMC_CX_STREAM_PRIO");
-  const bool prio = !(pr && *pr == '0') && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess;
+  const bool prio = unless_getenv("KMC_CX_STREAM_PRIO") && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess;
   if ((prio ? hipStreamCreateWithPriority(&s->side, hipStreamNonBlocking, hi)
             : hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking)) != hipSuccess ||
       hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -2179,1282 +2073,6 @@ int kmc_dd_counters(kmc_sim* s, int64_t* out) {
   HIPCHK(s, hipMemcpy(&c, s->d.ctl, sizeof c, hipMemcpyDeviceToHost));
   out[0] = c.dd_xcol;
   out[1] = c.dd_xbond;
-  return KMC_OK;
-}
-
-// ---------------------------------------------------------------- analysis
-// Read-only over the committed state (kmc_analysis.hip): nothing below writes
-// a buffer a step reads, so the trajectory, the step counter and
-// clusters_valid stay as they are.
-
-static int an_check(kmc_sim* s) {
-  if (!s->have_state) return fail(s, KMC_ERR_ARG, "analysis: no state");
-  if (s->K.dd) return fail(s, KMC_ERR_ARG, "analysis: a decomposed window is not analysed");
-  return KMC_OK;
-}
-
-// HIP events around one call's device work on the handle's stream
-static int an_begin(kmc_sim* s) {
-  for (auto& e : s->an_ev)
-    if (!e) HIPCHK(s, hipEventCreate(&e));
-  HIPCHK(s, hipEventRecord(s->an_ev[0], s->stream));
-  return KMC_OK;
-}
-static int an_end(kmc_sim* s) {
-  HIPCHK(s, hipEventRecord(s->an_ev[1], s->stream));
-  HIPCHK(s, hipStreamSynchronize(s->stream));
-  float ms = 0;
-  HIPCHK(s, hipEventElapsedTime(&ms, s->an_ev[0], s->an_ev[1]));
-  s->an_ms = ms;
-  return KMC_OK;
-}
-
-// labels (0-based roots, reference order) and the roots' member counts, left
-// on the device; the stream is not waited for
-static int an_components(kmc_sim* s) {
-  const int N = s->K.N, NA = s->K.NA;
-  if (!s->an_out) {
-    int rc = KMC_OK;
-    rc |= dalloc(s, &s->an_parent, (size_t)N);
-    rc |= dalloc(s, &s->an_label, (size_t)N);
-    rc |= dalloc(s, &s->an_cnt, (size_t)N);
-    if (!s->an_hist) rc |= dalloc(s, &s->an_hist, (size_t)AN_HIST_MAX);
-    rc |= dalloc(s, &s->an_out, 1);
-    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "analysis: scratch allocation failed");
-  }
-  hipStream_t st = s->stream;
-  const unsigned g = (unsigned)((N + AN_T - 1) / AN_T);
-  HIPCHK(s, hipMemsetAsync(s->an_out, 0, sizeof(AnOut), st));
-  if (g) {
-    k_an_init<<<g, AN_T, 0, st>>>(s->an_parent, s->an_cnt, N);
-    k_an_hook<<<g, AN_T, 0, st>>>(s->K, s->d, s->an_parent, s->an_out);
-    k_an_flatten<<<g, AN_T, 0, st>>>(s->an_parent, s->an_label, N, s->an_out);
-    k_an_count<<<g, AN_T, 0, st>>>(s->an_label, s->an_cnt, NA, N);
-  }
-  HIPCHK(s, hipGetLastError());
-  return KMC_OK;
-}
-
-int kmc_components(kmc_sim* s, int32_t* label) {
-  if (!s) return KMC_ERR_ARG;
-  int rc = an_check(s);
-  if (rc == KMC_OK) rc = an_begin(s);
-  if (rc == KMC_OK) rc = an_components(s);
-  if (rc == KMC_OK) rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  const int N = s->K.N;
-  AnOut o;
-  HIPCHK(s, hipMemcpy(&o, s->an_out, sizeof o, hipMemcpyDeviceToHost));
-  if (o.err) return fail(s, KMC_ERR_STATE, "analysis: a bond link leaves the state or the link chains do not end");
-  if (label) {
-    HIPCHK(s, hipMemcpy(label, s->an_label, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
-    for (int i = 0; i < N; ++i) label[i] += 1;
-  }
-  return KMC_OK;
-}
-
-int kmc_oligomer_census(kmc_sim* s, int32_t max_r, int32_t max_l, int64_t* hist, kmc_census* out) {
-  if (!s) return KMC_ERR_ARG;
-  if (!out || max_r < 0 || max_l < 0) return fail(s, KMC_ERR_ARG, "census: out is needed, max_r and max_l >= 0");
-  const int64_t nbin = hist ? ((int64_t)max_r + 1) * ((int64_t)max_l + 1) : 0;
-  if (nbin > AN_HIST_MAX)
-    return fail(s, KMC_ERR_ARG, "census: more than " + std::to_string(AN_HIST_MAX) + " bins (larger counts clamp into the last row / column)");
-  int rc = an_check(s);
-  if (rc == KMC_OK) rc = an_begin(s);
-  if (rc == KMC_OK) rc = an_components(s);
-  if (rc != KMC_OK) return rc;
-  const int N = s->K.N;
-  hipStream_t st = s->stream;
-  if (nbin) HIPCHK(s, hipMemsetAsync(s->an_hist, 0, sizeof(unsigned long long) * (size_t)nbin, st));
-  const unsigned g = (unsigned)std::min<int64_t>(AN_WG_MAX, ((int64_t)N + AN_T - 1) / AN_T);
-  if (g)
-    k_an_census<<<g, AN_T, sizeof(unsigned long long) * (size_t)(nbin + 5), st>>>(
-        s->an_label, s->an_cnt, N, max_r, max_l, nbin ? s->an_hist : nullptr, s->an_out);
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  AnOut o;
-  HIPCHK(s, hipMemcpy(&o, s->an_out, sizeof o, hipMemcpyDeviceToHost));
-  if (o.err) return fail(s, KMC_ERR_STATE, "analysis: a bond link leaves the state or the link chains do not end");
-  std::memset(out, 0, sizeof *out);
-  out->n_components = (int64_t)o.n_components;
-  out->n_complexes = (int64_t)o.n_complexes;
-  out->proteins_in_complexes = (int64_t)o.proteins_in_complexes;
-  out->n_cis_dimers = (int64_t)o.n_cis_dimers;
-  if (o.n_components) {
-    const uint32_t root = 0xffffffffu - (uint32_t)o.best;
-    unsigned long long c = 0;
-    HIPCHK(s, hipMemcpy(&c, s->an_cnt + root, sizeof c, hipMemcpyDeviceToHost));
-    out->max_size = (int32_t)(o.best >> 32);
-    out->max_receptors = (int32_t)(uint32_t)c;
-    out->max_ligands = (int32_t)(c >> 32);
-    out->max_label = (int32_t)root + 1;
-  }
-  if (nbin) HIPCHK(s, hipMemcpy(hist, s->an_hist, sizeof(int64_t) * (size_t)nbin, hipMemcpyDeviceToHost));
-  return KMC_OK;
-}
-
-int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int64_t* counts) {
-  if (!s) return KMC_ERR_ARG;
-  if (!counts || which < KMC_PAIR_AA || which > KMC_PAIR_BB || !(r_max > 0.0) || !std::isfinite(r_max) || nbins < 1 ||
-      nbins > AN_HIST_MAX)
-    return fail(s, KMC_ERR_ARG, "pair counts: which 0..2, r_max > 0, 1 <= nbins <= " + std::to_string(AN_HIST_MAX));
-  int rc = an_check(s);
-  if (rc != KMC_OK) return rc;
-  const KParams& K = s->K;
-  const double fx = std::floor(K.box_x / r_max), fy = std::floor(K.box_y / r_max);
-  if (!(fx >= 3.0) || !(fy >= 3.0))
-    return fail(s, KMC_ERR_ARG, "pair counts: r_max above a third of the box (fewer than 3 cells along an axis)");
-  AnGrid G;
-  G.ncx = (int)std::min<double>(fx, AN_NC_MAX);
-  G.ncy = (int)std::min<double>(fy, AN_NC_MAX);
-  G.box_x = K.box_x;
-  G.box_y = K.box_y;
-  G.nsets = which == KMC_PAIR_AB ? 2 : 1;
-  G.lo[0] = which == KMC_PAIR_BB ? K.NA : 0;
-  G.hi[0] = which == KMC_PAIR_BB ? K.N : K.NA;
-  G.lo[1] = K.NA;
-  G.hi[1] = K.N;
-  const int N = K.N, ncell = G.ncx * G.ncy, npts = (G.hi[0] - G.lo[0]) + (G.nsets > 1 ? G.hi[1] - G.lo[1] : 0);
-  const size_t ncnt = (size_t)G.nsets * ncell + 1;  // the scan's last entry is the number of points
-  if (!s->an_pts) {
-    rc = KMC_OK;
-    rc |= dalloc(s, &s->an_cell, (size_t)N);
-    rc |= dalloc(s, &s->an_rank, (size_t)N);
-    rc |= dalloc(s, &s->an_pts, (size_t)N);
-    rc |= dalloc(s, &s->an_edges, (size_t)AN_HIST_MAX + 1);
-    if (!s->an_hist) rc |= dalloc(s, &s->an_hist, (size_t)AN_HIST_MAX);
-    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "analysis: scratch allocation failed");
-  }
-  if (ncnt > s->an_ccap) {
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    dfree(s, s->an_ccnt);
-    dfree(s, s->an_cstart);
-    dfree(s, s->an_part);
-    s->an_ccap = 0;
-    rc = KMC_OK;
-    rc |= dalloc(s, &s->an_ccnt, ncnt);
-    rc |= dalloc(s, &s->an_cstart, ncnt);
-    rc |= dalloc(s, &s->an_part, (ncnt + SCAN_TILE - 1) / SCAN_TILE);
-    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "analysis: scratch allocation failed");
-    s->an_ccap = ncnt;
-  }
-  // bin k holds edges2[k] <= d2 < edges2[k + 1], edges2[m] = (m dr)(m dr) in double
-  const double dr = r_max / nbins;
-  std::vector<double> edges2((size_t)nbins + 1);
-  for (int m = 0; m <= nbins; ++m) edges2[m] = (m * dr) * (m * dr);
-  hipStream_t st = s->stream;
-  rc = an_begin(s);
-  if (rc != KMC_OK) return rc;
-  HIPCHK(s, hipMemcpyAsync(s->an_edges, edges2.data(), sizeof(double) * edges2.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(s, hipMemsetAsync(s->an_hist, 0, sizeof(unsigned long long) * (size_t)nbins, st));
-  HIPCHK(s, hipMemsetAsync(s->an_ccnt, 0, sizeof(int32_t) * ncnt, st));
-  if (npts > 0) {
-    const unsigned g = (unsigned)((npts + AN_T - 1) / AN_T);
-    k_an_cell_count<<<g, AN_T, 0, st>>>(s->K, s->d, G, s->an_ccnt, s->an_cell, s->an_rank);
-    const int nb = (int)((ncnt + SCAN_TILE - 1) / SCAN_TILE);
-    k_scan_part<<<nb, 256, 0, st>>>(s->an_ccnt, (int)ncnt, s->an_part);
-    k_scan_top<<<1, 256, 0, st>>>(s->an_part, nb);
-    k_scan_down<<<nb, 256, 0, st>>>(s->an_ccnt, s->an_cstart, (int)ncnt, s->an_part);
-    k_an_cell_scatter<<<g, AN_T, 0, st>>>(s->K, s->d, G, s->an_cstart, s->an_cell, s->an_rank, s->an_pts);
-    const size_t lds = sizeof(unsigned long long) * (size_t)nbins + 2 * sizeof(double2) * (size_t)s->an_chunk;
-    k_an_pairs<<<(unsigned)std::min(ncell, AN_WG_MAX), AN_T, lds, st>>>(G, s->an_cstart, s->an_pts, s->an_edges, nbins,
-                                                                        (float)(1.0 / dr), s->an_chunk, s->an_hist);
-  }
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);  // (waits: edges2 is read by the copy until here)
-  if (rc != KMC_OK) return rc;
-  HIPCHK(s, hipMemcpy(counts, s->an_hist, sizeof(int64_t) * (size_t)nbins, hipMemcpyDeviceToHost));
-  return KMC_OK;
-}
-
-double kmc_analysis_ms(const kmc_sim* s) { return s ? s->an_ms : 0.0; }
-
-// ---------------------------------------------------------------- cluster geometry
-// kmc_geometry.hip: read-only like the analysis above, on scratch of its own.
-
-static_assert(sizeof(kmc_geom_bin) == sizeof(unsigned long long) * GEO_BIN, "a table bin is GEO_BIN words");
-static_assert(sizeof(kmc_cluster) == 80, "kmc_cluster layout");
-static_assert(KMC_GEOM_MAX_SIZE == GEO_MAX_SIZE, "kmc.h and kmc_geometry.hip agree on the table limit");
-
-// labels, image shifts, spanning bits, member counts and moments by root, left
-// on the device (five launches); the stream is not waited for
-static int geo_run(kmc_sim* s) {
-  const int N = s->K.N, NA = s->K.NA;
-  if (!s->geo_out) {
-    int rc = KMC_OK;
-    rc |= dalloc(s, &s->geo_word, (size_t)N);
-    rc |= dalloc(s, &s->geo_cnt, (size_t)N);
-    rc |= dalloc(s, &s->geo_acc, (size_t)N * GEO_ACC);
-    rc |= dalloc(s, &s->geo_table, (size_t)(GEO_MAX_SIZE + 1) * GEO_BIN);
-    rc |= dalloc(s, &s->geo_X, (size_t)N);
-    rc |= dalloc(s, &s->geo_label, (size_t)N);
-    rc |= dalloc(s, &s->geo_off, (size_t)N);
-    rc |= dalloc(s, &s->geo_span, (size_t)N);
-    rc |= dalloc(s, &s->geo_out, 1);
-    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "geometry: scratch allocation failed");
-  }
-  hipStream_t st = s->stream;
-  const unsigned g = (unsigned)((N + AN_T - 1) / AN_T);
-  const long long BX = (long long)kmcm::round_(s->K.box_x * 1024.0), BY = (long long)kmcm::round_(s->K.box_y * 1024.0);
-  HIPCHK(s, hipMemsetAsync(s->geo_out, 0, sizeof(GeoOut), st));
-  if (g) {
-    k_geo_init<<<g, AN_T, 0, st>>>(s->K, s->d, s->geo_word, s->geo_X, s->geo_cnt, s->geo_span, s->geo_acc);
-    k_geo_hook<<<g, AN_T, 0, st>>>(s->K, s->d, s->geo_word, s->geo_out);
-    k_geo_flatten<<<g, AN_T, 0, st>>>(s->geo_word, s->geo_label, s->geo_off, s->geo_cnt, NA, N, s->geo_out);
-    k_geo_check<<<g, AN_T, 0, st>>>(s->K, s->d, s->geo_label, s->geo_off, s->geo_span, s->geo_out);
-    k_geo_moments<<<g, AN_T, 0, st>>>(s->geo_label, s->geo_off, s->geo_X, s->geo_span, BX, BY, N, s->geo_acc);
-  }
-  HIPCHK(s, hipGetLastError());
-  return KMC_OK;
-}
-
-// the device's verdict of the last geometry call
-static int geo_result(kmc_sim* s, GeoOut* o) {
-  HIPCHK(s, hipMemcpy(o, s->geo_out, sizeof *o, hipMemcpyDeviceToHost));
-  if (o->err & 1u)
-    return fail(s, KMC_ERR_STATE, "geometry: a bond link leaves the state or the link chains do not end");
-  if (o->err & 2u) return fail(s, KMC_ERR_CAPACITY, "geometry: an image shift leaves [-32767, 32767]");
-  return KMC_OK;
-}
-
-int kmc_unwrap(kmc_sim* s, int32_t* label, int32_t* shift, uint8_t* span) {
-  if (!s) return KMC_ERR_ARG;
-  int rc = an_check(s);
-  if (rc == KMC_OK) rc = an_begin(s);
-  if (rc == KMC_OK) rc = geo_run(s);
-  if (rc == KMC_OK) rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  GeoOut o;
-  rc = geo_result(s, &o);
-  if (rc != KMC_OK) return rc;
-  const size_t N = (size_t)s->K.N;
-  std::vector<int32_t> lab(N);
-  std::vector<uint32_t> sp(N);
-  HIPCHK(s, hipMemcpy(lab.data(), s->geo_label, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(sp.data(), s->geo_span, sizeof(uint32_t) * N, hipMemcpyDeviceToHost));
-  if (shift) {
-    std::vector<int2> off(N);
-    HIPCHK(s, hipMemcpy(off.data(), s->geo_off, sizeof(int2) * N, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < N; ++i) {
-      const bool wraps = sp[lab[i]] != 0;  // (its offsets depend on the tree: not reported)
-      shift[i] = wraps ? 0 : off[i].x;
-      shift[N + i] = wraps ? 0 : off[i].y;
-    }
-  }
-  if (span)
-    for (size_t i = 0; i < N; ++i) span[i] = (uint8_t)sp[lab[i]];
-  if (label)
-    for (size_t i = 0; i < N; ++i) label[i] = lab[i] + 1;
-  return KMC_OK;
-}
-
-int kmc_cluster_geometry(kmc_sim* s, int32_t max_size, kmc_geom_bin* table, kmc_geom* out) {
-  if (!s) return KMC_ERR_ARG;
-  if (!out || max_size < 2 || max_size > GEO_MAX_SIZE)
-    return fail(s, KMC_ERR_ARG, "cluster geometry: out is needed, 2 <= max_size <= " + std::to_string(GEO_MAX_SIZE) +
-                                    " (larger clusters clamp into the last bin)");
-  int rc = an_check(s);
-  if (rc == KMC_OK) rc = an_begin(s);
-  if (rc == KMC_OK) rc = geo_run(s);
-  if (rc != KMC_OK) return rc;
-  const int N = s->K.N;
-  const size_t nbin = table ? (size_t)max_size + 1 : 0;
-  hipStream_t st = s->stream;
-  if (nbin) HIPCHK(s, hipMemsetAsync(s->geo_table, 0, sizeof(kmc_geom_bin) * nbin, st));
-  const unsigned g = (unsigned)std::min<int64_t>(GEO_TABLE_WG, ((int64_t)N + AN_T - 1) / AN_T);
-  if (g)
-    k_geo_table<<<g, AN_T, sizeof(unsigned long long) * (nbin * GEO_BIN + 6), st>>>(
-        s->geo_label, s->geo_cnt, s->geo_span, s->geo_acc, N, max_size, nbin ? s->geo_table : nullptr, s->geo_out);
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  GeoOut o;
-  rc = geo_result(s, &o);
-  if (rc != KMC_OK) return rc;
-  std::memset(out, 0, sizeof *out);
-  out->n_measured = (int64_t)o.n_measured;
-  out->n_spanning = (int64_t)o.n_spanning;
-  out->n_span_x = (int64_t)o.n_span_x;
-  out->n_span_y = (int64_t)o.n_span_y;
-  out->proteins_in_spanning = (int64_t)o.proteins_in_spanning;
-  if (o.best) {
-    const uint32_t root = 0xffffffffu - (uint32_t)o.best;
-    uint32_t sp = 0;
-    HIPCHK(s, hipMemcpy(&sp, s->geo_span + root, sizeof sp, hipMemcpyDeviceToHost));
-    out->largest_label = (int32_t)root + 1;
-    out->largest_size = (int32_t)(o.best >> 32);
-    out->largest_span = (int32_t)sp;
-  }
-  if (nbin) HIPCHK(s, hipMemcpy(table, s->geo_table, sizeof(kmc_geom_bin) * nbin, hipMemcpyDeviceToHost));
-  return KMC_OK;
-}
-
-int kmc_cluster_list(kmc_sim* s, int32_t min_size, int64_t cap, kmc_cluster* rows, int64_t* n) {
-  if (!s) return KMC_ERR_ARG;
-  if (!n || min_size < 2 || cap < 0 || (cap > 0 && !rows))
-    return fail(s, KMC_ERR_ARG, "cluster list: n is needed, min_size >= 2, cap >= 0, rows for cap > 0");
-  int rc = an_check(s);
-  if (rc != KMC_OK) return rc;
-  const int N = s->K.N;
-  // no more than N / min_size roots can qualify: a larger cap needs no larger buffer
-  const size_t dcap = (size_t)std::min<int64_t>(cap, N / min_size);
-  if (dcap > s->geo_rows_cap) {
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    dfree(s, s->geo_rows);
-    s->geo_rows_cap = 0;
-    if (dalloc(s, &s->geo_rows, dcap) != KMC_OK) return fail(s, KMC_ERR_HIP, "geometry: scratch allocation failed");
-    s->geo_rows_cap = dcap;
-  }
-  rc = an_begin(s);
-  if (rc == KMC_OK) rc = geo_run(s);
-  if (rc != KMC_OK) return rc;
-  const unsigned g = (unsigned)((N + AN_T - 1) / AN_T);
-  if (g)
-    k_geo_list<<<g, AN_T, 0, s->stream>>>(s->geo_label, s->geo_cnt, s->geo_span, s->geo_acc, N, min_size,
-                                          (long long)dcap, s->geo_rows, s->geo_out);
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  GeoOut o;
-  rc = geo_result(s, &o);
-  if (rc != KMC_OK) return rc;
-  *n = (int64_t)o.n_rows;
-  if (*n > cap)
-    return fail(s, KMC_ERR_CAPACITY, "cluster list: " + std::to_string(*n) + " components qualify, cap is " +
-                                         std::to_string(cap));
-  if (*n) {
-    HIPCHK(s, hipMemcpy(rows, s->geo_rows, sizeof(kmc_cluster) * (size_t)*n, hipMemcpyDeviceToHost));
-    std::sort(rows, rows + *n, [](const kmc_cluster& a, const kmc_cluster& b) { return a.label < b.label; });
-  }
-  return KMC_OK;
-}
-
-// ---------------------------------------------------------------- structure factor
-// kmc_structure.hip: read-only like the analysis above, one launch on scratch of its own.
-
-static_assert(KMC_SK_MAX == SK_MAX, "kmc.h and kmc_structure.h agree on the grid limit");
-#define SK_NQ_MAX ((SK_MAX + 1) * (2 * SK_MAX + 1))
-
-int kmc_structure_factor(kmc_sim* s, int32_t hmax, int32_t kmax, int32_t select, int64_t* sums, int64_t n_sel[2]) {
-  if (!s) return KMC_ERR_ARG;
-  if (!sums || !n_sel || hmax < 0 || hmax > SK_MAX || kmax < 0 || kmax > SK_MAX ||
-      (select != KMC_SK_ALL && select != KMC_SK_BOUND))
-    return fail(s, KMC_ERR_ARG, "structure factor: sums and n_sel are needed, 0 <= hmax, kmax <= " +
-                                    std::to_string(SK_MAX) + ", select is KMC_SK_ALL or KMC_SK_BOUND");
-  int rc = an_check(s);
-  if (rc != KMC_OK) return rc;
-  SkArgs a;
-  a.hmax = hmax;
-  a.kmax = kmax;
-  a.select = select;
-  a.W = 2 * kmax + 1;
-  a.nq = (hmax + 1) * a.W;
-  const int nqb = (a.nq + SK_QB - 1) / SK_QB;
-  a.qb = (a.nq + nqb - 1) / nqb;
-  a.nh_max = std::min(hmax + 1, (a.qb - 1) / a.W + 2);
-  a.E = a.nh_max + kmax + 1;
-  a.BX = (long long)kmcm::round_(s->K.box_x * 1024.0);
-  a.BY = (long long)kmcm::round_(s->K.box_y * 1024.0);
-  if (a.BX < 1 || a.BY < 1) return fail(s, KMC_ERR_ARG, "structure factor: the box is below 2^-10 A");
-  if (a.E > SK_E_MAX) return fail(s, KMC_ERR_CAPACITY, "structure factor: axis tables beyond SK_E_MAX");
-  if (!s->sk_sums && dalloc(s, &s->sk_sums, (size_t)4 * SK_NQ_MAX + 2) != KMC_OK)
-    return fail(s, KMC_ERR_HIP, "structure factor: scratch allocation failed");
-  const size_t nw = (size_t)4 * a.nq;
-  unsigned long long* d_nsel = s->sk_sums + (size_t)4 * SK_NQ_MAX;
-  const int ntile = (std::max(s->K.NA, s->K.NB) + SK_TILE - 1) / SK_TILE;
-  const dim3 grid((unsigned)std::max(1, std::min(ntile, SK_WG / nqb)), (unsigned)nqb);
-  const size_t lds = (sizeof(double2) * (size_t)SK_TILE * a.E + sizeof(longlong2) * SK_TILE + sizeof(int) * (SK_TILE + 1) + 15) / 16 * 16;
-  rc = an_begin(s);
-  if (rc != KMC_OK) return rc;
-  hipStream_t st = s->stream;
-  HIPCHK(s, hipMemsetAsync(s->sk_sums, 0, sizeof(unsigned long long) * nw, st));
-  HIPCHK(s, hipMemsetAsync(d_nsel, 0, sizeof(unsigned long long) * 2, st));
-  k_sk_sums<<<grid, SK_T, lds, st>>>(s->K, s->d, a, s->sk_sums, d_nsel);
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  HIPCHK(s, hipMemcpy(sums, s->sk_sums, sizeof(int64_t) * nw, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(n_sel, d_nsel, sizeof(int64_t) * 2, hipMemcpyDeviceToHost));
-  return KMC_OK;
-}
-
-// ---------------------------------------------------------------- bond-orientational order
-// kmc_bondorder.hip: read-only like the analysis above, on scratch of its own.
-
-static_assert(KMC_BO_MAX_FOLD == BO_MAX_FOLD && KMC_BO_NN_ROWS == BO_NN_ROWS, "kmc.h and kmc_bondorder.h agree");
-static_assert(sizeof(kmc_bond_order_out) == 6 * sizeof(unsigned long long), "kmc_bond_order_out is BoOut's six sums");
-
-// a workgroup's dynamic LDS beyond the 64 KiB every launch may ask for (the CU has 160 KiB)
-static void bo_lds_limit(const void* kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return;
-  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-    (void)hipGetLastError();  // the launch itself reports what it cannot have
-}
-
-// the arguments both calls share, checked and turned into the kernels'; the scratch of the first call
-static int bo_setup(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select, BoArgs* a) {
-  if ((which != KMC_BO_A && which != KMC_BO_B) || (mode != KMC_BO_WITHIN && mode != KMC_BO_LINKED) || fold < 1 ||
-      fold > BO_MAX_FOLD || (select != KMC_BO_ALL && select != KMC_BO_BOUND) ||
-      (mode == KMC_BO_LINKED && which != KMC_BO_B))
-    return fail(s, KMC_ERR_ARG, "bond order: which 0 or 1, mode 0 or 1 (linked: ligands only), 1 <= fold <= " +
-                                    std::to_string(BO_MAX_FOLD) + ", select 0 or 1");
-  int rc = an_check(s);
-  if (rc != KMC_OK) return rc;
-  const KParams& K = s->K;
-  const double bx = kmcm::round_(K.box_x * 1024.0), by = kmcm::round_(K.box_y * 1024.0);
-  if (!(bx >= 1.0) || !(by >= 1.0) || !(bx < (double)BO_BOX_MAX) || !(by < (double)BO_BOX_MAX))
-    return fail(s, KMC_ERR_ARG, "bond order: the box is below 2^-10 A or not below 2^21 A");
-  a->which = which;
-  a->mode = mode;
-  a->fold = fold;
-  a->select = select;
-  a->base = which == KMC_BO_A ? 0 : K.NA;
-  a->n = which == KMC_BO_A ? K.NA : K.NB;
-  a->BX = (long long)bx;
-  a->BY = (long long)by;
-  a->RC2 = 0;
-  a->ncx = a->ncy = 0;
-  if (mode == KMC_BO_WITHIN) {
-    const long long RC =
-        r_cut > 0.0 && r_cut * 1024.0 < (double)BO_BOX_MAX ? (long long)kmcm::round_(r_cut * 1024.0) : 0;
-    if (RC < 1 || a->BX / RC < 3 || a->BY / RC < 3)
-      return fail(s, KMC_ERR_ARG, "bond order: r_cut must be positive and at most a third of the box (3 cells along an axis)");
-    a->RC2 = RC * RC;
-    a->ncx = (int)std::min<long long>(a->BX / RC, BO_NC_MAX);
-    a->ncy = (int)std::min<long long>(a->BY / RC, BO_NC_MAX);
-  }
-  if (!s->bo_out) {
-    const size_t n = (size_t)std::max(K.NA, K.NB);
-    rc = KMC_OK;
-    rc |= dalloc(s, &s->bo_cell, n);
-    rc |= dalloc(s, &s->bo_rank, n);
-    rc |= dalloc(s, &s->bo_ref, n);
-    rc |= dalloc(s, &s->bo_nn, n);
-    rc |= dalloc(s, &s->bo_pts, n);
-    rc |= dalloc(s, &s->bo_pcs, n);
-    rc |= dalloc(s, &s->bo_pcs_sorted, n);
-    rc |= dalloc(s, &s->bo_C, n);
-    rc |= dalloc(s, &s->bo_S, n);
-    rc |= dalloc(s, &s->bo_hist, (size_t)BO_NN_ROWS * BO_HIST_BINS);
-    rc |= dalloc(s, &s->bo_corr, (size_t)2 * BO_CORR_BINS);
-    rc |= dalloc(s, &s->bo_E2, (size_t)BO_CORR_BINS + 1);
-    rc |= dalloc(s, &s->bo_out, 1);
-    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "bond order: scratch allocation failed");
-  }
-  return KMC_OK;
-}
-
-// the set binned on the grid a->ncx x a->ncy (nn_filter: only the proteins with neighbours, with their (pc, ps))
-static int bo_grid(kmc_sim* s, const BoArgs& a, bool corr_grid) {
-  const size_t ncnt = (size_t)a.ncx * a.ncy + 1;  // the scan's last entry is the number of binned points
-  if (ncnt > s->bo_ccap) {
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    dfree(s, s->bo_ccnt);
-    dfree(s, s->bo_cstart);
-    dfree(s, s->bo_part);
-    s->bo_ccap = 0;
-    int rc = KMC_OK;
-    rc |= dalloc(s, &s->bo_ccnt, ncnt);
-    rc |= dalloc(s, &s->bo_cstart, ncnt);
-    rc |= dalloc(s, &s->bo_part, (ncnt + SCAN_TILE - 1) / SCAN_TILE);
-    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "bond order: scratch allocation failed");
-    s->bo_ccap = ncnt;
-  }
-  hipStream_t st = s->stream;
-  HIPCHK(s, hipMemsetAsync(s->bo_ccnt, 0, sizeof(int32_t) * ncnt, st));
-  const unsigned g = (unsigned)((a.n + BO_T - 1) / BO_T);
-  const int nb = (int)((ncnt + SCAN_TILE - 1) / SCAN_TILE);
-  if (g)
-    k_bo_cell_count<<<g, BO_T, 0, st>>>(s->K, s->d, a, corr_grid ? s->bo_nn : nullptr, s->bo_ccnt, s->bo_cell,
-                                        s->bo_rank, s->bo_out);
-  k_scan_part<<<nb, 256, 0, st>>>(s->bo_ccnt, (int)ncnt, s->bo_part);
-  k_scan_top<<<1, 256, 0, st>>>(s->bo_part, nb);
-  k_scan_down<<<nb, 256, 0, st>>>(s->bo_ccnt, s->bo_cstart, (int)ncnt, s->bo_part);
-  if (g)
-    k_bo_cell_scatter<<<g, BO_T, 0, st>>>(s->K, s->d, a, s->bo_cstart, s->bo_cell, s->bo_rank, s->bo_pts, s->bo_ref,
-                                          corr_grid ? s->bo_pcs : nullptr, s->bo_pcs_sorted);
-  HIPCHK(s, hipGetLastError());
-  return KMC_OK;
-}
-
-// the local pass and the reduce, left on the device: (C, S, N) and (pc, ps) by reference index, the six sums and,
-// for nbins > 0, the histogram.  The stream is not waited for.
-static int bo_local(kmc_sim* s, const BoArgs& a, int nbins) {
-  hipStream_t st = s->stream;
-  const size_t n = (size_t)a.n;
-  HIPCHK(s, hipMemsetAsync(s->bo_out, 0, sizeof(BoOut), st));
-  HIPCHK(s, hipMemsetAsync(s->bo_C, 0, sizeof(unsigned long long) * n, st));
-  HIPCHK(s, hipMemsetAsync(s->bo_S, 0, sizeof(unsigned long long) * n, st));
-  HIPCHK(s, hipMemsetAsync(s->bo_nn, 0xff, sizeof(int32_t) * n, st));  // -1: outside the set until a centre writes its count
-  if (nbins) HIPCHK(s, hipMemsetAsync(s->bo_hist, 0, sizeof(unsigned long long) * (size_t)BO_NN_ROWS * nbins, st));
-  if (a.n == 0) return KMC_OK;
-  if (a.mode == KMC_BO_WITHIN) {
-    const int rc = bo_grid(s, a, false);
-    if (rc != KMC_OK) return rc;
-    if (s->bo_variant == 0) {
-      const unsigned g = (unsigned)std::min<int64_t>(BO_WG_MAX, ((int64_t)a.n + BO_T - 1) / BO_T);
-      k_bo_local_lane<<<g, BO_T, 0, st>>>(a, s->bo_cstart, s->bo_pts, s->bo_ref, s->bo_C, s->bo_S, s->bo_nn);
-    } else {
-      const unsigned g = (unsigned)std::min<int64_t>(4 * BO_WG_MAX, ((int64_t)a.n + BO_T - 1) / BO_T);
-      k_bo_local_queue<<<g, BO_T, 0, st>>>(a, s->bo_cstart, s->bo_pts, s->bo_ref, s->bo_C, s->bo_S, s->bo_nn);
-    }
-  } else {
-    k_bo_local_linked<<<(unsigned)((a.n + BO_T - 1) / BO_T), BO_T, 0, st>>>(s->K, s->d, a, s->bo_C, s->bo_S, s->bo_nn,
-                                                                            s->bo_out);
-  }
-  const size_t lds = sizeof(unsigned long long) * (6 + (size_t)BO_NN_ROWS * nbins);
-  bo_lds_limit((const void*)k_bo_reduce, lds);
-  const unsigned g = (unsigned)std::min<int64_t>(nbins > 64 ? 256 : BO_WG_MAX, ((int64_t)a.n + BO_T - 1) / BO_T);
-  k_bo_reduce<<<g, BO_T, lds, st>>>(a.n, nbins, s->bo_C, s->bo_S, s->bo_nn, s->bo_pcs, nbins ? s->bo_hist : nullptr,
-                                    s->bo_out);
-  HIPCHK(s, hipGetLastError());
-  return KMC_OK;
-}
-
-static int bo_result(kmc_sim* s, BoOut* o) {
-  HIPCHK(s, hipMemcpy(o, s->bo_out, sizeof *o, hipMemcpyDeviceToHost));
-  if (o->err & 1u) return fail(s, KMC_ERR_STATE, "bond order: a bond link leaves the state");
-  if (o->err & 2u) return fail(s, KMC_ERR_CAPACITY, "bond order: a protein with more than 65535 neighbours");
-  return KMC_OK;
-}
-
-int kmc_bond_order(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select, int32_t nbins,
-                   int64_t* hist, kmc_bond_order_out* out, int64_t* C, int64_t* S, int32_t* nn) {
-  if (!s) return KMC_ERR_ARG;
-  if (!out || nbins < 1 || nbins > BO_HIST_BINS)
-    return fail(s, KMC_ERR_ARG, "bond order: out is needed, 1 <= nbins <= " + std::to_string(BO_HIST_BINS));
-  BoArgs a;
-  int rc = bo_setup(s, which, mode, fold, r_cut, select, &a);
-  if (rc == KMC_OK) rc = an_begin(s);
-  if (rc == KMC_OK) rc = bo_local(s, a, hist ? nbins : 0);
-  if (rc == KMC_OK) rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  BoOut o;
-  rc = bo_result(s, &o);
-  if (rc != KMC_OK) return rc;
-  std::memcpy(out, o.sum, sizeof *out);
-  const size_t n = (size_t)a.n;
-  if (hist) HIPCHK(s, hipMemcpy(hist, s->bo_hist, sizeof(int64_t) * (size_t)BO_NN_ROWS * nbins, hipMemcpyDeviceToHost));
-  if (C && n) HIPCHK(s, hipMemcpy(C, s->bo_C, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-  if (S && n) HIPCHK(s, hipMemcpy(S, s->bo_S, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-  if (nn && n) {
-    HIPCHK(s, hipMemcpy(nn, s->bo_nn, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i)
-      if (nn[i] < 0) nn[i] = 0;  // outside the set
-  }
-  return KMC_OK;
-}
-
-int kmc_bond_order_corr(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select,
-                        double r_max, int32_t nbins, int64_t* corr) {
-  if (!s) return KMC_ERR_ARG;
-  if (!corr || nbins < 1 || nbins > BO_CORR_BINS || !(r_max > 0.0) || !std::isfinite(r_max))
-    return fail(s, KMC_ERR_ARG, "bond order: corr is needed, r_max > 0, 1 <= nbins <= " + std::to_string(BO_CORR_BINS));
-  BoArgs a;
-  int rc = bo_setup(s, which, mode, fold, r_cut, select, &a);
-  if (rc != KMC_OK) return rc;
-  const double dr = r_max / nbins;
-  const int64_t EN = r_max * 1024.0 < (double)BO_BOX_MAX ? kmcb::corr_edge(nbins, dr) : 0;
-  if (EN < 1 || !(std::floor(s->K.box_x / r_max) >= 3.0) || !(std::floor(s->K.box_y / r_max) >= 3.0) ||
-      a.BX / EN < 3 || a.BY / EN < 3)
-    return fail(s, KMC_ERR_ARG, "bond order: r_max must be at least 2^-10 A and at most a third of the box (3 cells along an axis)");
-  std::vector<int64_t> E2((size_t)nbins + 1);
-  for (int m = 0; m <= nbins; ++m) {
-    const int64_t e = kmcb::corr_edge(m, dr);
-    E2[m] = e * e;
-  }
-  hipStream_t st = s->stream;
-  rc = an_begin(s);
-  if (rc == KMC_OK) rc = bo_local(s, a, 0);
-  if (rc != KMC_OK) return rc;
-  BoOut o;
-  HIPCHK(s, hipStreamSynchronize(st));
-  rc = bo_result(s, &o);  // a local pass that failed ends the call before the pair walk
-  if (rc != KMC_OK) return rc;
-  HIPCHK(s, hipMemcpyAsync(s->bo_E2, E2.data(), sizeof(int64_t) * E2.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(s, hipMemsetAsync(s->bo_corr, 0, sizeof(unsigned long long) * 2 * (size_t)nbins, st));
-  if (a.n > 0) {
-    BoArgs g = a;  // the second grid: cells no narrower than the last edge
-    g.ncx = (int)std::min<int64_t>(a.BX / EN, BO_NC_MAX);
-    g.ncy = (int)std::min<int64_t>(a.BY / EN, BO_NC_MAX);
-    rc = bo_grid(s, g, true);
-    if (rc != KMC_OK) return rc;
-    const size_t lds = 48 * (size_t)s->bo_chunk + sizeof(unsigned long long) * 2 * (size_t)nbins;
-    bo_lds_limit((const void*)k_bo_corr, lds);
-    k_bo_corr<<<(unsigned)std::min(g.ncx * g.ncy, BO_WG_MAX), BO_T, lds, st>>>(
-        g, s->bo_cstart, s->bo_pts, s->bo_pcs_sorted, s->bo_E2, nbins, (float)(1.0 / (dr * 1024.0)), s->bo_chunk,
-        s->bo_corr);
-    HIPCHK(s, hipGetLastError());
-  }
-  rc = an_end(s);  // (waits: E2 is read by the copy until here)
-  if (rc == KMC_OK) rc = bo_result(s, &o);  // the second grid's index check
-  if (rc != KMC_OK) return rc;
-  HIPCHK(s, hipMemcpy(corr, s->bo_corr, sizeof(int64_t) * 2 * (size_t)nbins, hipMemcpyDeviceToHost));
-  return KMC_OK;
-}
-
-// ---------------------------------------------------------------- displacement tracking
-// kmc_dynamics.hip: the tracker is a layer of its own over the committed
-// state; its calls write only the trk_* buffers.
-
-static int trk_check(kmc_sim* s) {
-  const int rc = an_check(s);
-  if (rc != KMC_OK) return rc;
-  if (!s->trk_on) return fail(s, KMC_ERR_ARG, "track: no origin (kmc_track_begin; a new state drops the tracker)");
-  return KMC_OK;
-}
-
-static void trk_free(kmc_sim* s) {
-  dfree(s, s->trk.prev);
-  dfree(s, s->trk.u);
-  dfree(s, s->trk.flags);
-  dfree(s, s->trk.cls);
-  dfree(s, s->trk.link0);
-  dfree(s, s->trk_acc);
-  dfree(s, s->trk_out);
-  dfree(s, s->trk_part[0]);
-  dfree(s, s->trk_part[1]);
-  dfree(s, s->trk_edges);
-  dfree(s, s->trk_vh);
-}
-
-int kmc_track_begin(kmc_sim* s, double max_jump) {
-  if (!s) return KMC_ERR_ARG;
-  int rc = an_check(s);
-  if (rc != KMC_OK) return rc;
-  const double half = 0.5 * std::min(s->K.box_x, s->K.box_y);
-  if (!(max_jump <= 0.0) && !(max_jump <= half))  // (a NaN fails both)
-    return fail(s, KMC_ERR_ARG, "track: max_jump above half the box (or not a number)");
-  const int N = s->K.N;
-  if (!s->trk_acc) {
-    const size_t nblk = ((size_t)N + TRK_T - 1) / TRK_T;
-    rc = KMC_OK;
-    rc |= dalloc(s, &s->trk.prev, (size_t)N);
-    rc |= dalloc(s, &s->trk.u, (size_t)N);
-    rc |= dalloc(s, &s->trk.flags, (size_t)N);
-    rc |= dalloc(s, &s->trk.cls, (size_t)N);
-    rc |= dalloc(s, &s->trk.link0, 3 * (size_t)N);
-    rc |= dalloc(s, &s->trk_out, 1);
-    rc |= dalloc(s, &s->trk_part[0], TRK_NSUM * nblk);
-    rc |= dalloc(s, &s->trk_part[1], TRK_NSUM * ((nblk + TRK_T - 1) / TRK_T));
-    rc |= dalloc(s, &s->trk_edges, (size_t)TRK_BINS_MAX + 1);
-    rc |= dalloc(s, &s->trk_vh, (size_t)TRK_CLASSES * TRK_BINS_MAX);
-    rc |= dalloc(s, &s->trk_acc, 1);
-    if (rc != KMC_OK) {
-      trk_free(s);
-      return fail(s, KMC_ERR_HIP, "track: scratch allocation failed");
-    }
-  }
-  s->trk_on = false;
-  rc = an_begin(s);
-  if (rc != KMC_OK) return rc;
-  HIPCHK(s, hipMemsetAsync(s->trk_acc, 0, sizeof(TrkAcc), s->stream));
-  if (N > 0) k_trk_begin<<<(unsigned)((N + TRK_T - 1) / TRK_T), TRK_T, 0, s->stream>>>(s->K, s->d, s->trk);
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  s->trk_max_jump = max_jump <= 0.0 ? 0.5 * half : max_jump;
-  s->trk_origin = s->trk_last = s->step_done;
-  s->trk_updates = 0;
-  s->trk_on = true;
-  return KMC_OK;
-}
-
-int kmc_track_update(kmc_sim* s, kmc_track_info* info) {
-  if (!s) return KMC_ERR_ARG;
-  int rc = trk_check(s);
-  if (rc == KMC_OK) rc = an_begin(s);
-  if (rc != KMC_OK) return rc;
-  const int N = s->K.N;
-  // the maxima persist since begin; the flag counts are of this update
-  HIPCHK(s, hipMemsetAsync(&s->trk_acc->n_jumped, 0, 2 * sizeof(unsigned long long), s->stream));
-  if (N > 0)
-    k_trk_update<<<(unsigned)((N + TRK_T - 1) / TRK_T), TRK_T, 0, s->stream>>>(s->K, s->d, s->trk, s->trk_max_jump,
-                                                                             s->trk_acc);
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  s->trk_last = s->step_done;
-  s->trk_updates += 1;
-  if (info) {
-    TrkAcc a;
-    HIPCHK(s, hipMemcpy(&a, s->trk_acc, sizeof a, hipMemcpyDeviceToHost));
-    info->origin_step = s->trk_origin;
-    info->last_step = s->trk_last;
-    info->n_updates = s->trk_updates;
-    std::memcpy(&info->max_dx, &a.max_dx, sizeof(double));
-    std::memcpy(&info->max_dy, &a.max_dy, sizeof(double));
-    info->n_jumped = (int64_t)a.n_jumped;
-    info->n_changed = (int64_t)a.n_changed;
-  }
-  return KMC_OK;
-}
-
-int kmc_track_sample(kmc_sim* s, double r_max, int32_t nbins, kmc_track_sample_t* out, int64_t* vanhove) {
-  if (!s) return KMC_ERR_ARG;
-  if (!out || !(r_max > 0.0) || !std::isfinite(r_max) || nbins < 1 || nbins > TRK_BINS_MAX)
-    return fail(s, KMC_ERR_ARG, "track sample: out is needed, r_max > 0, 1 <= nbins <= " + std::to_string(TRK_BINS_MAX));
-  int rc = trk_check(s);
-  if (rc != KMC_OK) return rc;
-  const int N = s->K.N;
-  const double dr = r_max / nbins;
-  std::vector<double> edges2((size_t)nbins + 1);
-  for (int m = 0; m <= nbins; ++m) edges2[m] = (m * dr) * (m * dr);
-  hipStream_t st = s->stream;
-  rc = an_begin(s);
-  if (rc != KMC_OK) return rc;
-  HIPCHK(s, hipMemcpyAsync(s->trk_edges, edges2.data(), sizeof(double) * edges2.size(), hipMemcpyHostToDevice, st));
-  HIPCHK(s, hipMemsetAsync(s->trk_out, 0, sizeof(TrkOut), st));
-  if (vanhove) HIPCHK(s, hipMemsetAsync(s->trk_vh, 0, sizeof(unsigned long long) * TRK_CLASSES * (size_t)nbins, st));
-  // level 1: blocks of 256 proteins -> part[0][s][nblk]; then the tree's next levels until one value per sum
-  int n = (N + TRK_T - 1) / TRK_T, cur = 0;
-  if (n > 0) {
-    const size_t lds = sizeof(unsigned long long) * (size_t)(TRK_NSUM * TRK_T + TRK_NCNT + (vanhove ? TRK_CLASSES * nbins : 0));
-    k_trk_sample<<<(unsigned)std::min(n, AN_WG_MAX), TRK_T, lds, st>>>(s->K, s->d, s->trk, s->trk_edges, nbins,
-                                                                      (float)(1.0 / dr), vanhove ? s->trk_vh : nullptr, n,
-                                                                      s->trk_part[0], s->trk_out);
-    while (n > 1) {
-      const int nout = (n + TRK_T - 1) / TRK_T;
-      k_trk_tree<<<dim3((unsigned)nout, TRK_NSUM), TRK_T, 0, st>>>(s->trk_part[cur], n, s->trk_part[cur ^ 1], nout);
-      n = nout;
-      cur ^= 1;
-    }
-  }
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);  // (waits: edges2 is read by the copy until here)
-  if (rc != KMC_OK) return rc;
-  TrkOut o;
-  double sums[TRK_NSUM] = {0};
-  HIPCHK(s, hipMemcpy(&o, s->trk_out, sizeof o, hipMemcpyDeviceToHost));
-  if (n == 1) HIPCHK(s, hipMemcpy(sums, s->trk_part[cur], sizeof sums, hipMemcpyDeviceToHost));
-  std::memset(out, 0, sizeof *out);
-  out->origin_step = s->trk_origin;
-  out->last_step = s->trk_last;
-  for (int c = 0; c < TRK_CLASSES; ++c) {
-    out->n[c] = (int64_t)o.cnt[c];
-    out->n_clean[c] = (int64_t)o.cnt[TRK_CLASSES + c];
-    out->sum_u2[c] = sums[c];
-    out->sum_u2_clean[c] = sums[TRK_CLASSES + c];
-  }
-  out->rl0 = (int64_t)o.cnt[10];
-  out->rl_now = (int64_t)o.cnt[11];
-  out->rl_kept = (int64_t)o.cnt[12];
-  out->cis0 = (int64_t)o.cnt[13];
-  out->cis_now = (int64_t)o.cnt[14];
-  out->cis_kept = (int64_t)o.cnt[15];
-  if (vanhove)
-    HIPCHK(s, hipMemcpy(vanhove, s->trk_vh, sizeof(int64_t) * TRK_CLASSES * (size_t)nbins, hipMemcpyDeviceToHost));
-  return KMC_OK;
-}
-
-int kmc_track_displacements(kmc_sim* s, double* u, uint8_t* flags) {
-  if (!s) return KMC_ERR_ARG;
-  if (!u) return fail(s, KMC_ERR_ARG, "track displacements: u is needed");
-  const int rc = trk_check(s);
-  if (rc != KMC_OK) return rc;
-  const size_t N = (size_t)s->K.N;
-  std::vector<double2> h(N);
-  HIPCHK(s, hipStreamSynchronize(s->stream));
-  HIPCHK(s, hipMemcpy(h.data(), s->trk.u, sizeof(double2) * N, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < N; ++i) {
-    u[i] = h[i].x;
-    u[N + i] = h[i].y;
-  }
-  if (flags) {
-    HIPCHK(s, hipMemcpy(flags, s->trk.flags, N, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < N; ++i) flags[i] &= (uint8_t)(KMC_TRACK_CHANGED | KMC_TRACK_JUMPED);
-  }
-  return KMC_OK;
-}
-
-int kmc_track_end(kmc_sim* s) {
-  if (!s) return KMC_ERR_ARG;
-  if (s->stream) HIPCHK(s, hipStreamSynchronize(s->stream));
-  trk_free(s);
-  s->trk_on = false;
-  return KMC_OK;
-}
-
-// ---------------------------------------------------------------- bond kinetics
-// kmc_kinetics.hip: the recorder is a layer of its own over the committed
-// state, independent of the tracker; its calls write only the kin_* buffers.
-
-static int kin_check(kmc_sim* s) {
-  const int rc = an_check(s);
-  if (rc != KMC_OK) return rc;
-  if (!s->kin_on) return fail(s, KMC_ERR_ARG, "kinetics: not begun (kmc_kin_begin; a new state drops the recorder)");
-  return KMC_OK;
-}
-
-static void kin_free(kmc_sim* s) {
-  dfree(s, s->kin.rl_lig);
-  dfree(s, s->kin.rl_site);
-  dfree(s, s->kin.cis_with);
-  dfree(s, s->kin.last_lig);
-  dfree(s, s->kin.rl_since);
-  dfree(s, s->kin.cis_since);
-  dfree(s, s->kin.free_since);
-  dfree(s, s->kin.bits);
-  dfree(s, s->kin_hist);
-  dfree(s, s->kin_acc);
-}
-
-// the counters of the call that just ran; a link out of range drops the recorder
-static int kin_result(kmc_sim* s, KinAcc* a) {
-  HIPCHK(s, hipMemcpy(a, s->kin_acc, sizeof *a, hipMemcpyDeviceToHost));
-  if (a->err) {
-    s->kin_on = false;
-    return fail(s, KMC_ERR_STATE, "kinetics: a receptor's bond link leaves its range");
-  }
-  return KMC_OK;
-}
-
-static void kin_fill(const kmc_sim* s, const KinAcc& a, kmc_kin_out* out) {
-  std::memset(out, 0, sizeof *out);
-  out->origin_step = s->kin_origin;
-  out->last_step = s->kin_last;
-  out->n_updates = s->kin_updates;
-  out->rl_on = (int64_t)a.ev[kmck::KIN_EV_RL_ON];
-  out->rl_off = (int64_t)a.ev[kmck::KIN_EV_RL_OFF];
-  out->rl_swap = (int64_t)a.ev[kmck::KIN_EV_RL_SWAP];
-  out->cis_on = (int64_t)a.ev[kmck::KIN_EV_CIS_ON];
-  out->cis_off_mono = (int64_t)a.ev[kmck::KIN_EV_CIS_OFF_MONO];
-  out->cis_off_cx = (int64_t)a.ev[kmck::KIN_EV_CIS_OFF_CX];
-  out->cis_swap = (int64_t)a.ev[kmck::KIN_EV_CIS_SWAP];
-  out->exp_rl = s->kin_exp[0];
-  out->exp_mono = s->kin_exp[1];
-  out->exp_cx = s->kin_exp[2];
-  out->exp_free_receptor = s->kin_exp[3];
-  out->exp_free_site = s->kin_exp[4];
-  out->occ_rl = s->kin_occ[0];
-  out->occ_mono = s->kin_occ[1];
-  out->occ_cx = s->kin_occ[2];
-  out->occ_free_receptor = (int64_t)s->p.n_a - s->kin_occ[0];
-  out->occ_free_site = 3 * (int64_t)s->p.n_b - s->kin_occ[0];
-}
-
-int kmc_kin_begin(kmc_sim* s) {
-  if (!s) return KMC_ERR_ARG;
-  int rc = an_check(s);
-  if (rc != KMC_OK) return rc;
-  const int NA = s->K.NA;
-  if (!s->kin_acc) {
-    rc = KMC_OK;
-    rc |= dalloc(s, &s->kin.rl_lig, (size_t)NA);
-    rc |= dalloc(s, &s->kin.rl_site, (size_t)NA);
-    rc |= dalloc(s, &s->kin.cis_with, (size_t)NA);
-    rc |= dalloc(s, &s->kin.last_lig, (size_t)NA);
-    rc |= dalloc(s, &s->kin.rl_since, (size_t)NA);
-    rc |= dalloc(s, &s->kin.cis_since, (size_t)NA);
-    rc |= dalloc(s, &s->kin.free_since, (size_t)NA);
-    rc |= dalloc(s, &s->kin.bits, (size_t)NA);
-    rc |= dalloc(s, &s->kin_hist, (size_t)KIN_HISTS * KIN_BINS);
-    rc |= dalloc(s, &s->kin_acc, 1);
-    if (rc != KMC_OK) {
-      kin_free(s);
-      return fail(s, KMC_ERR_HIP, "kinetics: scratch allocation failed");
-    }
-  }
-  s->kin_on = false;
-  rc = an_begin(s);
-  if (rc != KMC_OK) return rc;
-  HIPCHK(s, hipMemsetAsync(s->kin_acc, 0, sizeof(KinAcc), s->stream));
-  HIPCHK(s, hipMemsetAsync(s->kin_hist, 0, sizeof(unsigned long long) * KIN_HISTS * KIN_BINS, s->stream));
-  if (NA > 0)
-    k_kin_begin<<<(unsigned)((NA + KIN_T - 1) / KIN_T), KIN_T, 0, s->stream>>>(s->K, s->d, s->kin,
-                                                                              (long long)s->step_done, s->kin_acc);
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  KinAcc a;
-  rc = kin_result(s, &a);
-  if (rc != KMC_OK) return rc;
-  s->kin_on = true;
-  s->kin_origin = s->kin_last = s->step_done;
-  s->kin_updates = 0;
-  for (int k = 0; k < 3; ++k) s->kin_occ[k] = (int64_t)a.occ[k];
-  for (auto& e : s->kin_exp) e = 0;
-  return KMC_OK;
-}
-
-int kmc_kin_update(kmc_sim* s, kmc_kin_out* out) {
-  if (!s) return KMC_ERR_ARG;
-  int rc = kin_check(s);
-  if (rc == KMC_OK) rc = an_begin(s);
-  if (rc != KMC_OK) return rc;
-  const int NA = s->K.NA;
-  // the events persist since begin; the occupancy and the error flag are of this update
-  HIPCHK(s, hipMemsetAsync(s->kin_acc->occ, 0, sizeof(KinAcc) - offsetof(KinAcc, occ), s->stream));
-  if (NA > 0)
-    k_kin_update<<<(unsigned)((NA + KIN_T - 1) / KIN_T), KIN_T, 0, s->stream>>>(
-        s->K, s->d, s->kin, (long long)s->step_done, s->kin_hist, s->kin_acc);
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  // the occupancy is the next update's exposure: read back at every update
-  KinAcc a;
-  rc = kin_result(s, &a);
-  if (rc != KMC_OK) return rc;
-  const int64_t dt = s->step_done - s->kin_last;
-  const int64_t prev[5] = {s->kin_occ[0], s->kin_occ[1], s->kin_occ[2], (int64_t)s->p.n_a - s->kin_occ[0],
-                           3 * (int64_t)s->p.n_b - s->kin_occ[0]};
-  for (int k = 0; k < 5; ++k) s->kin_exp[k] += dt * prev[k];
-  for (int k = 0; k < 3; ++k) s->kin_occ[k] = (int64_t)a.occ[k];
-  s->kin_last = s->step_done;
-  s->kin_updates += 1;
-  if (out) kin_fill(s, a, out);
-  return KMC_OK;
-}
-
-int kmc_kin_sample(kmc_sim* s, kmc_kin_out* out, int64_t* hist) {
-  if (!s) return KMC_ERR_ARG;
-  if (!out) return fail(s, KMC_ERR_ARG, "kinetics sample: out is needed");
-  int rc = kin_check(s);
-  if (rc == KMC_OK) rc = an_begin(s);
-  if (rc != KMC_OK) return rc;
-  const int NA = s->K.NA;
-  unsigned long long* rows = s->kin_hist + (size_t)KIN_ROWS_UPD * KIN_BINS;
-  HIPCHK(s, hipMemsetAsync(rows, 0, sizeof(unsigned long long) * 2 * KIN_BINS, s->stream));
-  HIPCHK(s, hipMemsetAsync(s->kin_acc->alive, 0, sizeof(KinAcc) - offsetof(KinAcc, alive), s->stream));
-  const int nblk = (NA + KIN_T - 1) / KIN_T;
-  if (nblk > 0)
-    k_kin_sample<<<(unsigned)std::min(nblk, AN_WG_MAX), KIN_T, 0, s->stream>>>(NA, s->kin, (long long)s->kin_last, nblk,
-                                                                              rows, s->kin_acc);
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  KinAcc a;
-  rc = kin_result(s, &a);
-  if (rc != KMC_OK) return rc;
-  kin_fill(s, a, out);
-  out->n_rl_censored_alive = (int64_t)a.alive[0];
-  out->n_cis_censored_alive = (int64_t)a.alive[1];
-  if (hist)
-    HIPCHK(s, hipMemcpy(hist, s->kin_hist, sizeof(int64_t) * KIN_HISTS * KIN_BINS, hipMemcpyDeviceToHost));
-  return KMC_OK;
-}
-
-int kmc_kin_get(kmc_sim* s, const kmc_kin_view* v) {
-  if (!s) return KMC_ERR_ARG;
-  if (!v || !v->rl_lig || !v->rl_site || !v->rl_since || !v->cis_with || !v->cis_since || !v->last_lig ||
-      !v->free_since || !v->bits)
-    return fail(s, KMC_ERR_ARG, "kinetics get: the view and its eight arrays are needed");
-  const int rc = kin_check(s);
-  if (rc != KMC_OK) return rc;
-  const size_t NA = (size_t)s->K.NA;
-  HIPCHK(s, hipStreamSynchronize(s->stream));
-  HIPCHK(s, hipMemcpy(v->rl_lig, s->kin.rl_lig, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(v->rl_site, s->kin.rl_site, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(v->rl_since, s->kin.rl_since, sizeof(int64_t) * NA, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(v->cis_with, s->kin.cis_with, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(v->cis_since, s->kin.cis_since, sizeof(int64_t) * NA, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(v->last_lig, s->kin.last_lig, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(v->free_since, s->kin.free_since, sizeof(int64_t) * NA, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(v->bits, s->kin.bits, NA, hipMemcpyDeviceToHost));
-  return KMC_OK;
-}
-
-int kmc_kin_end(kmc_sim* s) {
-  if (!s) return KMC_ERR_ARG;
-  if (s->stream) HIPCHK(s, hipStreamSynchronize(s->stream));
-  kin_free(s);
-  s->kin_on = false;
-  return KMC_OK;
-}
-
-// ---------------------------------------------------------------- cluster growth kinetics
-// kmc_coag.hip: a layer of its own over the committed state, independent of
-// the tracker and of the kinetics recorder; its calls write only the cf_*
-// buffers and the analysis scratch an_components fills.
-
-static int cf_check(kmc_sim* s) {
-  const int rc = an_check(s);
-  if (rc != KMC_OK) return rc;
-  if (!s->cf_on) return fail(s, KMC_ERR_ARG, "growth: not begun (kmc_cf_begin; a new state drops the recorder)");
-  return KMC_OK;
-}
-
-static void cf_free(kmc_sim* s) {
-  dfree(s, s->cf.rl_lig);
-  dfree(s, s->cf.cis_with);
-  for (int k = 0; k < 2; ++k) {
-    dfree(s, s->cf.label[k]);
-    dfree(s, s->cf.cnt[k]);
-  }
-  dfree(s, s->cf.parent);
-  dfree(s, s->cf.core);
-  dfree(s, s->cf.core_cnt);
-  dfree(s, s->cf.pieces_prev);
-  dfree(s, s->cf.pieces_cur);
-  dfree(s, s->cf_tab);
-  dfree(s, s->cf_acc);
-}
-
-// the counters of the call that just ran (the components' flag included); an
-// error drops the recorder
-static int cf_result(kmc_sim* s, bool components, CfAcc* a) {
-  HIPCHK(s, hipMemcpy(a, s->cf_acc, sizeof *a, hipMemcpyDeviceToHost));
-  AnOut o;
-  o.err = 0;
-  if (components) HIPCHK(s, hipMemcpy(&o, s->an_out, sizeof o, hipMemcpyDeviceToHost));
-  if (a->err || o.err) {
-    s->cf_on = false;
-    return fail(s, KMC_ERR_STATE, "growth: a bond link leaves its range or the link chains do not end");
-  }
-  return KMC_OK;
-}
-
-// the look that a begin, an update or a put just took becomes the last one
-static void cf_look(kmc_sim* s, const CfAcc& a) {
-  s->cf_clusters = (int64_t)a.n_clusters;
-  s->cf_max = (int64_t)a.max_cluster;
-  for (int k = 0; k <= CF_MAX_SIZE; ++k) s->cf_ns[k] = (int64_t)a.n_s[k];
-}
-
-// every table and counter since begin starts again at `origin`
-static int cf_reset(kmc_sim* s, int64_t origin) {
-  HIPCHK(s, hipMemsetAsync(s->cf_tab, 0, sizeof(CfTab), s->stream));
-  HIPCHK(s, hipMemsetAsync(s->cf_acc, 0, sizeof(CfAcc), s->stream));
-  s->cf_origin = s->cf_last = origin;
-  s->cf_updates = 0;
-  for (auto& e : s->cf_ev) e = 0;
-  s->cf_cores = s->cf_closed = s->cf_opened = 0;
-  for (auto& e : s->cf_expo) e = 0;
-  s->cf_expo2.assign((size_t)(s->cf_S + 1) * (s->cf_S + 1), (__int128)0);
-  return KMC_OK;
-}
-
-static void cf_fill(const kmc_sim* s, kmc_cf_out* out) {
-  std::memset(out, 0, sizeof *out);
-  out->origin_step = s->cf_origin;
-  out->last_step = s->cf_last;
-  out->n_updates = s->cf_updates;
-  out->max_size = s->cf_S;
-  out->formed_rl = s->cf_ev[CF_EV_FORMED_RL];
-  out->formed_cis = s->cf_ev[CF_EV_FORMED_CIS];
-  out->broken_rl = s->cf_ev[CF_EV_BROKEN_RL];
-  out->broken_cis = s->cf_ev[CF_EV_BROKEN_CIS];
-  out->n_cores = s->cf_cores;
-  out->n_clusters = s->cf_clusters;
-  out->cycles_closed = s->cf_closed;
-  out->cycles_opened = s->cf_opened;
-  out->max_cluster = s->cf_max;
-}
-
-// the components of the current state into the other label / count set, which
-// becomes the last look's
-static int cf_take_components(kmc_sim* s) {
-  const int rc = an_components(s);
-  if (rc != KMC_OK) return rc;
-  const size_t N = (size_t)s->K.N;
-  s->cf_cur ^= 1;
-  HIPCHK(s, hipMemcpyAsync(s->cf.label[s->cf_cur], s->an_label, sizeof(int32_t) * N, hipMemcpyDeviceToDevice,
-                           s->stream));
-  HIPCHK(s, hipMemcpyAsync(s->cf.cnt[s->cf_cur], s->an_cnt, sizeof(unsigned long long) * N, hipMemcpyDeviceToDevice,
-                           s->stream));
-  return KMC_OK;
-}
-
-int kmc_cf_begin(kmc_sim* s, int32_t max_size) {
-  if (!s) return KMC_ERR_ARG;
-  int rc = an_check(s);
-  if (rc != KMC_OK) return rc;
-  if (max_size < CF_MIN_SIZE || max_size > CF_MAX_SIZE)
-    return fail(s, KMC_ERR_ARG, "growth begin: 2 <= max_size <= " + std::to_string(CF_MAX_SIZE));
-  const int NA = s->K.NA, N = s->K.N;
-  if (!s->cf_acc) {
-    rc = KMC_OK;
-    rc |= dalloc(s, &s->cf.rl_lig, (size_t)NA);
-    rc |= dalloc(s, &s->cf.cis_with, (size_t)NA);
-    for (int k = 0; k < 2; ++k) {
-      rc |= dalloc(s, &s->cf.label[k], (size_t)N);
-      rc |= dalloc(s, &s->cf.cnt[k], (size_t)N);
-    }
-    rc |= dalloc(s, &s->cf.parent, (size_t)N);
-    rc |= dalloc(s, &s->cf.core, (size_t)N);
-    rc |= dalloc(s, &s->cf.core_cnt, (size_t)N);
-    rc |= dalloc(s, &s->cf.pieces_prev, (size_t)N);
-    rc |= dalloc(s, &s->cf.pieces_cur, (size_t)N);
-    rc |= dalloc(s, &s->cf_tab, 1);
-    rc |= dalloc(s, &s->cf_acc, 1);
-    if (rc != KMC_OK) {
-      cf_free(s);
-      return fail(s, KMC_ERR_HIP, "growth: scratch allocation failed");
-    }
-  }
-  s->cf_on = false;
-  s->cf_S = max_size;
-  rc = an_begin(s);
-  if (rc == KMC_OK) rc = cf_reset(s, s->step_done);
-  if (rc == KMC_OK) rc = cf_take_components(s);
-  if (rc != KMC_OK) return rc;
-  if (NA > 0) k_cf_begin<<<(unsigned)((NA + CF_T - 1) / CF_T), CF_T, 0, s->stream>>>(s->K, s->d, s->cf, s->cf_acc);
-  if (N > 0)
-    k_cf_sizes<<<(unsigned)((N + CF_T - 1) / CF_T), CF_T, 0, s->stream>>>(s->cf.label[s->cf_cur], s->cf.cnt[s->cf_cur],
-                                                                           N, s->cf_S, s->cf_acc);
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  CfAcc a;
-  rc = cf_result(s, true, &a);
-  if (rc != KMC_OK) return rc;
-  cf_look(s, a);
-  s->cf_on = true;
-  return KMC_OK;
-}
-
-int kmc_cf_update(kmc_sim* s, kmc_cf_out* out) {
-  if (!s) return KMC_ERR_ARG;
-  int rc = cf_check(s);
-  if (rc != KMC_OK) return rc;
-  if (s->step_done == s->cf_last) {  // the state of the last look: nothing to file
-    s->cf_updates += 1;
-    if (out) cf_fill(s, out);
-    return KMC_OK;
-  }
-  rc = an_begin(s);
-  if (rc == KMC_OK) rc = cf_take_components(s);
-  if (rc != KMC_OK) return rc;
-  const int NA = s->K.NA, N = s->K.N, cur = s->cf_cur, prev = cur ^ 1;
-  // the bond counters persist since begin; the rest is of this update
-  HIPCHK(s, hipMemsetAsync(&s->cf_acc->n_cores, 0, sizeof(CfAcc) - offsetof(CfAcc, n_cores), s->stream));
-  const unsigned g = (unsigned)((N + CF_T - 1) / CF_T);
-  if (g) {
-    k_cf_init<<<g, CF_T, 0, s->stream>>>(s->cf, N);
-    if (NA > 0) k_cf_hook<<<(unsigned)((NA + CF_T - 1) / CF_T), CF_T, 0, s->stream>>>(s->K, s->d, s->cf, s->cf_acc);
-    k_cf_flatten<<<g, CF_T, 0, s->stream>>>(s->cf, s->cf.label[prev], s->cf.label[cur], NA, N, s->cf_acc);
-    k_cf_events<<<g, CF_T, 0, s->stream>>>(s->cf, s->cf.label[prev], s->cf.cnt[prev], s->cf.label[cur],
-                                           s->cf.cnt[cur], N, s->cf_S, s->cf_tab, s->cf_acc);
-  }
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);
-  if (rc != KMC_OK) return rc;
-  CfAcc a;
-  rc = cf_result(s, true, &a);
-  if (rc != KMC_OK) return rc;
-  // exposures of the interval that ended, from the previous look's n_s
-  const int S = s->cf_S;
-  const int64_t dt = s->step_done - s->cf_last;
-  for (int x = 1; x <= S; ++x) {
-    const int64_t nx = s->cf_ns[x];
-    s->cf_expo[x] += dt * nx;
-    s->cf_expo2[(size_t)x * (S + 1) + x] += (__int128)dt * nx * (nx - 1) / 2;
-    for (int y = x + 1; y <= S; ++y) s->cf_expo2[(size_t)x * (S + 1) + y] += (__int128)dt * nx * s->cf_ns[y];
-  }
-  // the change of the cycle rank, from this update's bonds
-  int64_t ev[CF_NEV];
-  for (int k = 0; k < CF_NEV; ++k) ev[k] = (int64_t)a.ev[k] - s->cf_ev[k];
-  const int64_t formed = ev[CF_EV_FORMED_RL] + ev[CF_EV_FORMED_CIS], broken = ev[CF_EV_BROKEN_RL] + ev[CF_EV_BROKEN_CIS];
-  const int64_t cores = (int64_t)a.n_cores;
-  s->cf_closed += formed - (cores - (int64_t)a.n_clusters);
-  s->cf_opened += broken - (cores - s->cf_clusters);
-  for (int k = 0; k < CF_NEV; ++k) s->cf_ev[k] = (int64_t)a.ev[k];
-  s->cf_cores = cores;
-  cf_look(s, a);
-  s->cf_last = s->step_done;
-  s->cf_updates += 1;
-  if (out) cf_fill(s, out);
-  return KMC_OK;
-}
-
-int kmc_cf_sample(kmc_sim* s, kmc_cf_out* out, const kmc_cf_tables* t) {
-  if (!s) return KMC_ERR_ARG;
-  if (!out) return fail(s, KMC_ERR_ARG, "growth sample: out is needed");
-  const int rc = cf_check(s);
-  if (rc != KMC_OK) return rc;
-  cf_fill(s, out);
-  if (!t) return KMC_OK;
-  const int S = s->cf_S;
-  const size_t n1 = (size_t)S + 1, n2 = n1 * n1;
-  HIPCHK(s, hipStreamSynchronize(s->stream));
-  auto pull = [&](int64_t* dst, const unsigned long long* src, size_t n) -> hipError_t {
-    return dst ? hipMemcpy(dst, src, sizeof(int64_t) * n, hipMemcpyDeviceToHost) : hipSuccess;
-  };
-  HIPCHK(s, pull(t->merge, s->cf_tab->merge, n2));
-  HIPCHK(s, pull(t->frag, s->cf_tab->frag, n2));
-  HIPCHK(s, pull(t->merge_kind, s->cf_tab->merge_kind, CF_KINDS * CF_KINDS));
-  HIPCHK(s, pull(t->frag_kind, s->cf_tab->frag_kind, CF_KINDS * CF_KINDS));
-  HIPCHK(s, pull(t->merge_pieces, s->cf_tab->merge_pieces, CF_PIECES));
-  HIPCHK(s, pull(t->frag_pieces, s->cf_tab->frag_pieces, CF_PIECES));
-  HIPCHK(s, pull(t->merge_product, s->cf_tab->merge_product, n1));
-  HIPCHK(s, pull(t->frag_parent, s->cf_tab->frag_parent, n1));
-  if (t->n_s) std::copy(s->cf_ns, s->cf_ns + n1, t->n_s);
-  if (t->expo) std::copy(s->cf_expo, s->cf_expo + n1, t->expo);
-  if (t->expo2)
-    for (size_t b = 0; b < n2; ++b) {
-      t->expo2[b].lo = (uint64_t)(unsigned __int128)s->cf_expo2[b];
-      t->expo2[b].hi = (int64_t)(s->cf_expo2[b] >> 64);
-    }
-  return KMC_OK;
-}
-
-int kmc_cf_get(kmc_sim* s, const kmc_cf_view* v) {
-  if (!s) return KMC_ERR_ARG;
-  if (!v || !v->rl_lig || !v->cis_with || !v->prev_label)
-    return fail(s, KMC_ERR_ARG, "growth get: the view and its three arrays are needed");
-  const int rc = cf_check(s);
-  if (rc != KMC_OK) return rc;
-  const size_t NA = (size_t)s->K.NA, N = (size_t)s->K.N;
-  HIPCHK(s, hipStreamSynchronize(s->stream));
-  HIPCHK(s, hipMemcpy(v->rl_lig, s->cf.rl_lig, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(v->cis_with, s->cf.cis_with, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
-  HIPCHK(s, hipMemcpy(v->prev_label, s->cf.label[s->cf_cur], sizeof(int32_t) * N, hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < N; ++i) v->prev_label[i] += 1;
-  return KMC_OK;
-}
-
-int kmc_cf_put(kmc_sim* s, const kmc_cf_view* v, int64_t last_step) {
-  if (!s) return KMC_ERR_ARG;
-  if (!v || !v->rl_lig || !v->cis_with || !v->prev_label)
-    return fail(s, KMC_ERR_ARG, "growth put: the view and its three arrays are needed");
-  int rc = cf_check(s);
-  if (rc != KMC_OK) return rc;
-  if (last_step > s->step_done) return fail(s, KMC_ERR_ARG, "growth put: last_step lies after the current step");
-  const int NA = s->K.NA, N = s->K.N;
-  for (int i = 0; i < NA; ++i) {
-    const int32_t l = v->rl_lig[i], c = v->cis_with[i];
-    if ((l != 0 && (l <= NA || l > N)) || (c != 0 && (c < 1 || c > NA || c == i + 1)))
-      return fail(s, KMC_ERR_STATE, "growth put: a stored bond of receptor " + std::to_string(i + 1) + " leaves its range");
-  }
-  std::vector<int32_t> lab((size_t)N);
-  for (int i = 0; i < N; ++i) {
-    const int32_t l = v->prev_label[i];
-    // a class' label is one of its members, labelled by itself, and no member lies below it
-    if (l < 1 || l > i + 1 || v->prev_label[l - 1] != l)
-      return fail(s, KMC_ERR_STATE, "growth put: the label of protein " + std::to_string(i + 1) +
-                                        " is out of range or not the smallest member of its class");
-    lab[(size_t)i] = l - 1;
-  }
-  rc = an_begin(s);
-  if (rc == KMC_OK) rc = cf_reset(s, last_step);
-  if (rc != KMC_OK) return rc;
-  const int cur = s->cf_cur;
-  hipStream_t st = s->stream;
-  HIPCHK(s, hipMemcpyAsync(s->cf.rl_lig, v->rl_lig, sizeof(int32_t) * (size_t)NA, hipMemcpyHostToDevice, st));
-  HIPCHK(s, hipMemcpyAsync(s->cf.cis_with, v->cis_with, sizeof(int32_t) * (size_t)NA, hipMemcpyHostToDevice, st));
-  HIPCHK(s, hipMemcpyAsync(s->cf.label[cur], lab.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, st));
-  HIPCHK(s, hipMemsetAsync(s->cf.cnt[cur], 0, sizeof(unsigned long long) * (size_t)N, st));
-  const unsigned g = (unsigned)((N + CF_T - 1) / CF_T);
-  if (g) {
-    k_an_count<<<g, AN_T, 0, st>>>(s->cf.label[cur], s->cf.cnt[cur], NA, N);
-    k_cf_sizes<<<g, CF_T, 0, st>>>(s->cf.label[cur], s->cf.cnt[cur], N, s->cf_S, s->cf_acc);
-  }
-  HIPCHK(s, hipGetLastError());
-  rc = an_end(s);  // (waits: lab is read by the copy until here)
-  if (rc != KMC_OK) return rc;
-  CfAcc a;
-  rc = cf_result(s, false, &a);
-  if (rc != KMC_OK) return rc;
-  cf_look(s, a);
-  return KMC_OK;
-}
-
-int kmc_cf_end(kmc_sim* s) {
-  if (!s) return KMC_ERR_ARG;
-  if (s->stream) HIPCHK(s, hipStreamSynchronize(s->stream));
-  cf_free(s);
-  s->cf_on = false;
   return KMC_OK;
 }
 

@@ -5,9 +5,11 @@
 // b_int, id_of), name proteins by their reference index and run in a fixed
 // number of launches whatever the shape of the clusters.
 //
-// Included by kmc_engine.hip after kmc_analysis.hip (one translation unit, the
-// library's flags: -ffp-contract=off, so the edge shift below is the quotient
-// and the rounding include/kmc.h writes down and nothing else).
+// Included by kmc_engine.hip after kmc_analysis.hip, whose prot_links and an_xy
+// it uses (one translation unit, the library's flags: -ffp-contract=off, so the
+// edge shift below is the quotient and the rounding include/kmc.h writes down
+// and nothing else); the host side of the calls is kmc_observe.hip §cluster
+// geometry.
 #include "kmc_device.h"
 
 namespace kmcd {
@@ -29,6 +31,20 @@ struct GeoOut {
                              // words of GeoOut, which one device-scope line takes at ≈90 per µs only
 
 typedef unsigned long long geo_u64;
+
+// host side: scratch of the first geometry call, its own (an interleaved
+// kmc_components / census / track_* call touches none of it)
+struct GeoState {
+  geo_u64 *word = nullptr, *cnt = nullptr;   // [N] (parent, rel) words; packed member counts by root
+  geo_u64 *acc = nullptr, *table = nullptr;  // [N][GEO_ACC] moments by root; [GEO_MAX_SIZE + 1][GEO_BIN] bins
+  longlong2* X = nullptr;                    // [N] integer coordinates
+  int32_t* label = nullptr;
+  int2* off = nullptr;       // [N] image shift against the root
+  uint32_t* span = nullptr;  // [N] spanning bits by root
+  GeoOut* out = nullptr;
+  kmc_cluster* rows = nullptr;  // [rows_cap] kmc_cluster_list's rows
+  size_t rows_cap = 0;
+};
 
 // one vertex word: parent << 32 | (uint16) rel_x << 16 | (uint16) rel_y, rel = off(vertex) − off(parent)
 __device__ __forceinline__ geo_u64 geo_pack(int parent, int rx, int ry) {
@@ -146,15 +162,7 @@ __device__ __forceinline__ void geo_unite(geo_u64* word, int a, int b, int nx, i
 
 // the <= 3 neighbour slots of slot p (0-based; −1 none), false when a link leaves [1, N]
 __device__ __forceinline__ bool geo_links(const KParams& P, const Dev& d, int p, int* nb) {
-  const int NA = P.NA, NB = P.NB;
-  int n = 0;
-  if (p < NA) {
-    nb[n++] = A_NEI2(d, p);
-    nb[n++] = A_NEI3(d, p);
-    nb[n++] = 0;
-  } else {
-    for (int j = 2; j <= 4; ++j) nb[n++] = B_NEI(d, p - NA, j);
-  }
+  prot_links(P, d, p, nb);
   bool ok = true;
   for (int e = 0; e < 3; ++e) {
     if (nb[e] < 0 || nb[e] > P.N) {

@@ -13,8 +13,11 @@
 // gathered.  The per-receptor transition and the bin rule are kmc_kinetics.h's,
 // shared with the host counterpart.  Integers only.
 //
-// Included by kmc_engine.hip after kmc_dynamics.hip.
+// Included by kmc_engine.hip after kmc_dynamics.hip (and kmc_analysis.hip,
+// whose receptor_bonds kin_cur calls); the host side of the calls is
+// kmc_observe.hip §bond kinetics.
 #include "kmc_device.h"
+#include "kmc_observe.h"
 #include "kmc_kinetics.h"
 
 namespace kmcd {
@@ -35,31 +38,25 @@ struct KinAcc {
   unsigned int pad;
 };
 
+// host side: scratch of the first kmc_kin_begin, its own; rec.on: a recorder is
+// running (a new state drops it)
+struct KinState {
+  Recorder rec;
+  Scratch scratch;
+  Kin dev = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  KinAcc* acc = nullptr;
+  unsigned long long* hist = nullptr;  // [KIN_HISTS][KIN_BINS]: rows 0-6 since begin, 7 and 8 of the last sample
+  int64_t occ[3] = {0, 0, 0};          // rl, mono, complex at the last update
+  int64_t exp[5] = {0, 0, 0, 0, 0};    // exposures since begin
+};
+
 // the current links of receptor i (0-based reference index) as the recorder
 // names them; false when a slot or a link leaves its range (nothing is read
 // through it then)
 __device__ __forceinline__ bool kin_cur(const KParams& P, const Dev& d, int i, kmck::Cur& c) {
-  const int NA = P.NA, N = P.N;
-  c.lig = c.site = c.cis = 0;
+  c.site = 0;
   c.cx = false;
-  const int slot = d.slot_of[i];
-  if ((unsigned)slot >= (unsigned)NA) return false;
-  const int32_t v2 = A_NEI2(d, slot), v4 = A_NEI4(d, slot), v3 = A_NEI3(d, slot);
-  if (v2 != 0 && (v2 <= NA || v2 > N)) return false;
-  if (v3 != 0 && (v3 < 1 || v3 > NA)) return false;
-  if (v4 < 0 || v4 > 4) return false;
-  bool ok = true;
-  c.site = v4;
-  if (v2 != 0) {
-    c.lig = d.id_of[v2 - 1] + 1;
-    ok = c.lig > NA && c.lig <= N;
-  }
-  if (v3 != 0) {
-    c.cis = d.id_of[v3 - 1] + 1;
-    c.cx = v2 != 0 || A_NEI2(d, v3 - 1) != 0;  // the partner's nei2 at the partner's slot
-    ok = ok && c.cis >= 1 && c.cis <= NA && c.cis != i + 1;
-  }
-  return ok;
+  return receptor_bonds(P, d, i, c.lig, c.cis, &c.site, &c.cx);
 }
 
 // the counters: per wave one ballot per counter, lane 0 adds the non-zero

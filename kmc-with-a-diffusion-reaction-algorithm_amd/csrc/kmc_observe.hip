@@ -1,0 +1,1281 @@
+// kmc_observe.hip — the host side of the read-only layers over the committed
+// state: their C-ABI calls, one section a layer, over the
+// kernels and the state structs of kmc_analysis.hip ... kmc_coag.hip.  Nothing
+// here writes a buffer a step reads, so the trajectory, the step counter and
+// clusters_valid stay as they are.
+//
+// Included by kmc_engine.hip after its helpers (fail, HIPCHK, dalloc, dfree):
+// one translation unit, the library's flags.  What the layers share comes
+// first; the engine uses the knob helpers and bins_scan too.
+
+namespace {
+
+// ---------------------------------------------------------------- environment knobs
+// the three idioms: on by '1'; on unless '0'; an integer clamped into [lo, hi]
+// (dflt when unset or empty).  The knob's literal name comes first:
+// tests/test_knob_docs.py finds the knobs by it.
+bool flag_getenv(const char* name) {
+  const char* v = getenv(name);
+  return v && *v == '1';
+}
+bool unless_getenv(const char* name) {
+  const char* v = getenv(name);
+  return !(v && *v == '0');
+}
+int64_t int_getenv(const char* name, int64_t dflt, int64_t lo, int64_t hi) {
+  const char* v = getenv(name);
+  return v && *v ? std::max(lo, std::min(hi, (int64_t)atoll(v))) : dflt;
+}
+
+void observe_knobs(kmc_sim* s) {
+  // debug: kmc_pair_counts stages fewer points at a time
+  s->an.chunk = (int)int_getenv("KMC_DEBUG_PAIR_CHUNK", AN_CHUNK, 1, AN_CHUNK);
+  // debug: kmc_bond_order_corr stages fewer points at a time
+  s->bo.chunk = (int)int_getenv("KMC_DEBUG_BO_CHUNK", BO_CHUNK, 1, BO_CHUNK);
+}
+
+// ---------------------------------------------------------------- cell binning
+// Exclusive scan of n counts (in may be out) on the handle's stream: tile sums
+// into part, their scan, the tiles.
+void bins_scan(kmc_sim* s, const int32_t* in, int32_t* out, int n, int32_t* part) {
+  const int nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+  k_scan_part<<<nb, 256, 0, s->stream>>>(in, n, part);
+  k_scan_top<<<1, 256, 0, s->stream>>>(part, nb);
+  k_scan_down<<<nb, 256, 0, s->stream>>>(in, out, n, part);
+}
+
+// room for ncnt counts (the cells and the scan's last entry); `what` names the layer in the failure
+int bins_reserve(kmc_sim* s, CellBins& b, size_t ncnt, const char* what) {
+  if (ncnt <= b.cap) return KMC_OK;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  dfree(s, b.ccnt);
+  dfree(s, b.cstart);
+  dfree(s, b.part);
+  b.cap = 0;
+  int rc = KMC_OK;
+  rc |= dalloc(s, &b.ccnt, ncnt);
+  rc |= dalloc(s, &b.cstart, ncnt);
+  rc |= dalloc(s, &b.part, (ncnt + SCAN_TILE - 1) / SCAN_TILE);
+  if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, std::string(what) + ": scratch allocation failed");
+  b.cap = ncnt;
+  return KMC_OK;
+}
+
+// squared bin edges: bin k holds e[k] <= d2 < e[k + 1], e[m] the product (m dr)(m dr) in double
+std::vector<double> sq_edges(double r_max, int nbins) {
+  const double dr = r_max / nbins;
+  std::vector<double> edges2((size_t)nbins + 1);
+  for (int m = 0; m <= nbins; ++m) edges2[m] = (m * dr) * (m * dr);
+  return edges2;
+}
+
+// ---------------------------------------------------------------- scratch groups
+// dalloc, recorded in the layer's group
+template <typename T>
+int salloc(kmc_sim* s, Scratch& g, T** p, size_t n) {
+  const int rc = dalloc(s, p, n);
+  if (rc == KMC_OK) g.ptrs.push_back(*p);
+  return rc;
+}
+
+// frees what the group holds (dfree: the handle's list forgets the buffers too)
+void scratch_free(kmc_sim* s, Scratch& g) {
+  for (void*& v : g.ptrs) dfree(s, v);
+  g.ptrs.clear();
+}
+
+// ---------------------------------------------------------------- calls and recorders
+int an_check(kmc_sim* s) {
+  if (!s->have_state) return fail(s, KMC_ERR_ARG, "analysis: no state");
+  if (s->K.dd) return fail(s, KMC_ERR_ARG, "analysis: a decomposed window is not analysed");
+  return KMC_OK;
+}
+
+// HIP events around one call's device work on the handle's stream
+int an_begin(kmc_sim* s) {
+  for (auto& e : s->an_ev)
+    if (!e) HIPCHK(s, hipEventCreate(&e));
+  HIPCHK(s, hipEventRecord(s->an_ev[0], s->stream));
+  return KMC_OK;
+}
+int an_end(kmc_sim* s) {
+  HIPCHK(s, hipEventRecord(s->an_ev[1], s->stream));
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  float ms = 0;
+  HIPCHK(s, hipEventElapsedTime(&ms, s->an_ev[0], s->an_ev[1]));
+  s->an_ms = ms;
+  return KMC_OK;
+}
+
+// a recorder's call other than its begin: `off` is the layer's "not begun" message
+int rec_check(kmc_sim* s, const Recorder& r, const char* off) {
+  const int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  if (!r.on) return fail(s, KMC_ERR_ARG, off);
+  return KMC_OK;
+}
+
+// the layer's scratch is freed and its state starts over: a begin's way out
+// when an allocation failed, and, after the stream's work, a recorder's end
+template <typename State>
+void scratch_drop(kmc_sim* s, State& st) {
+  scratch_free(s, st.scratch);
+  st = State{};
+}
+template <typename State>
+int rec_end(kmc_sim* s, State& st) {
+  if (s->stream) HIPCHK(s, hipStreamSynchronize(s->stream));
+  scratch_drop(s, st);
+  return KMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---------------------------------------------------------------- analysis
+// kmc_analysis.hip: components with the census, pair counts.
+
+// labels (0-based roots, reference order) and the roots' member counts, left
+// on the device; the stream is not waited for
+static int an_components(kmc_sim* s) {
+  const int N = s->K.N, NA = s->K.NA;
+  if (!s->an.out) {
+    int rc = KMC_OK;
+    rc |= dalloc(s, &s->an.parent, (size_t)N);
+    rc |= dalloc(s, &s->an.label, (size_t)N);
+    rc |= dalloc(s, &s->an.cnt, (size_t)N);
+    if (!s->an.hist) rc |= dalloc(s, &s->an.hist, (size_t)AN_HIST_MAX);
+    rc |= dalloc(s, &s->an.out, 1);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "analysis: scratch allocation failed");
+  }
+  hipStream_t st = s->stream;
+  const unsigned g = (unsigned)((N + AN_T - 1) / AN_T);
+  HIPCHK(s, hipMemsetAsync(s->an.out, 0, sizeof(AnOut), st));
+  if (g) {
+    k_an_init<<<g, AN_T, 0, st>>>(s->an.parent, s->an.cnt, N);
+    k_an_hook<<<g, AN_T, 0, st>>>(s->K, s->d, s->an.parent, s->an.out);
+    k_an_flatten<<<g, AN_T, 0, st>>>(s->an.parent, s->an.label, N, s->an.out);
+    k_an_count<<<g, AN_T, 0, st>>>(s->an.label, s->an.cnt, NA, N);
+  }
+  HIPCHK(s, hipGetLastError());
+  return KMC_OK;
+}
+
+int kmc_components(kmc_sim* s, int32_t* label) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = an_components(s);
+  if (rc == KMC_OK) rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  AnOut o;
+  HIPCHK(s, hipMemcpy(&o, s->an.out, sizeof o, hipMemcpyDeviceToHost));
+  if (o.err) return fail(s, KMC_ERR_STATE, "analysis: a bond link leaves the state or the link chains do not end");
+  if (label) {
+    HIPCHK(s, hipMemcpy(label, s->an.label, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    for (int i = 0; i < N; ++i) label[i] += 1;
+  }
+  return KMC_OK;
+}
+
+int kmc_oligomer_census(kmc_sim* s, int32_t max_r, int32_t max_l, int64_t* hist, kmc_census* out) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out || max_r < 0 || max_l < 0) return fail(s, KMC_ERR_ARG, "census: out is needed, max_r and max_l >= 0");
+  const int64_t nbin = hist ? ((int64_t)max_r + 1) * ((int64_t)max_l + 1) : 0;
+  if (nbin > AN_HIST_MAX)
+    return fail(s, KMC_ERR_ARG, "census: more than " + std::to_string(AN_HIST_MAX) + " bins (larger counts clamp into the last row / column)");
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = an_components(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  hipStream_t st = s->stream;
+  if (nbin) HIPCHK(s, hipMemsetAsync(s->an.hist, 0, sizeof(unsigned long long) * (size_t)nbin, st));
+  const unsigned g = (unsigned)std::min<int64_t>(AN_WG_MAX, ((int64_t)N + AN_T - 1) / AN_T);
+  if (g)
+    k_an_census<<<g, AN_T, sizeof(unsigned long long) * (size_t)(nbin + 5), st>>>(
+        s->an.label, s->an.cnt, N, max_r, max_l, nbin ? s->an.hist : nullptr, s->an.out);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  AnOut o;
+  HIPCHK(s, hipMemcpy(&o, s->an.out, sizeof o, hipMemcpyDeviceToHost));
+  if (o.err) return fail(s, KMC_ERR_STATE, "analysis: a bond link leaves the state or the link chains do not end");
+  std::memset(out, 0, sizeof *out);
+  out->n_components = (int64_t)o.n_components;
+  out->n_complexes = (int64_t)o.n_complexes;
+  out->proteins_in_complexes = (int64_t)o.proteins_in_complexes;
+  out->n_cis_dimers = (int64_t)o.n_cis_dimers;
+  if (o.n_components) {
+    const uint32_t root = 0xffffffffu - (uint32_t)o.best;
+    unsigned long long c = 0;
+    HIPCHK(s, hipMemcpy(&c, s->an.cnt + root, sizeof c, hipMemcpyDeviceToHost));
+    out->max_size = (int32_t)(o.best >> 32);
+    out->max_receptors = (int32_t)(uint32_t)c;
+    out->max_ligands = (int32_t)(c >> 32);
+    out->max_label = (int32_t)root + 1;
+  }
+  if (nbin) HIPCHK(s, hipMemcpy(hist, s->an.hist, sizeof(int64_t) * (size_t)nbin, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_pair_counts(kmc_sim* s, int32_t which, double r_max, int32_t nbins, int64_t* counts) {
+  if (!s) return KMC_ERR_ARG;
+  if (!counts || which < KMC_PAIR_AA || which > KMC_PAIR_BB || !(r_max > 0.0) || !std::isfinite(r_max) || nbins < 1 ||
+      nbins > AN_HIST_MAX)
+    return fail(s, KMC_ERR_ARG, "pair counts: which 0..2, r_max > 0, 1 <= nbins <= " + std::to_string(AN_HIST_MAX));
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const KParams& K = s->K;
+  const double fx = std::floor(K.box_x / r_max), fy = std::floor(K.box_y / r_max);
+  if (!(fx >= 3.0) || !(fy >= 3.0))
+    return fail(s, KMC_ERR_ARG, "pair counts: r_max above a third of the box (fewer than 3 cells along an axis)");
+  AnGrid G;
+  G.ncx = (int)std::min<double>(fx, AN_NC_MAX);
+  G.ncy = (int)std::min<double>(fy, AN_NC_MAX);
+  G.box_x = K.box_x;
+  G.box_y = K.box_y;
+  G.nsets = which == KMC_PAIR_AB ? 2 : 1;
+  G.lo[0] = which == KMC_PAIR_BB ? K.NA : 0;
+  G.hi[0] = which == KMC_PAIR_BB ? K.N : K.NA;
+  G.lo[1] = K.NA;
+  G.hi[1] = K.N;
+  const int N = K.N, ncell = G.ncx * G.ncy, npts = (G.hi[0] - G.lo[0]) + (G.nsets > 1 ? G.hi[1] - G.lo[1] : 0);
+  const size_t ncnt = (size_t)G.nsets * ncell + 1;  // the scan's last entry is the number of points
+  if (!s->an.pts) {
+    rc = KMC_OK;
+    rc |= dalloc(s, &s->an.cell, (size_t)N);
+    rc |= dalloc(s, &s->an.rank, (size_t)N);
+    rc |= dalloc(s, &s->an.pts, (size_t)N);
+    rc |= dalloc(s, &s->an.edges, (size_t)AN_HIST_MAX + 1);
+    if (!s->an.hist) rc |= dalloc(s, &s->an.hist, (size_t)AN_HIST_MAX);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "analysis: scratch allocation failed");
+  }
+  rc = bins_reserve(s, s->an.bins, ncnt, "analysis");
+  if (rc != KMC_OK) return rc;
+  const double dr = r_max / nbins;
+  const std::vector<double> edges2 = sq_edges(r_max, nbins);
+  hipStream_t st = s->stream;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpyAsync(s->an.edges, edges2.data(), sizeof(double) * edges2.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemsetAsync(s->an.hist, 0, sizeof(unsigned long long) * (size_t)nbins, st));
+  HIPCHK(s, hipMemsetAsync(s->an.bins.ccnt, 0, sizeof(int32_t) * ncnt, st));
+  if (npts > 0) {
+    const unsigned g = (unsigned)((npts + AN_T - 1) / AN_T);
+    k_an_cell_count<<<g, AN_T, 0, st>>>(s->K, s->d, G, s->an.bins.ccnt, s->an.cell, s->an.rank);
+    bins_scan(s, s->an.bins.ccnt, s->an.bins.cstart, (int)ncnt, s->an.bins.part);
+    k_an_cell_scatter<<<g, AN_T, 0, st>>>(s->K, s->d, G, s->an.bins.cstart, s->an.cell, s->an.rank, s->an.pts);
+    const size_t lds = sizeof(unsigned long long) * (size_t)nbins + 2 * sizeof(double2) * (size_t)s->an.chunk;
+    k_an_pairs<<<(unsigned)std::min(ncell, AN_WG_MAX), AN_T, lds, st>>>(
+        G, s->an.bins.cstart, s->an.pts, s->an.edges, nbins, (float)(1.0 / dr), s->an.chunk, s->an.hist);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);  // (waits: edges2 is read by the copy until here)
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpy(counts, s->an.hist, sizeof(int64_t) * (size_t)nbins, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+double kmc_analysis_ms(const kmc_sim* s) { return s ? s->an_ms : 0.0; }
+
+// ---------------------------------------------------------------- cluster geometry
+// kmc_geometry.hip: read-only like the analysis above, on scratch of its own.
+
+static_assert(sizeof(kmc_geom_bin) == sizeof(unsigned long long) * GEO_BIN, "a table bin is GEO_BIN words");
+static_assert(sizeof(kmc_cluster) == 80, "kmc_cluster layout");
+static_assert(KMC_GEOM_MAX_SIZE == GEO_MAX_SIZE, "kmc.h and kmc_geometry.hip agree on the table limit");
+
+// labels, image shifts, spanning bits, member counts and moments by root, left
+// on the device (five launches); the stream is not waited for
+static int geo_run(kmc_sim* s) {
+  const int N = s->K.N, NA = s->K.NA;
+  if (!s->geo.out) {
+    int rc = KMC_OK;
+    rc |= dalloc(s, &s->geo.word, (size_t)N);
+    rc |= dalloc(s, &s->geo.cnt, (size_t)N);
+    rc |= dalloc(s, &s->geo.acc, (size_t)N * GEO_ACC);
+    rc |= dalloc(s, &s->geo.table, (size_t)(GEO_MAX_SIZE + 1) * GEO_BIN);
+    rc |= dalloc(s, &s->geo.X, (size_t)N);
+    rc |= dalloc(s, &s->geo.label, (size_t)N);
+    rc |= dalloc(s, &s->geo.off, (size_t)N);
+    rc |= dalloc(s, &s->geo.span, (size_t)N);
+    rc |= dalloc(s, &s->geo.out, 1);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "geometry: scratch allocation failed");
+  }
+  hipStream_t st = s->stream;
+  const unsigned g = (unsigned)((N + AN_T - 1) / AN_T);
+  const long long BX = (long long)kmcm::round_(s->K.box_x * 1024.0), BY = (long long)kmcm::round_(s->K.box_y * 1024.0);
+  HIPCHK(s, hipMemsetAsync(s->geo.out, 0, sizeof(GeoOut), st));
+  if (g) {
+    k_geo_init<<<g, AN_T, 0, st>>>(s->K, s->d, s->geo.word, s->geo.X, s->geo.cnt, s->geo.span, s->geo.acc);
+    k_geo_hook<<<g, AN_T, 0, st>>>(s->K, s->d, s->geo.word, s->geo.out);
+    k_geo_flatten<<<g, AN_T, 0, st>>>(s->geo.word, s->geo.label, s->geo.off, s->geo.cnt, NA, N, s->geo.out);
+    k_geo_check<<<g, AN_T, 0, st>>>(s->K, s->d, s->geo.label, s->geo.off, s->geo.span, s->geo.out);
+    k_geo_moments<<<g, AN_T, 0, st>>>(s->geo.label, s->geo.off, s->geo.X, s->geo.span, BX, BY, N, s->geo.acc);
+  }
+  HIPCHK(s, hipGetLastError());
+  return KMC_OK;
+}
+
+// the device's verdict of the last geometry call
+static int geo_result(kmc_sim* s, GeoOut* o) {
+  HIPCHK(s, hipMemcpy(o, s->geo.out, sizeof *o, hipMemcpyDeviceToHost));
+  if (o->err & 1u)
+    return fail(s, KMC_ERR_STATE, "geometry: a bond link leaves the state or the link chains do not end");
+  if (o->err & 2u) return fail(s, KMC_ERR_CAPACITY, "geometry: an image shift leaves [-32767, 32767]");
+  return KMC_OK;
+}
+
+int kmc_unwrap(kmc_sim* s, int32_t* label, int32_t* shift, uint8_t* span) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = geo_run(s);
+  if (rc == KMC_OK) rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  GeoOut o;
+  rc = geo_result(s, &o);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  std::vector<int32_t> lab(N);
+  std::vector<uint32_t> sp(N);
+  HIPCHK(s, hipMemcpy(lab.data(), s->geo.label, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(sp.data(), s->geo.span, sizeof(uint32_t) * N, hipMemcpyDeviceToHost));
+  if (shift) {
+    std::vector<int2> off(N);
+    HIPCHK(s, hipMemcpy(off.data(), s->geo.off, sizeof(int2) * N, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N; ++i) {
+      const bool wraps = sp[lab[i]] != 0;  // (its offsets depend on the tree: not reported)
+      shift[i] = wraps ? 0 : off[i].x;
+      shift[N + i] = wraps ? 0 : off[i].y;
+    }
+  }
+  if (span)
+    for (size_t i = 0; i < N; ++i) span[i] = (uint8_t)sp[lab[i]];
+  if (label)
+    for (size_t i = 0; i < N; ++i) label[i] = lab[i] + 1;
+  return KMC_OK;
+}
+
+int kmc_cluster_geometry(kmc_sim* s, int32_t max_size, kmc_geom_bin* table, kmc_geom* out) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out || max_size < 2 || max_size > GEO_MAX_SIZE)
+    return fail(s, KMC_ERR_ARG, "cluster geometry: out is needed, 2 <= max_size <= " + std::to_string(GEO_MAX_SIZE) +
+                                    " (larger clusters clamp into the last bin)");
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = geo_run(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  const size_t nbin = table ? (size_t)max_size + 1 : 0;
+  hipStream_t st = s->stream;
+  if (nbin) HIPCHK(s, hipMemsetAsync(s->geo.table, 0, sizeof(kmc_geom_bin) * nbin, st));
+  const unsigned g = (unsigned)std::min<int64_t>(GEO_TABLE_WG, ((int64_t)N + AN_T - 1) / AN_T);
+  if (g)
+    k_geo_table<<<g, AN_T, sizeof(unsigned long long) * (nbin * GEO_BIN + 6), st>>>(
+        s->geo.label, s->geo.cnt, s->geo.span, s->geo.acc, N, max_size, nbin ? s->geo.table : nullptr, s->geo.out);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  GeoOut o;
+  rc = geo_result(s, &o);
+  if (rc != KMC_OK) return rc;
+  std::memset(out, 0, sizeof *out);
+  out->n_measured = (int64_t)o.n_measured;
+  out->n_spanning = (int64_t)o.n_spanning;
+  out->n_span_x = (int64_t)o.n_span_x;
+  out->n_span_y = (int64_t)o.n_span_y;
+  out->proteins_in_spanning = (int64_t)o.proteins_in_spanning;
+  if (o.best) {
+    const uint32_t root = 0xffffffffu - (uint32_t)o.best;
+    uint32_t sp = 0;
+    HIPCHK(s, hipMemcpy(&sp, s->geo.span + root, sizeof sp, hipMemcpyDeviceToHost));
+    out->largest_label = (int32_t)root + 1;
+    out->largest_size = (int32_t)(o.best >> 32);
+    out->largest_span = (int32_t)sp;
+  }
+  if (nbin) HIPCHK(s, hipMemcpy(table, s->geo.table, sizeof(kmc_geom_bin) * nbin, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_cluster_list(kmc_sim* s, int32_t min_size, int64_t cap, kmc_cluster* rows, int64_t* n) {
+  if (!s) return KMC_ERR_ARG;
+  if (!n || min_size < 2 || cap < 0 || (cap > 0 && !rows))
+    return fail(s, KMC_ERR_ARG, "cluster list: n is needed, min_size >= 2, cap >= 0, rows for cap > 0");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  // no more than N / min_size roots can qualify: a larger cap needs no larger buffer
+  const size_t dcap = (size_t)std::min<int64_t>(cap, N / min_size);
+  if (dcap > s->geo.rows_cap) {
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    dfree(s, s->geo.rows);
+    s->geo.rows_cap = 0;
+    if (dalloc(s, &s->geo.rows, dcap) != KMC_OK) return fail(s, KMC_ERR_HIP, "geometry: scratch allocation failed");
+    s->geo.rows_cap = dcap;
+  }
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = geo_run(s);
+  if (rc != KMC_OK) return rc;
+  const unsigned g = (unsigned)((N + AN_T - 1) / AN_T);
+  if (g)
+    k_geo_list<<<g, AN_T, 0, s->stream>>>(s->geo.label, s->geo.cnt, s->geo.span, s->geo.acc, N, min_size,
+                                          (long long)dcap, s->geo.rows, s->geo.out);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  GeoOut o;
+  rc = geo_result(s, &o);
+  if (rc != KMC_OK) return rc;
+  *n = (int64_t)o.n_rows;
+  if (*n > cap)
+    return fail(s, KMC_ERR_CAPACITY, "cluster list: " + std::to_string(*n) + " components qualify, cap is " +
+                                         std::to_string(cap));
+  if (*n) {
+    HIPCHK(s, hipMemcpy(rows, s->geo.rows, sizeof(kmc_cluster) * (size_t)*n, hipMemcpyDeviceToHost));
+    std::sort(rows, rows + *n, [](const kmc_cluster& a, const kmc_cluster& b) { return a.label < b.label; });
+  }
+  return KMC_OK;
+}
+
+// ---------------------------------------------------------------- structure factor
+// kmc_structure.hip: read-only like the analysis above, one launch on scratch of its own.
+
+static_assert(KMC_SK_MAX == SK_MAX, "kmc.h and kmc_structure.h agree on the grid limit");
+#define SK_NQ_MAX ((SK_MAX + 1) * (2 * SK_MAX + 1))
+
+int kmc_structure_factor(kmc_sim* s, int32_t hmax, int32_t kmax, int32_t select, int64_t* sums, int64_t n_sel[2]) {
+  if (!s) return KMC_ERR_ARG;
+  if (!sums || !n_sel || hmax < 0 || hmax > SK_MAX || kmax < 0 || kmax > SK_MAX ||
+      (select != KMC_SK_ALL && select != KMC_SK_BOUND))
+    return fail(s, KMC_ERR_ARG, "structure factor: sums and n_sel are needed, 0 <= hmax, kmax <= " +
+                                    std::to_string(SK_MAX) + ", select is KMC_SK_ALL or KMC_SK_BOUND");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  SkArgs a;
+  a.hmax = hmax;
+  a.kmax = kmax;
+  a.select = select;
+  a.W = 2 * kmax + 1;
+  a.nq = (hmax + 1) * a.W;
+  const int nqb = (a.nq + SK_QB - 1) / SK_QB;
+  a.qb = (a.nq + nqb - 1) / nqb;
+  a.nh_max = std::min(hmax + 1, (a.qb - 1) / a.W + 2);
+  a.E = a.nh_max + kmax + 1;
+  a.BX = (long long)kmcm::round_(s->K.box_x * 1024.0);
+  a.BY = (long long)kmcm::round_(s->K.box_y * 1024.0);
+  if (a.BX < 1 || a.BY < 1) return fail(s, KMC_ERR_ARG, "structure factor: the box is below 2^-10 A");
+  if (a.E > SK_E_MAX) return fail(s, KMC_ERR_CAPACITY, "structure factor: axis tables beyond SK_E_MAX");
+  if (!s->sk.sums && dalloc(s, &s->sk.sums, (size_t)4 * SK_NQ_MAX + 2) != KMC_OK)
+    return fail(s, KMC_ERR_HIP, "structure factor: scratch allocation failed");
+  const size_t nw = (size_t)4 * a.nq;
+  unsigned long long* d_nsel = s->sk.sums + (size_t)4 * SK_NQ_MAX;
+  const int ntile = (std::max(s->K.NA, s->K.NB) + SK_TILE - 1) / SK_TILE;
+  const dim3 grid((unsigned)std::max(1, std::min(ntile, SK_WG / nqb)), (unsigned)nqb);
+  const size_t lds = (sizeof(double2) * (size_t)SK_TILE * a.E + sizeof(longlong2) * SK_TILE + sizeof(int) * (SK_TILE + 1) + 15) / 16 * 16;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  hipStream_t st = s->stream;
+  HIPCHK(s, hipMemsetAsync(s->sk.sums, 0, sizeof(unsigned long long) * nw, st));
+  HIPCHK(s, hipMemsetAsync(d_nsel, 0, sizeof(unsigned long long) * 2, st));
+  k_sk_sums<<<grid, SK_T, lds, st>>>(s->K, s->d, a, s->sk.sums, d_nsel);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpy(sums, s->sk.sums, sizeof(int64_t) * nw, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(n_sel, d_nsel, sizeof(int64_t) * 2, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+// ---------------------------------------------------------------- bond-orientational order
+// kmc_bondorder.hip: read-only like the analysis above, on scratch of its own.
+
+static_assert(KMC_BO_MAX_FOLD == BO_MAX_FOLD && KMC_BO_NN_ROWS == BO_NN_ROWS, "kmc.h and kmc_bondorder.h agree");
+static_assert(sizeof(kmc_bond_order_out) == 6 * sizeof(unsigned long long), "kmc_bond_order_out is BoOut's six sums");
+
+// a workgroup's dynamic LDS beyond the 64 KiB every launch may ask for (the CU has 160 KiB)
+static void bo_lds_limit(const void* kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    (void)hipGetLastError();  // the launch itself reports what it cannot have
+}
+
+// the arguments both calls share, checked and turned into the kernels'; the scratch of the first call
+static int bo_setup(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select, BoArgs* a) {
+  if ((which != KMC_BO_A && which != KMC_BO_B) || (mode != KMC_BO_WITHIN && mode != KMC_BO_LINKED) || fold < 1 ||
+      fold > BO_MAX_FOLD || (select != KMC_BO_ALL && select != KMC_BO_BOUND) ||
+      (mode == KMC_BO_LINKED && which != KMC_BO_B))
+    return fail(s, KMC_ERR_ARG, "bond order: which 0 or 1, mode 0 or 1 (linked: ligands only), 1 <= fold <= " +
+                                    std::to_string(BO_MAX_FOLD) + ", select 0 or 1");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const KParams& K = s->K;
+  const double bx = kmcm::round_(K.box_x * 1024.0), by = kmcm::round_(K.box_y * 1024.0);
+  if (!(bx >= 1.0) || !(by >= 1.0) || !(bx < (double)BO_BOX_MAX) || !(by < (double)BO_BOX_MAX))
+    return fail(s, KMC_ERR_ARG, "bond order: the box is below 2^-10 A or not below 2^21 A");
+  a->which = which;
+  a->mode = mode;
+  a->fold = fold;
+  a->select = select;
+  a->base = which == KMC_BO_A ? 0 : K.NA;
+  a->n = which == KMC_BO_A ? K.NA : K.NB;
+  a->BX = (long long)bx;
+  a->BY = (long long)by;
+  a->RC2 = 0;
+  a->ncx = a->ncy = 0;
+  if (mode == KMC_BO_WITHIN) {
+    const long long RC =
+        r_cut > 0.0 && r_cut * 1024.0 < (double)BO_BOX_MAX ? (long long)kmcm::round_(r_cut * 1024.0) : 0;
+    if (RC < 1 || a->BX / RC < 3 || a->BY / RC < 3)
+      return fail(s, KMC_ERR_ARG, "bond order: r_cut must be positive and at most a third of the box (3 cells along an axis)");
+    a->RC2 = RC * RC;
+    a->ncx = (int)std::min<long long>(a->BX / RC, BO_NC_MAX);
+    a->ncy = (int)std::min<long long>(a->BY / RC, BO_NC_MAX);
+  }
+  if (!s->bo.out) {
+    const size_t n = (size_t)std::max(K.NA, K.NB);
+    rc = KMC_OK;
+    rc |= dalloc(s, &s->bo.cell, n);
+    rc |= dalloc(s, &s->bo.rank, n);
+    rc |= dalloc(s, &s->bo.ref, n);
+    rc |= dalloc(s, &s->bo.nn, n);
+    rc |= dalloc(s, &s->bo.pts, n);
+    rc |= dalloc(s, &s->bo.pcs, n);
+    rc |= dalloc(s, &s->bo.pcs_sorted, n);
+    rc |= dalloc(s, &s->bo.C, n);
+    rc |= dalloc(s, &s->bo.S, n);
+    rc |= dalloc(s, &s->bo.hist, (size_t)BO_NN_ROWS * BO_HIST_BINS);
+    rc |= dalloc(s, &s->bo.corr, (size_t)2 * BO_CORR_BINS);
+    rc |= dalloc(s, &s->bo.E2, (size_t)BO_CORR_BINS + 1);
+    rc |= dalloc(s, &s->bo.out, 1);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "bond order: scratch allocation failed");
+  }
+  return KMC_OK;
+}
+
+// the set binned on the grid a->ncx x a->ncy (nn_filter: only the proteins with neighbours, with their (pc, ps))
+static int bo_grid(kmc_sim* s, const BoArgs& a, bool corr_grid) {
+  const size_t ncnt = (size_t)a.ncx * a.ncy + 1;  // the scan's last entry is the number of binned points
+  const int rc = bins_reserve(s, s->bo.bins, ncnt, "bond order");
+  if (rc != KMC_OK) return rc;
+  hipStream_t st = s->stream;
+  HIPCHK(s, hipMemsetAsync(s->bo.bins.ccnt, 0, sizeof(int32_t) * ncnt, st));
+  const unsigned g = (unsigned)((a.n + BO_T - 1) / BO_T);
+  if (g)
+    k_bo_cell_count<<<g, BO_T, 0, st>>>(s->K, s->d, a, corr_grid ? s->bo.nn : nullptr, s->bo.bins.ccnt, s->bo.cell,
+                                        s->bo.rank, s->bo.out);
+  bins_scan(s, s->bo.bins.ccnt, s->bo.bins.cstart, (int)ncnt, s->bo.bins.part);
+  if (g)
+    k_bo_cell_scatter<<<g, BO_T, 0, st>>>(s->K, s->d, a, s->bo.bins.cstart, s->bo.cell, s->bo.rank, s->bo.pts,
+                                          s->bo.ref, corr_grid ? s->bo.pcs : nullptr, s->bo.pcs_sorted);
+  HIPCHK(s, hipGetLastError());
+  return KMC_OK;
+}
+
+// the local pass and the reduce, left on the device: (C, S, N) and (pc, ps) by reference index, the six sums and,
+// for nbins > 0, the histogram.  The stream is not waited for.
+static int bo_local(kmc_sim* s, const BoArgs& a, int nbins) {
+  hipStream_t st = s->stream;
+  const size_t n = (size_t)a.n;
+  HIPCHK(s, hipMemsetAsync(s->bo.out, 0, sizeof(BoOut), st));
+  HIPCHK(s, hipMemsetAsync(s->bo.C, 0, sizeof(unsigned long long) * n, st));
+  HIPCHK(s, hipMemsetAsync(s->bo.S, 0, sizeof(unsigned long long) * n, st));
+  HIPCHK(s, hipMemsetAsync(s->bo.nn, 0xff, sizeof(int32_t) * n, st));  // -1: outside the set until a centre writes its count
+  if (nbins) HIPCHK(s, hipMemsetAsync(s->bo.hist, 0, sizeof(unsigned long long) * (size_t)BO_NN_ROWS * nbins, st));
+  if (a.n == 0) return KMC_OK;
+  if (a.mode == KMC_BO_WITHIN) {
+    const int rc = bo_grid(s, a, false);
+    if (rc != KMC_OK) return rc;
+    const unsigned g = (unsigned)std::min<int64_t>(4 * BO_WG_MAX, ((int64_t)a.n + BO_T - 1) / BO_T);
+    k_bo_local_queue<<<g, BO_T, 0, st>>>(a, s->bo.bins.cstart, s->bo.pts, s->bo.ref, s->bo.C, s->bo.S, s->bo.nn);
+  } else {
+    k_bo_local_linked<<<(unsigned)((a.n + BO_T - 1) / BO_T), BO_T, 0, st>>>(s->K, s->d, a, s->bo.C, s->bo.S, s->bo.nn,
+                                                                            s->bo.out);
+  }
+  const size_t lds = sizeof(unsigned long long) * (6 + (size_t)BO_NN_ROWS * nbins);
+  bo_lds_limit((const void*)k_bo_reduce, lds);
+  const unsigned g = (unsigned)std::min<int64_t>(nbins > 64 ? 256 : BO_WG_MAX, ((int64_t)a.n + BO_T - 1) / BO_T);
+  k_bo_reduce<<<g, BO_T, lds, st>>>(a.n, nbins, s->bo.C, s->bo.S, s->bo.nn, s->bo.pcs, nbins ? s->bo.hist : nullptr,
+                                    s->bo.out);
+  HIPCHK(s, hipGetLastError());
+  return KMC_OK;
+}
+
+static int bo_result(kmc_sim* s, BoOut* o) {
+  HIPCHK(s, hipMemcpy(o, s->bo.out, sizeof *o, hipMemcpyDeviceToHost));
+  if (o->err & 1u) return fail(s, KMC_ERR_STATE, "bond order: a bond link leaves the state");
+  if (o->err & 2u) return fail(s, KMC_ERR_CAPACITY, "bond order: a protein with more than 65535 neighbours");
+  return KMC_OK;
+}
+
+int kmc_bond_order(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select, int32_t nbins,
+                   int64_t* hist, kmc_bond_order_out* out, int64_t* C, int64_t* S, int32_t* nn) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out || nbins < 1 || nbins > BO_HIST_BINS)
+    return fail(s, KMC_ERR_ARG, "bond order: out is needed, 1 <= nbins <= " + std::to_string(BO_HIST_BINS));
+  BoArgs a;
+  int rc = bo_setup(s, which, mode, fold, r_cut, select, &a);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = bo_local(s, a, hist ? nbins : 0);
+  if (rc == KMC_OK) rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  BoOut o;
+  rc = bo_result(s, &o);
+  if (rc != KMC_OK) return rc;
+  std::memcpy(out, o.sum, sizeof *out);
+  const size_t n = (size_t)a.n;
+  if (hist) HIPCHK(s, hipMemcpy(hist, s->bo.hist, sizeof(int64_t) * (size_t)BO_NN_ROWS * nbins, hipMemcpyDeviceToHost));
+  if (C && n) HIPCHK(s, hipMemcpy(C, s->bo.C, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+  if (S && n) HIPCHK(s, hipMemcpy(S, s->bo.S, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+  if (nn && n) {
+    HIPCHK(s, hipMemcpy(nn, s->bo.nn, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i)
+      if (nn[i] < 0) nn[i] = 0;  // outside the set
+  }
+  return KMC_OK;
+}
+
+int kmc_bond_order_corr(kmc_sim* s, int32_t which, int32_t mode, int32_t fold, double r_cut, int32_t select,
+                        double r_max, int32_t nbins, int64_t* corr) {
+  if (!s) return KMC_ERR_ARG;
+  if (!corr || nbins < 1 || nbins > BO_CORR_BINS || !(r_max > 0.0) || !std::isfinite(r_max))
+    return fail(s, KMC_ERR_ARG, "bond order: corr is needed, r_max > 0, 1 <= nbins <= " + std::to_string(BO_CORR_BINS));
+  BoArgs a;
+  int rc = bo_setup(s, which, mode, fold, r_cut, select, &a);
+  if (rc != KMC_OK) return rc;
+  const double dr = r_max / nbins;
+  const int64_t EN = r_max * 1024.0 < (double)BO_BOX_MAX ? kmcb::corr_edge(nbins, dr) : 0;
+  if (EN < 1 || !(std::floor(s->K.box_x / r_max) >= 3.0) || !(std::floor(s->K.box_y / r_max) >= 3.0) ||
+      a.BX / EN < 3 || a.BY / EN < 3)
+    return fail(s, KMC_ERR_ARG, "bond order: r_max must be at least 2^-10 A and at most a third of the box (3 cells along an axis)");
+  std::vector<int64_t> E2((size_t)nbins + 1);
+  for (int m = 0; m <= nbins; ++m) {
+    const int64_t e = kmcb::corr_edge(m, dr);
+    E2[m] = e * e;
+  }
+  hipStream_t st = s->stream;
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = bo_local(s, a, 0);
+  if (rc != KMC_OK) return rc;
+  BoOut o;
+  HIPCHK(s, hipStreamSynchronize(st));
+  rc = bo_result(s, &o);  // a local pass that failed ends the call before the pair walk
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpyAsync(s->bo.E2, E2.data(), sizeof(int64_t) * E2.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemsetAsync(s->bo.corr, 0, sizeof(unsigned long long) * 2 * (size_t)nbins, st));
+  if (a.n > 0) {
+    BoArgs g = a;  // the second grid: cells no narrower than the last edge
+    g.ncx = (int)std::min<int64_t>(a.BX / EN, BO_NC_MAX);
+    g.ncy = (int)std::min<int64_t>(a.BY / EN, BO_NC_MAX);
+    rc = bo_grid(s, g, true);
+    if (rc != KMC_OK) return rc;
+    const size_t lds = 48 * (size_t)s->bo.chunk + sizeof(unsigned long long) * 2 * (size_t)nbins;
+    bo_lds_limit((const void*)k_bo_corr, lds);
+    k_bo_corr<<<(unsigned)std::min(g.ncx * g.ncy, BO_WG_MAX), BO_T, lds, st>>>(
+        g, s->bo.bins.cstart, s->bo.pts, s->bo.pcs_sorted, s->bo.E2, nbins, (float)(1.0 / (dr * 1024.0)), s->bo.chunk,
+        s->bo.corr);
+    HIPCHK(s, hipGetLastError());
+  }
+  rc = an_end(s);  // (waits: E2 is read by the copy until here)
+  if (rc == KMC_OK) rc = bo_result(s, &o);  // the second grid's index check
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpy(corr, s->bo.corr, sizeof(int64_t) * 2 * (size_t)nbins, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+// ---------------------------------------------------------------- displacement tracking
+// kmc_dynamics.hip: the tracker is a layer of its own over the committed
+// state; its calls write only TrkState's buffers.
+
+static const char* const TRK_OFF = "track: no origin (kmc_track_begin; a new state drops the tracker)";
+
+int kmc_track_begin(kmc_sim* s, double max_jump) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const double half = 0.5 * std::min(s->K.box_x, s->K.box_y);
+  if (!(max_jump <= 0.0) && !(max_jump <= half))  // (a NaN fails both)
+    return fail(s, KMC_ERR_ARG, "track: max_jump above half the box (or not a number)");
+  const int N = s->K.N;
+  if (!s->trk.acc) {
+    const size_t nblk = ((size_t)N + TRK_T - 1) / TRK_T;
+    Scratch& g = s->trk.scratch;
+    rc = KMC_OK;
+    rc |= salloc(s, g, &s->trk.dev.prev, (size_t)N);
+    rc |= salloc(s, g, &s->trk.dev.u, (size_t)N);
+    rc |= salloc(s, g, &s->trk.dev.flags, (size_t)N);
+    rc |= salloc(s, g, &s->trk.dev.cls, (size_t)N);
+    rc |= salloc(s, g, &s->trk.dev.link0, 3 * (size_t)N);
+    rc |= salloc(s, g, &s->trk.out, 1);
+    rc |= salloc(s, g, &s->trk.part[0], TRK_NSUM * nblk);
+    rc |= salloc(s, g, &s->trk.part[1], TRK_NSUM * ((nblk + TRK_T - 1) / TRK_T));
+    rc |= salloc(s, g, &s->trk.edges, (size_t)TRK_BINS_MAX + 1);
+    rc |= salloc(s, g, &s->trk.vh, (size_t)TRK_CLASSES * TRK_BINS_MAX);
+    rc |= salloc(s, g, &s->trk.acc, 1);
+    if (rc != KMC_OK) {
+      scratch_drop(s, s->trk);
+      return fail(s, KMC_ERR_HIP, "track: scratch allocation failed");
+    }
+  }
+  s->trk.rec.on = false;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemsetAsync(s->trk.acc, 0, sizeof(TrkAcc), s->stream));
+  if (N > 0) k_trk_begin<<<(unsigned)((N + TRK_T - 1) / TRK_T), TRK_T, 0, s->stream>>>(s->K, s->d, s->trk.dev);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  s->trk.max_jump = max_jump <= 0.0 ? 0.5 * half : max_jump;
+  s->trk.rec = Recorder{true, s->step_done, s->step_done, 0};
+  return KMC_OK;
+}
+
+int kmc_track_update(kmc_sim* s, kmc_track_info* info) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = rec_check(s, s->trk.rec, TRK_OFF);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  // the maxima persist since begin; the flag counts are of this update
+  HIPCHK(s, hipMemsetAsync(&s->trk.acc->n_jumped, 0, 2 * sizeof(unsigned long long), s->stream));
+  if (N > 0)
+    k_trk_update<<<(unsigned)((N + TRK_T - 1) / TRK_T), TRK_T, 0, s->stream>>>(s->K, s->d, s->trk.dev, s->trk.max_jump,
+                                                                             s->trk.acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  s->trk.rec.last = s->step_done;
+  s->trk.rec.updates += 1;
+  if (info) {
+    TrkAcc a;
+    HIPCHK(s, hipMemcpy(&a, s->trk.acc, sizeof a, hipMemcpyDeviceToHost));
+    info->origin_step = s->trk.rec.origin;
+    info->last_step = s->trk.rec.last;
+    info->n_updates = s->trk.rec.updates;
+    std::memcpy(&info->max_dx, &a.max_dx, sizeof(double));
+    std::memcpy(&info->max_dy, &a.max_dy, sizeof(double));
+    info->n_jumped = (int64_t)a.n_jumped;
+    info->n_changed = (int64_t)a.n_changed;
+  }
+  return KMC_OK;
+}
+
+int kmc_track_sample(kmc_sim* s, double r_max, int32_t nbins, kmc_track_sample_t* out, int64_t* vanhove) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out || !(r_max > 0.0) || !std::isfinite(r_max) || nbins < 1 || nbins > TRK_BINS_MAX)
+    return fail(s, KMC_ERR_ARG, "track sample: out is needed, r_max > 0, 1 <= nbins <= " + std::to_string(TRK_BINS_MAX));
+  int rc = rec_check(s, s->trk.rec, TRK_OFF);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  const double dr = r_max / nbins;
+  const std::vector<double> edges2 = sq_edges(r_max, nbins);
+  hipStream_t st = s->stream;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpyAsync(s->trk.edges, edges2.data(), sizeof(double) * edges2.size(), hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemsetAsync(s->trk.out, 0, sizeof(TrkOut), st));
+  if (vanhove) HIPCHK(s, hipMemsetAsync(s->trk.vh, 0, sizeof(unsigned long long) * TRK_CLASSES * (size_t)nbins, st));
+  // level 1: blocks of 256 proteins -> part[0][s][nblk]; then the tree's next levels until one value per sum
+  int n = (N + TRK_T - 1) / TRK_T, cur = 0;
+  if (n > 0) {
+    const size_t lds = sizeof(unsigned long long) * (size_t)(TRK_NSUM * TRK_T + TRK_NCNT + (vanhove ? TRK_CLASSES * nbins : 0));
+    k_trk_sample<<<(unsigned)std::min(n, AN_WG_MAX), TRK_T, lds, st>>>(s->K, s->d, s->trk.dev, s->trk.edges, nbins,
+                                                                      (float)(1.0 / dr), vanhove ? s->trk.vh : nullptr, n,
+                                                                      s->trk.part[0], s->trk.out);
+    while (n > 1) {
+      const int nout = (n + TRK_T - 1) / TRK_T;
+      k_trk_tree<<<dim3((unsigned)nout, TRK_NSUM), TRK_T, 0, st>>>(s->trk.part[cur], n, s->trk.part[cur ^ 1], nout);
+      n = nout;
+      cur ^= 1;
+    }
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);  // (waits: edges2 is read by the copy until here)
+  if (rc != KMC_OK) return rc;
+  TrkOut o;
+  double sums[TRK_NSUM] = {0};
+  HIPCHK(s, hipMemcpy(&o, s->trk.out, sizeof o, hipMemcpyDeviceToHost));
+  if (n == 1) HIPCHK(s, hipMemcpy(sums, s->trk.part[cur], sizeof sums, hipMemcpyDeviceToHost));
+  std::memset(out, 0, sizeof *out);
+  out->origin_step = s->trk.rec.origin;
+  out->last_step = s->trk.rec.last;
+  for (int c = 0; c < TRK_CLASSES; ++c) {
+    out->n[c] = (int64_t)o.cnt[c];
+    out->n_clean[c] = (int64_t)o.cnt[TRK_CLASSES + c];
+    out->sum_u2[c] = sums[c];
+    out->sum_u2_clean[c] = sums[TRK_CLASSES + c];
+  }
+  out->rl0 = (int64_t)o.cnt[10];
+  out->rl_now = (int64_t)o.cnt[11];
+  out->rl_kept = (int64_t)o.cnt[12];
+  out->cis0 = (int64_t)o.cnt[13];
+  out->cis_now = (int64_t)o.cnt[14];
+  out->cis_kept = (int64_t)o.cnt[15];
+  if (vanhove)
+    HIPCHK(s, hipMemcpy(vanhove, s->trk.vh, sizeof(int64_t) * TRK_CLASSES * (size_t)nbins, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_track_displacements(kmc_sim* s, double* u, uint8_t* flags) {
+  if (!s) return KMC_ERR_ARG;
+  if (!u) return fail(s, KMC_ERR_ARG, "track displacements: u is needed");
+  const int rc = rec_check(s, s->trk.rec, TRK_OFF);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  std::vector<double2> h(N);
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  HIPCHK(s, hipMemcpy(h.data(), s->trk.dev.u, sizeof(double2) * N, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < N; ++i) {
+    u[i] = h[i].x;
+    u[N + i] = h[i].y;
+  }
+  if (flags) {
+    HIPCHK(s, hipMemcpy(flags, s->trk.dev.flags, N, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N; ++i) flags[i] &= (uint8_t)(KMC_TRACK_CHANGED | KMC_TRACK_JUMPED);
+  }
+  return KMC_OK;
+}
+
+int kmc_track_end(kmc_sim* s) {
+  return s ? rec_end(s, s->trk) : KMC_ERR_ARG;
+}
+
+// ---------------------------------------------------------------- bond kinetics
+// kmc_kinetics.hip: the recorder is a layer of its own over the committed
+// state, independent of the tracker; its calls write only KinState's buffers.
+
+static const char* const KIN_OFF = "kinetics: not begun (kmc_kin_begin; a new state drops the recorder)";
+
+// the counters of the call that just ran; a link out of range drops the recorder
+static int kin_result(kmc_sim* s, KinAcc* a) {
+  HIPCHK(s, hipMemcpy(a, s->kin.acc, sizeof *a, hipMemcpyDeviceToHost));
+  if (a->err) {
+    s->kin.rec.on = false;
+    return fail(s, KMC_ERR_STATE, "kinetics: a receptor's bond link leaves its range");
+  }
+  return KMC_OK;
+}
+
+static void kin_fill(const kmc_sim* s, const KinAcc& a, kmc_kin_out* out) {
+  std::memset(out, 0, sizeof *out);
+  out->origin_step = s->kin.rec.origin;
+  out->last_step = s->kin.rec.last;
+  out->n_updates = s->kin.rec.updates;
+  out->rl_on = (int64_t)a.ev[kmck::KIN_EV_RL_ON];
+  out->rl_off = (int64_t)a.ev[kmck::KIN_EV_RL_OFF];
+  out->rl_swap = (int64_t)a.ev[kmck::KIN_EV_RL_SWAP];
+  out->cis_on = (int64_t)a.ev[kmck::KIN_EV_CIS_ON];
+  out->cis_off_mono = (int64_t)a.ev[kmck::KIN_EV_CIS_OFF_MONO];
+  out->cis_off_cx = (int64_t)a.ev[kmck::KIN_EV_CIS_OFF_CX];
+  out->cis_swap = (int64_t)a.ev[kmck::KIN_EV_CIS_SWAP];
+  out->exp_rl = s->kin.exp[0];
+  out->exp_mono = s->kin.exp[1];
+  out->exp_cx = s->kin.exp[2];
+  out->exp_free_receptor = s->kin.exp[3];
+  out->exp_free_site = s->kin.exp[4];
+  out->occ_rl = s->kin.occ[0];
+  out->occ_mono = s->kin.occ[1];
+  out->occ_cx = s->kin.occ[2];
+  out->occ_free_receptor = (int64_t)s->p.n_a - s->kin.occ[0];
+  out->occ_free_site = 3 * (int64_t)s->p.n_b - s->kin.occ[0];
+}
+
+int kmc_kin_begin(kmc_sim* s) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const int NA = s->K.NA;
+  if (!s->kin.acc) {
+    Scratch& g = s->kin.scratch;
+    rc = KMC_OK;
+    rc |= salloc(s, g, &s->kin.dev.rl_lig, (size_t)NA);
+    rc |= salloc(s, g, &s->kin.dev.rl_site, (size_t)NA);
+    rc |= salloc(s, g, &s->kin.dev.cis_with, (size_t)NA);
+    rc |= salloc(s, g, &s->kin.dev.last_lig, (size_t)NA);
+    rc |= salloc(s, g, &s->kin.dev.rl_since, (size_t)NA);
+    rc |= salloc(s, g, &s->kin.dev.cis_since, (size_t)NA);
+    rc |= salloc(s, g, &s->kin.dev.free_since, (size_t)NA);
+    rc |= salloc(s, g, &s->kin.dev.bits, (size_t)NA);
+    rc |= salloc(s, g, &s->kin.hist, (size_t)KIN_HISTS * KIN_BINS);
+    rc |= salloc(s, g, &s->kin.acc, 1);
+    if (rc != KMC_OK) {
+      scratch_drop(s, s->kin);
+      return fail(s, KMC_ERR_HIP, "kinetics: scratch allocation failed");
+    }
+  }
+  s->kin.rec.on = false;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemsetAsync(s->kin.acc, 0, sizeof(KinAcc), s->stream));
+  HIPCHK(s, hipMemsetAsync(s->kin.hist, 0, sizeof(unsigned long long) * KIN_HISTS * KIN_BINS, s->stream));
+  if (NA > 0)
+    k_kin_begin<<<(unsigned)((NA + KIN_T - 1) / KIN_T), KIN_T, 0, s->stream>>>(s->K, s->d, s->kin.dev,
+                                                                              (long long)s->step_done, s->kin.acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  KinAcc a;
+  rc = kin_result(s, &a);
+  if (rc != KMC_OK) return rc;
+  s->kin.rec = Recorder{true, s->step_done, s->step_done, 0};
+  for (int k = 0; k < 3; ++k) s->kin.occ[k] = (int64_t)a.occ[k];
+  for (auto& e : s->kin.exp) e = 0;
+  return KMC_OK;
+}
+
+int kmc_kin_update(kmc_sim* s, kmc_kin_out* out) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = rec_check(s, s->kin.rec, KIN_OFF);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  const int NA = s->K.NA;
+  // the events persist since begin; the occupancy and the error flag are of this update
+  HIPCHK(s, hipMemsetAsync(s->kin.acc->occ, 0, sizeof(KinAcc) - offsetof(KinAcc, occ), s->stream));
+  if (NA > 0)
+    k_kin_update<<<(unsigned)((NA + KIN_T - 1) / KIN_T), KIN_T, 0, s->stream>>>(
+        s->K, s->d, s->kin.dev, (long long)s->step_done, s->kin.hist, s->kin.acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  // the occupancy is the next update's exposure: read back at every update
+  KinAcc a;
+  rc = kin_result(s, &a);
+  if (rc != KMC_OK) return rc;
+  const int64_t dt = s->step_done - s->kin.rec.last;
+  const int64_t prev[5] = {s->kin.occ[0], s->kin.occ[1], s->kin.occ[2], (int64_t)s->p.n_a - s->kin.occ[0],
+                           3 * (int64_t)s->p.n_b - s->kin.occ[0]};
+  for (int k = 0; k < 5; ++k) s->kin.exp[k] += dt * prev[k];
+  for (int k = 0; k < 3; ++k) s->kin.occ[k] = (int64_t)a.occ[k];
+  s->kin.rec.last = s->step_done;
+  s->kin.rec.updates += 1;
+  if (out) kin_fill(s, a, out);
+  return KMC_OK;
+}
+
+int kmc_kin_sample(kmc_sim* s, kmc_kin_out* out, int64_t* hist) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "kinetics sample: out is needed");
+  int rc = rec_check(s, s->kin.rec, KIN_OFF);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  const int NA = s->K.NA;
+  unsigned long long* rows = s->kin.hist + (size_t)KIN_ROWS_UPD * KIN_BINS;
+  HIPCHK(s, hipMemsetAsync(rows, 0, sizeof(unsigned long long) * 2 * KIN_BINS, s->stream));
+  HIPCHK(s, hipMemsetAsync(s->kin.acc->alive, 0, sizeof(KinAcc) - offsetof(KinAcc, alive), s->stream));
+  const int nblk = (NA + KIN_T - 1) / KIN_T;
+  if (nblk > 0)
+    k_kin_sample<<<(unsigned)std::min(nblk, AN_WG_MAX), KIN_T, 0, s->stream>>>(
+        NA, s->kin.dev, (long long)s->kin.rec.last, nblk, rows, s->kin.acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  KinAcc a;
+  rc = kin_result(s, &a);
+  if (rc != KMC_OK) return rc;
+  kin_fill(s, a, out);
+  out->n_rl_censored_alive = (int64_t)a.alive[0];
+  out->n_cis_censored_alive = (int64_t)a.alive[1];
+  if (hist)
+    HIPCHK(s, hipMemcpy(hist, s->kin.hist, sizeof(int64_t) * KIN_HISTS * KIN_BINS, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_kin_get(kmc_sim* s, const kmc_kin_view* v) {
+  if (!s) return KMC_ERR_ARG;
+  if (!v || !v->rl_lig || !v->rl_site || !v->rl_since || !v->cis_with || !v->cis_since || !v->last_lig ||
+      !v->free_since || !v->bits)
+    return fail(s, KMC_ERR_ARG, "kinetics get: the view and its eight arrays are needed");
+  const int rc = rec_check(s, s->kin.rec, KIN_OFF);
+  if (rc != KMC_OK) return rc;
+  const size_t NA = (size_t)s->K.NA;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  HIPCHK(s, hipMemcpy(v->rl_lig, s->kin.dev.rl_lig, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->rl_site, s->kin.dev.rl_site, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->rl_since, s->kin.dev.rl_since, sizeof(int64_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->cis_with, s->kin.dev.cis_with, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->cis_since, s->kin.dev.cis_since, sizeof(int64_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->last_lig, s->kin.dev.last_lig, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->free_since, s->kin.dev.free_since, sizeof(int64_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->bits, s->kin.dev.bits, NA, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_kin_end(kmc_sim* s) {
+  return s ? rec_end(s, s->kin) : KMC_ERR_ARG;
+}
+
+// ---------------------------------------------------------------- cluster growth kinetics
+// kmc_coag.hip: a layer of its own over the committed state, independent of
+// the tracker and of the kinetics recorder; its calls write only CfState's
+// buffers and the analysis scratch an_components fills.
+
+static const char* const CF_OFF = "growth: not begun (kmc_cf_begin; a new state drops the recorder)";
+
+// the counters of the call that just ran (the components' flag included); an
+// error drops the recorder
+static int cf_result(kmc_sim* s, bool components, CfAcc* a) {
+  HIPCHK(s, hipMemcpy(a, s->cf.acc, sizeof *a, hipMemcpyDeviceToHost));
+  AnOut o;
+  o.err = 0;
+  if (components) HIPCHK(s, hipMemcpy(&o, s->an.out, sizeof o, hipMemcpyDeviceToHost));
+  if (a->err || o.err) {
+    s->cf.rec.on = false;
+    return fail(s, KMC_ERR_STATE, "growth: a bond link leaves its range or the link chains do not end");
+  }
+  return KMC_OK;
+}
+
+// the look that a begin, an update or a put just took becomes the last one
+static void cf_look(kmc_sim* s, const CfAcc& a) {
+  s->cf.clusters = (int64_t)a.n_clusters;
+  s->cf.max = (int64_t)a.max_cluster;
+  for (int k = 0; k <= CF_MAX_SIZE; ++k) s->cf.ns[k] = (int64_t)a.n_s[k];
+}
+
+// every table and counter since begin starts again at `origin`
+static int cf_reset(kmc_sim* s, int64_t origin) {
+  HIPCHK(s, hipMemsetAsync(s->cf.tab, 0, sizeof(CfTab), s->stream));
+  HIPCHK(s, hipMemsetAsync(s->cf.acc, 0, sizeof(CfAcc), s->stream));
+  s->cf.rec.origin = s->cf.rec.last = origin;
+  s->cf.rec.updates = 0;
+  for (auto& e : s->cf.ev) e = 0;
+  s->cf.cores = s->cf.closed = s->cf.opened = 0;
+  for (auto& e : s->cf.expo) e = 0;
+  s->cf.expo2.assign((size_t)(s->cf.S + 1) * (s->cf.S + 1), (__int128)0);
+  return KMC_OK;
+}
+
+static void cf_fill(const kmc_sim* s, kmc_cf_out* out) {
+  std::memset(out, 0, sizeof *out);
+  out->origin_step = s->cf.rec.origin;
+  out->last_step = s->cf.rec.last;
+  out->n_updates = s->cf.rec.updates;
+  out->max_size = s->cf.S;
+  out->formed_rl = s->cf.ev[CF_EV_FORMED_RL];
+  out->formed_cis = s->cf.ev[CF_EV_FORMED_CIS];
+  out->broken_rl = s->cf.ev[CF_EV_BROKEN_RL];
+  out->broken_cis = s->cf.ev[CF_EV_BROKEN_CIS];
+  out->n_cores = s->cf.cores;
+  out->n_clusters = s->cf.clusters;
+  out->cycles_closed = s->cf.closed;
+  out->cycles_opened = s->cf.opened;
+  out->max_cluster = s->cf.max;
+}
+
+// the components of the current state into the other label / count set, which
+// becomes the last look's
+static int cf_take_components(kmc_sim* s) {
+  const int rc = an_components(s);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  s->cf.cur ^= 1;
+  HIPCHK(s, hipMemcpyAsync(s->cf.dev.label[s->cf.cur], s->an.label, sizeof(int32_t) * N, hipMemcpyDeviceToDevice,
+                           s->stream));
+  HIPCHK(s, hipMemcpyAsync(s->cf.dev.cnt[s->cf.cur], s->an.cnt, sizeof(unsigned long long) * N, hipMemcpyDeviceToDevice,
+                           s->stream));
+  return KMC_OK;
+}
+
+int kmc_cf_begin(kmc_sim* s, int32_t max_size) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  if (max_size < CF_MIN_SIZE || max_size > CF_MAX_SIZE)
+    return fail(s, KMC_ERR_ARG, "growth begin: 2 <= max_size <= " + std::to_string(CF_MAX_SIZE));
+  const int NA = s->K.NA, N = s->K.N;
+  if (!s->cf.acc) {
+    Scratch& g = s->cf.scratch;
+    rc = KMC_OK;
+    rc |= salloc(s, g, &s->cf.dev.rl_lig, (size_t)NA);
+    rc |= salloc(s, g, &s->cf.dev.cis_with, (size_t)NA);
+    for (int k = 0; k < 2; ++k) {
+      rc |= salloc(s, g, &s->cf.dev.label[k], (size_t)N);
+      rc |= salloc(s, g, &s->cf.dev.cnt[k], (size_t)N);
+    }
+    rc |= salloc(s, g, &s->cf.dev.parent, (size_t)N);
+    rc |= salloc(s, g, &s->cf.dev.core, (size_t)N);
+    rc |= salloc(s, g, &s->cf.dev.core_cnt, (size_t)N);
+    rc |= salloc(s, g, &s->cf.dev.pieces_prev, (size_t)N);
+    rc |= salloc(s, g, &s->cf.dev.pieces_cur, (size_t)N);
+    rc |= salloc(s, g, &s->cf.tab, 1);
+    rc |= salloc(s, g, &s->cf.acc, 1);
+    if (rc != KMC_OK) {
+      scratch_drop(s, s->cf);
+      return fail(s, KMC_ERR_HIP, "growth: scratch allocation failed");
+    }
+  }
+  s->cf.rec.on = false;
+  s->cf.S = max_size;
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = cf_reset(s, s->step_done);
+  if (rc == KMC_OK) rc = cf_take_components(s);
+  if (rc != KMC_OK) return rc;
+  if (NA > 0) k_cf_begin<<<(unsigned)((NA + CF_T - 1) / CF_T), CF_T, 0, s->stream>>>(s->K, s->d, s->cf.dev, s->cf.acc);
+  if (N > 0)
+    k_cf_sizes<<<(unsigned)((N + CF_T - 1) / CF_T), CF_T, 0, s->stream>>>(
+        s->cf.dev.label[s->cf.cur], s->cf.dev.cnt[s->cf.cur], N, s->cf.S, s->cf.acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  CfAcc a;
+  rc = cf_result(s, true, &a);
+  if (rc != KMC_OK) return rc;
+  cf_look(s, a);
+  s->cf.rec.on = true;
+  return KMC_OK;
+}
+
+int kmc_cf_update(kmc_sim* s, kmc_cf_out* out) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = rec_check(s, s->cf.rec, CF_OFF);
+  if (rc != KMC_OK) return rc;
+  if (s->step_done == s->cf.rec.last) {  // the state of the last look: nothing to file
+    s->cf.rec.updates += 1;
+    if (out) cf_fill(s, out);
+    return KMC_OK;
+  }
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = cf_take_components(s);
+  if (rc != KMC_OK) return rc;
+  const int NA = s->K.NA, N = s->K.N, cur = s->cf.cur, prev = cur ^ 1;
+  // the bond counters persist since begin; the rest is of this update
+  HIPCHK(s, hipMemsetAsync(&s->cf.acc->n_cores, 0, sizeof(CfAcc) - offsetof(CfAcc, n_cores), s->stream));
+  const unsigned g = (unsigned)((N + CF_T - 1) / CF_T);
+  if (g) {
+    k_cf_init<<<g, CF_T, 0, s->stream>>>(s->cf.dev, N);
+    if (NA > 0) k_cf_hook<<<(unsigned)((NA + CF_T - 1) / CF_T), CF_T, 0, s->stream>>>(s->K, s->d, s->cf.dev, s->cf.acc);
+    k_cf_flatten<<<g, CF_T, 0, s->stream>>>(s->cf.dev, s->cf.dev.label[prev], s->cf.dev.label[cur], NA, N, s->cf.acc);
+    k_cf_events<<<g, CF_T, 0, s->stream>>>(s->cf.dev, s->cf.dev.label[prev], s->cf.dev.cnt[prev], s->cf.dev.label[cur],
+                                           s->cf.dev.cnt[cur], N, s->cf.S, s->cf.tab, s->cf.acc);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  CfAcc a;
+  rc = cf_result(s, true, &a);
+  if (rc != KMC_OK) return rc;
+  // exposures of the interval that ended, from the previous look's n_s
+  const int S = s->cf.S;
+  const int64_t dt = s->step_done - s->cf.rec.last;
+  for (int x = 1; x <= S; ++x) {
+    const int64_t nx = s->cf.ns[x];
+    s->cf.expo[x] += dt * nx;
+    s->cf.expo2[(size_t)x * (S + 1) + x] += (__int128)dt * nx * (nx - 1) / 2;
+    for (int y = x + 1; y <= S; ++y) s->cf.expo2[(size_t)x * (S + 1) + y] += (__int128)dt * nx * s->cf.ns[y];
+  }
+  // the change of the cycle rank, from this update's bonds
+  int64_t ev[CF_NEV];
+  for (int k = 0; k < CF_NEV; ++k) ev[k] = (int64_t)a.ev[k] - s->cf.ev[k];
+  const int64_t formed = ev[CF_EV_FORMED_RL] + ev[CF_EV_FORMED_CIS], broken = ev[CF_EV_BROKEN_RL] + ev[CF_EV_BROKEN_CIS];
+  const int64_t cores = (int64_t)a.n_cores;
+  s->cf.closed += formed - (cores - (int64_t)a.n_clusters);
+  s->cf.opened += broken - (cores - s->cf.clusters);
+  for (int k = 0; k < CF_NEV; ++k) s->cf.ev[k] = (int64_t)a.ev[k];
+  s->cf.cores = cores;
+  cf_look(s, a);
+  s->cf.rec.last = s->step_done;
+  s->cf.rec.updates += 1;
+  if (out) cf_fill(s, out);
+  return KMC_OK;
+}
+
+int kmc_cf_sample(kmc_sim* s, kmc_cf_out* out, const kmc_cf_tables* t) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "growth sample: out is needed");
+  const int rc = rec_check(s, s->cf.rec, CF_OFF);
+  if (rc != KMC_OK) return rc;
+  cf_fill(s, out);
+  if (!t) return KMC_OK;
+  const int S = s->cf.S;
+  const size_t n1 = (size_t)S + 1, n2 = n1 * n1;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  auto pull = [&](int64_t* dst, const unsigned long long* src, size_t n) -> hipError_t {
+    return dst ? hipMemcpy(dst, src, sizeof(int64_t) * n, hipMemcpyDeviceToHost) : hipSuccess;
+  };
+  HIPCHK(s, pull(t->merge, s->cf.tab->merge, n2));
+  HIPCHK(s, pull(t->frag, s->cf.tab->frag, n2));
+  HIPCHK(s, pull(t->merge_kind, s->cf.tab->merge_kind, CF_KINDS * CF_KINDS));
+  HIPCHK(s, pull(t->frag_kind, s->cf.tab->frag_kind, CF_KINDS * CF_KINDS));
+  HIPCHK(s, pull(t->merge_pieces, s->cf.tab->merge_pieces, CF_PIECES));
+  HIPCHK(s, pull(t->frag_pieces, s->cf.tab->frag_pieces, CF_PIECES));
+  HIPCHK(s, pull(t->merge_product, s->cf.tab->merge_product, n1));
+  HIPCHK(s, pull(t->frag_parent, s->cf.tab->frag_parent, n1));
+  if (t->n_s) std::copy(s->cf.ns, s->cf.ns + n1, t->n_s);
+  if (t->expo) std::copy(s->cf.expo, s->cf.expo + n1, t->expo);
+  if (t->expo2)
+    for (size_t b = 0; b < n2; ++b) {
+      t->expo2[b].lo = (uint64_t)(unsigned __int128)s->cf.expo2[b];
+      t->expo2[b].hi = (int64_t)(s->cf.expo2[b] >> 64);
+    }
+  return KMC_OK;
+}
+
+int kmc_cf_get(kmc_sim* s, const kmc_cf_view* v) {
+  if (!s) return KMC_ERR_ARG;
+  if (!v || !v->rl_lig || !v->cis_with || !v->prev_label)
+    return fail(s, KMC_ERR_ARG, "growth get: the view and its three arrays are needed");
+  const int rc = rec_check(s, s->cf.rec, CF_OFF);
+  if (rc != KMC_OK) return rc;
+  const size_t NA = (size_t)s->K.NA, N = (size_t)s->K.N;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  HIPCHK(s, hipMemcpy(v->rl_lig, s->cf.dev.rl_lig, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->cis_with, s->cf.dev.cis_with, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(v->prev_label, s->cf.dev.label[s->cf.cur], sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < N; ++i) v->prev_label[i] += 1;
+  return KMC_OK;
+}
+
+int kmc_cf_put(kmc_sim* s, const kmc_cf_view* v, int64_t last_step) {
+  if (!s) return KMC_ERR_ARG;
+  if (!v || !v->rl_lig || !v->cis_with || !v->prev_label)
+    return fail(s, KMC_ERR_ARG, "growth put: the view and its three arrays are needed");
+  int rc = rec_check(s, s->cf.rec, CF_OFF);
+  if (rc != KMC_OK) return rc;
+  if (last_step > s->step_done) return fail(s, KMC_ERR_ARG, "growth put: last_step lies after the current step");
+  const int NA = s->K.NA, N = s->K.N;
+  for (int i = 0; i < NA; ++i) {
+    const int32_t l = v->rl_lig[i], c = v->cis_with[i];
+    if ((l != 0 && (l <= NA || l > N)) || (c != 0 && (c < 1 || c > NA || c == i + 1)))
+      return fail(s, KMC_ERR_STATE, "growth put: a stored bond of receptor " + std::to_string(i + 1) + " leaves its range");
+  }
+  std::vector<int32_t> lab((size_t)N);
+  for (int i = 0; i < N; ++i) {
+    const int32_t l = v->prev_label[i];
+    // a class' label is one of its members, labelled by itself, and no member lies below it
+    if (l < 1 || l > i + 1 || v->prev_label[l - 1] != l)
+      return fail(s, KMC_ERR_STATE, "growth put: the label of protein " + std::to_string(i + 1) +
+                                        " is out of range or not the smallest member of its class");
+    lab[(size_t)i] = l - 1;
+  }
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = cf_reset(s, last_step);
+  if (rc != KMC_OK) return rc;
+  const int cur = s->cf.cur;
+  hipStream_t st = s->stream;
+  HIPCHK(s, hipMemcpyAsync(s->cf.dev.rl_lig, v->rl_lig, sizeof(int32_t) * (size_t)NA, hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemcpyAsync(s->cf.dev.cis_with, v->cis_with, sizeof(int32_t) * (size_t)NA, hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemcpyAsync(s->cf.dev.label[cur], lab.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemsetAsync(s->cf.dev.cnt[cur], 0, sizeof(unsigned long long) * (size_t)N, st));
+  const unsigned g = (unsigned)((N + CF_T - 1) / CF_T);
+  if (g) {
+    k_an_count<<<g, AN_T, 0, st>>>(s->cf.dev.label[cur], s->cf.dev.cnt[cur], NA, N);
+    k_cf_sizes<<<g, CF_T, 0, st>>>(s->cf.dev.label[cur], s->cf.dev.cnt[cur], N, s->cf.S, s->cf.acc);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);  // (waits: lab is read by the copy until here)
+  if (rc != KMC_OK) return rc;
+  CfAcc a;
+  rc = cf_result(s, false, &a);
+  if (rc != KMC_OK) return rc;
+  cf_look(s, a);
+  return KMC_OK;
+}
+
+int kmc_cf_end(kmc_sim* s) {
+  return s ? rec_end(s, s->cf) : KMC_ERR_ARG;
+}
+
+}  // extern "C"

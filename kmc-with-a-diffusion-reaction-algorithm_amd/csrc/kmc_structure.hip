@@ -7,7 +7,8 @@
 //
 // Included by kmc_engine.hip after kmc_geometry.hip (one translation unit, the
 // library's flags: -ffp-contract=off, so a term is the four products, the two
-// sums and the two roundings include/kmc.h writes down and nothing else).
+// sums and the two roundings include/kmc.h writes down and nothing else); the
+// host side of the call is kmc_observe.hip §structure factor.
 #include "kmc_device.h"
 #include "kmc_structure.h"
 
@@ -29,6 +30,11 @@ struct SkArgs {
   int qb;           // q indices per q-block: nq spread evenly over the fewest blocks of at most SK_QB
   int nh_max, E;    // h rows reserved per protein; pairs per protein (nh_max + kmax + 1 <= SK_E_MAX)
   long long BX, BY;
+};
+
+// host side: [4][SK_NQ_MAX] sums, then the two selection counts; its own, whatever N
+struct SkState {
+  unsigned long long* sums = nullptr;
 };
 
 // rows spanned by the q-block whose first index is q0

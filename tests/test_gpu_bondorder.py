@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from _analysis import np_bin, np_d2
 from _bondorder import neighbour_lists, place_ligands, ref_bond_order, ref_bond_order_corr
 from _kmc import DENSE, REPO, build, capi, engine, params
 from _structure import PITCH, lattice_state
@@ -193,6 +194,35 @@ def test_read_only_and_repeatable(evolved):
     s0, v0, e0, c0 = tracked(False)
     s1, v1, e1, c1 = tracked(True)
     assert s0 == s1 and np.array_equal(v0, v1) and e0 == e1 and c0 == c1 == 300
+
+
+def test_cell_bins_grow_and_shrink_on_one_handle():
+    # The pair counts and the bond order keep one set of cell bins each, reserved by the same code.  On one handle,
+    # the two interleaved: r_max = r_cut = 1000 in the 3000 x 3000 box is the smallest grid accepted, 3 x 3 cells
+    # (10 counts); 60 makes 50 x 50 cells (2501 counts), so both sets are reallocated on a used handle; 1000 again
+    # keeps the capacity while the count shrinks.  Each result equals the same call on a fresh handle, the host's
+    # (bond order) and the brute-force reference (pair counts).  2250 + 300 proteins, placed, no step.
+    kw = dict(DENSE)
+    kw.update(box_x=3000.0, box_y=3000.0, box_z=250.0)
+    p = params(seed=31, n_a=2250, n_b=300, **kw)
+    hs = engine.host_init_random(p)
+    d2 = np_d2(hs, p, "AA")
+
+    def fresh(call):
+        with engine.Simulation(p) as s:
+            s.set_state(hs)
+            return call(s)
+
+    with engine.Simulation(p) as sim:
+        sim.set_state(hs)
+        for r in (1000.0, 60.0, 1000.0):
+            for call, want in ((lambda s: s.pair_counts("AA", r, 32), np_bin(d2, r, 32)),
+                               (lambda s: s.bond_order_corr("A", 6, r, r, nbins=32),
+                                engine.host_bond_order_corr(p, hs, "A", 6, r, r, nbins=32))):
+                got = call(sim)
+                assert want.sum() > 0
+                assert np.array_equal(got, want) and np.array_equal(got, fresh(call))
+        assert sim.get_state().equal(hs) and sim.current_step == 0
 
 
 def test_bad_arguments(evolved):

@@ -1,9 +1,8 @@
 """Cost of the bond-orientational order at C3 (1e6 proteins) after 2000 steps,
 beside its sequential host counterpart on the same state.  Run by hand:
   python tools/bondorder_time.py [--workload C3] [--steps 2000] [--repeats 20] [--out profiles/bondorder_C3.json]
-For receptors and ligands, fold 6: bond_order within r_cut 150 with both
-variants of the cutoff pass (KMC_BO_VARIANT=0 one lane per centre, 1 the wave's
-hit queue), bond_order linked (ligands), and bond_order_corr at r_max 300 with
+For receptors and ligands, fold 6: bond_order within r_cut 150, bond_order
+linked (ligands), and bond_order_corr at r_max 300 with
 60 bins: the median and minimum wall time of a call over the repeats (what the
 caller waits for: the launches, the wait, the result copies) and the HIP-event
 time of its kernels (kmc_analysis_ms); the number of ordered neighbour pairs
@@ -62,42 +61,36 @@ def timed(call):
             "device_ms_median": statistics.median(dev), "device_ms_min": min(dev)}
 
 
-host = {}
-for variant in ("1", "0"):
-    os.environ["KMC_BO_VARIANT"] = variant  # read when the handle is made
-    with engine.Simulation(p) as sim:
-        sim.set_state(hs)
-        for which in ("A", "B"):
-            for mode in ("within", "linked"):
-                if mode == "linked" and (which == "A" or variant == "0"):
-                    continue
-                r_cut = a.r_cut if mode == "within" else None
-                key = f"{which}_{mode}"
-                if key not in host:
-                    t = time.perf_counter()
-                    h = engine.host_bond_order(p, hs, which, FOLD, r_cut, mode, "all", NBINS, per_protein=True)
-                    host[key] = (h, (time.perf_counter() - t) * 1e3)
-                h, host_ms = host[key]
-                d = sim.bond_order(which, FOLD, r_cut, mode, "all", NBINS, per_protein=True)
-                same = d[1].as_dict() == h[1].as_dict() and all(np.array_equal(x, y) for x, y in zip(d[2:], h[2:])) \
-                    and np.array_equal(d[0], h[0])
-                if not same:
-                    raise SystemExit(f"bondorder_time: the device and the host differ ({key}, variant {variant})")
-                r = timed(lambda: sim.bond_order(which, FOLD, r_cut, mode, "all", NBINS))
-                pairs = int(h[1].sum_nn)
-                r.update(ordered_pairs=pairs, n_sel=int(h[1].n_sel), host_wall_ms=host_ms, device_equals_host=True,
-                         ps_per_term=r["device_ms_median"] * 1e9 / pairs if pairs else None)
-                res["calls"][key + (f"_variant{variant}" if mode == "within" else "")] = r
-            if variant == "1":
-                t = time.perf_counter()
-                hc = engine.host_bond_order_corr(p, hs, which, FOLD, a.r_max, a.r_cut, nbins=CORR_BINS)
-                host_ms = (time.perf_counter() - t) * 1e3
-                dc = sim.bond_order_corr(which, FOLD, a.r_max, a.r_cut, nbins=CORR_BINS)
-                if not np.array_equal(dc, hc):
-                    raise SystemExit(f"bondorder_time: the device and the host correlation differ ({which})")
-                r = timed(lambda: sim.bond_order_corr(which, FOLD, a.r_max, a.r_cut, nbins=CORR_BINS))
-                r.update(pairs=int(hc[1].sum()), host_wall_ms=host_ms, device_equals_host=True)
-                res["calls"][f"{which}_corr"] = r
+with engine.Simulation(p) as sim:
+    sim.set_state(hs)
+    for which in ("A", "B"):
+        for mode in ("within", "linked"):
+            if mode == "linked" and which == "A":
+                continue
+            r_cut = a.r_cut if mode == "within" else None
+            key = f"{which}_{mode}"
+            t = time.perf_counter()
+            h = engine.host_bond_order(p, hs, which, FOLD, r_cut, mode, "all", NBINS, per_protein=True)
+            host_ms = (time.perf_counter() - t) * 1e3
+            d = sim.bond_order(which, FOLD, r_cut, mode, "all", NBINS, per_protein=True)
+            same = d[1].as_dict() == h[1].as_dict() and all(np.array_equal(x, y) for x, y in zip(d[2:], h[2:])) \
+                and np.array_equal(d[0], h[0])
+            if not same:
+                raise SystemExit(f"bondorder_time: the device and the host differ ({key})")
+            r = timed(lambda: sim.bond_order(which, FOLD, r_cut, mode, "all", NBINS))
+            pairs = int(h[1].sum_nn)
+            r.update(ordered_pairs=pairs, n_sel=int(h[1].n_sel), host_wall_ms=host_ms, device_equals_host=True,
+                     ps_per_term=r["device_ms_median"] * 1e9 / pairs if pairs else None)
+            res["calls"][key] = r
+        t = time.perf_counter()
+        hc = engine.host_bond_order_corr(p, hs, which, FOLD, a.r_max, a.r_cut, nbins=CORR_BINS)
+        host_ms = (time.perf_counter() - t) * 1e3
+        dc = sim.bond_order_corr(which, FOLD, a.r_max, a.r_cut, nbins=CORR_BINS)
+        if not np.array_equal(dc, hc):
+            raise SystemExit(f"bondorder_time: the device and the host correlation differ ({which})")
+        r = timed(lambda: sim.bond_order_corr(which, FOLD, a.r_max, a.r_cut, nbins=CORR_BINS))
+        r.update(pairs=int(hc[1].sum()), host_wall_ms=host_ms, device_equals_host=True)
+        res["calls"][f"{which}_corr"] = r
 line = json.dumps(res)
 print(line)
 if a.out:
