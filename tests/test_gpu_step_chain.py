@@ -263,3 +263,23 @@ def test_busy_complexes_equal_oracle(monkeypatch, capfd, busy, chain, resort):
         assert reclassified > 500 and registered > 100 and heavy > 100, out[-1]
     else:
         assert (reclassified, registered, heavy) == (0, 0, 0)
+
+
+def test_full_bfs_every_step_equals_oracle(monkeypatch, busy):
+    # KMC_FULL_BFS=1: no complex kept from step to step, every row a BFS from scratch after k_cx_kill — the same
+    # records, hashes and unit rows; the launch counts show that the full rebuild ran on every step
+    monkeypatch.setenv("KMC_FULL_BFS", "1")
+    monkeypatch.setenv("KMC_RESORT", "0")
+    p, st, obs_o, hashes, rows_o = busy
+    with engine.Simulation(p) as sim:
+        sim.set_state(st)
+        sim.set_timing(("k_cx_kill",))
+        for s in range(BUSY_STEPS):
+            rec = sim.step(1)
+            assert rec[0] == obs_o[s], f"step {s + 1}: record {rec[0]} != {obs_o[s]}"
+            h = engine.state_hash(p, sim.get_state())
+            assert h == hashes[s], f"step {s + 1}: hash {h:x} != {hashes[s]:x}"
+            rl, mem = sim.clusters()
+            assert _rows(p, rl, mem)[0] == rows_o[s], f"step {s + 1}: unit rows differ from the oracle's"
+        # (without the knob and without re-sorts: once, for the new state)
+        assert sim.kernel_times()["k_cx_kill"][1] >= BUSY_STEPS
