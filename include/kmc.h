@@ -237,7 +237,7 @@ int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label
                     int64_t* hist, kmc_census* out);
 /* Device milliseconds of the last kmc_components / kmc_oligomer_census /
  * kmc_pair_counts / kmc_track_* / kmc_kin_* / kmc_cf_* / kmc_unwrap / kmc_cluster_* / kmc_structure_factor /
- * kmc_bond_order / kmc_bond_order_corr call: HIP events on the handle's stream around
+ * kmc_bond_order / kmc_bond_order_corr / kmc_network / kmc_rings call: HIP events on the handle's stream around
  * its kernels and clears (the result copies to the host excluded); 0 before
  * the first. */
 double kmc_analysis_ms(const kmc_sim* s);
@@ -843,6 +843,94 @@ int kmc_host_bond_order(const kmc_params* p, const kmc_state_view* v, int32_t wh
 int kmc_host_bond_order_corr(const kmc_params* p, const kmc_state_view* v, int32_t which, int32_t mode,
                              int32_t fold, double r_cut, int32_t select, double r_max, int32_t nbins,
                              int64_t* corr);
+
+/* Ring statistics and valency census of the ligand network:
+ * the graph the bonds draw — its ligand – receptor = receptor – ligand bridges,
+ * how many of a ligand's sites are occupied and continue to another ligand,
+ * and its closed rings by length, hexagons among them.  Like the other
+ * analyses the calls read the CURRENT state on the device (valid straight
+ * after kmc_set_state / kmc_load_*), launch nothing inside kmc_step, leave the
+ * state, the step counter, the recorders, kmc_get_clusters' validity and the
+ * other analyses' scratch untouched and are timed by kmc_analysis_ms; their
+ * scratch is their own (allocated by the first call, freed by kmc_destroy).
+ *
+ * Definitions — the device, kmc_host_network / kmc_host_rings and the tests
+ * share them; integers only, no position is read:
+ *   hop             from ligand b (reference index) by site s in {2, 3, 4},
+ *                   a zero link at any stage meaning no bridge:
+ *                     r  = res_nei[b][s]    the receptor on the site,
+ *                     r' = res_nei[r][3]    its cis partner,
+ *                     l  = res_nei[r'][2]   the partner's ligand (0: r' holds
+ *                                           none — a HALF BRIDGE),
+ *                     s' = res_nei[r'][4]   the site of l it sits on;
+ *                   the hop returns (l, s').
+ *   consistency     every bond is checked from its other side: r is 0 or a
+ *                   receptor with res_nei[r][2] = b and res_nei[r][4] = s; r'
+ *                   is 0 or another receptor with res_nei[r'][3] = r; l is 0
+ *                   or a ligand with s' in 2..4 and res_nei[l][s'] = r'.  Then
+ *                   the hop from (l, s') returns (b, s).  Likewise a
+ *                   receptor's nei2 is 0 or a ligand and its nei3 0 or
+ *                   another receptor whose nei3 points back.  Anything else —
+ *                   a link of the wrong kind, an asymmetric bridge — is
+ *                   KMC_ERR_STATE; nothing is read through a bad link.
+ *   bridge          the unordered pair {(b, s), (l, s')} of a hop with l != 0.
+ *                   l = b is a LOOP (then s' != s).
+ *   ligand graph G  a multigraph: the ligands are its vertices, the bridges
+ *                   its edges; a loop adds 2 to its ligand's degree, so every
+ *                   degree is at most 3.
+ *   ring of length L  L distinct ligands v_0 .. v_{L-1} and L distinct bridges
+ *                   e_i, e_i joining v_i and v_{(i+1) mod L}.  L = 1 is a loop,
+ *                   L = 2 two distinct bridges between the same two ligands.
+ *                   Two descriptions are the same ring iff their bridge sets
+ *                   are equal: parallel bridges give distinct rings.
+ *   chordless ring  no bridge outside the ring has both its ends at ligands of
+ *                   the ring.  (A ring's ligand uses two sites on the ring: it
+ *                   has at most one bridge off the ring and cannot carry a
+ *                   loop.)  The rule holds for every L: a double bridge beside
+ *                   a third parallel bridge is not chordless.
+ *   valency census  rec[(nei2 != 0) + 2 (nei3 != 0)] counts the receptors;
+ *                   lig_hist[occupied sites][bridge ends] the ligands (a
+ *                   ligand's bridge ends: its sites whose hop has l != 0).
+ *   counters        n_bridges (a loop counts once), n_loops, n_half (receptors
+ *                   with a ligand whose cis partner has none), n_free_dimers
+ *                   (cis pairs with no ligand on either side), n_vertices
+ *                   (ligands with >= 1 bridge end), n_net_components
+ *                   (kmc_components labels that hold >= 1 bridge), cycle_rank
+ *                   = n_bridges - n_vertices + n_net_components.
+ *   kmc_network     out: the counters and rec; lig_hist[4][4]; adj_lig[n_b][3]
+ *                   and adj_site[n_b][3] by the ligand's reference index and
+ *                   site - 2: the hop's l as a 1-based ligand number (1..n_b,
+ *                   0: none) and s' (0: none).  Every array may be NULL.
+ *   kmc_rings       1 <= max_len <= KMC_RING_MAX.  counts[2][KMC_RING_MAX + 1]:
+ *                   row 0 the rings of each length, row 1 the chordless ones;
+ *                   index 0 and the entries above max_len are zero.  member[2]
+ *                   [n_b] (uint32, by the ligand's reference index; may be
+ *                   NULL): bit L is set iff the ligand lies on at least one
+ *                   such ring of length L.  out (may be NULL) as kmc_network's.
+ *                   Each ring is counted once; the counts do not depend on the
+ *                   order of the proteins.  A call follows at most 3 *
+ *                   2^(max_len - 1) hops per ligand.
+ * kmc_host_network / kmc_host_rings: the same from a host state view,
+ * sequentially, no device.
+ * KMC_ERR_ARG for a null / out-of-range argument, a handle without state and a
+ * decomposed window; KMC_ERR_STATE as above; every loop is bounded, so a bad
+ * link ends the call and cannot hang. */
+#define KMC_RING_MAX 12
+typedef struct kmc_net_out {
+  int64_t n_bridges, n_loops, n_half, n_free_dimers, n_vertices, n_net_components, cycle_rank;
+  int64_t rec[4];
+} kmc_net_out;
+int kmc_network(kmc_sim* s, kmc_net_out* out, int64_t* lig_hist /* [4][4] */, int32_t* adj_lig /* [n_b][3] */,
+                int32_t* adj_site /* [n_b][3] */);
+int kmc_rings(kmc_sim* s, int32_t max_len, int64_t* counts /* [2][KMC_RING_MAX + 1] */,
+              uint32_t* member /* [2][n_b] */, kmc_net_out* out);
+/* Adjacency rows the last successful kmc_rings call gathered along its paths (its hops; 0 before the first): the
+ * work the call did, for a rate beside kmc_analysis_ms.  Unlike the counts it depends on the order of the slots. */
+int64_t kmc_rings_hops(const kmc_sim* s);
+int kmc_host_network(const kmc_params* p, const kmc_state_view* v, kmc_net_out* out, int64_t* lig_hist,
+                     int32_t* adj_lig, int32_t* adj_site);
+int kmc_host_rings(const kmc_params* p, const kmc_state_view* v, int32_t max_len, int64_t* counts, uint32_t* member,
+                   kmc_net_out* out);
 
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */

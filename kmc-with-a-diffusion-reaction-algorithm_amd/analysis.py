@@ -9,12 +9,13 @@ G_n(r) from the integers of bond_order / bond_order_corr, the effective on- and
 off-rates, the rebinding fraction and the Kaplan–Meier survival of bond
 lifetimes from the bond kinetics recorder (kin_sample), the coagulation and
 fragmentation kernels K(a, b), F(a, b) and the growth modes from the cluster
-growth recorder (cf_sample), and the replica sums of integer histograms,
+growth recorder (cf_sample), the hexagon fraction and ring densities of the
+ligand network from the ring counts (rings), and the replica sums of integer histograms,
 float64 sums and geometry tables.
 
 The counts and sums themselves come from libkmc (kmc_analysis.hip,
 kmc_dynamics.hip, kmc_geometry.hip, kmc_structure.hip, kmc_bondorder.hip,
-kmc_kinetics.hip, kmc_coag.hip);
+kmc_kinetics.hip, kmc_coag.hip, kmc_rings.hip);
 nothing here touches a trajectory.
 """
 from __future__ import annotations
@@ -423,3 +424,28 @@ def growth_modes(out, merge_kind) -> dict:
     return dict(binary_mergers=total, receptor_addition=ratio(rec, total), ligand_addition=ratio(lig, total),
                 cluster_cluster=ratio(total - rec - lig, total), cycles_closed=d["cycles_closed"],
                 cycles_opened=d["cycles_opened"], ring_fraction=ratio(d["cycles_closed"], formed))
+
+
+def ring_stats(counts, net) -> dict:
+    """The ring statistics of the ligand network from kmc_rings' counts[2, RING_MAX + 1] (all, chordless) and the
+    network's counters (a capi.NetOut, its as_dict(), or any mapping with n_vertices and cycle_rank):
+    hexagon_fraction = 2 chordless[6] / n_vertices, the share of the network ligands' ring positions that hexagons
+    fill (a ligand of the honeycomb lies on three hexagons of six ligands each: 1 for the perfect lattice);
+    rings_per_vertex = sum of the chordless rings / n_vertices; mean_ring_length, of the chordless rings;
+    rings_per_cycle = sum of the chordless rings / cycle_rank (1 when the chordless rings are a basis of the
+    network's cycles).  Zeros where a denominator is zero.  Sum counts and the counters over replicas
+    (reduce_counts) before the call: every input is additive."""
+    c = np.asarray(counts, dtype=np.int64)
+    if c.ndim != 2 or c.shape[0] != 2 or c.shape[1] != capi.RING_MAX + 1:
+        raise ValueError("ring_stats: counts is [2, RING_MAX + 1]")
+    d = net.as_dict() if hasattr(net, "as_dict") else dict(net)
+    nv, rank = int(d["n_vertices"]), int(d["cycle_rank"])
+    chordless = c[1]
+    total = int(chordless.sum())
+    lengths = int((chordless * np.arange(capi.RING_MAX + 1, dtype=np.int64)).sum())
+
+    def ratio(num, den):
+        return float(num) / float(den) if den else 0.0
+
+    return dict(hexagon_fraction=ratio(2 * int(chordless[6]), nv), rings_per_vertex=ratio(total, nv),
+                mean_ring_length=ratio(lengths, total), rings_per_cycle=ratio(total, rank))

@@ -468,6 +468,21 @@ class BondOrderOut(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+RING_MAX = 12  # KMC_RING_MAX: the longest ring kmc_rings counts
+
+
+class NetOut(C.Structure):
+    """kmc_net_out — the counters of the ligand network (kmc_network, kmc_rings) and the receptors' valency bins."""
+
+    _fields_ = [(name, C.c_int64) for name in ("n_bridges", "n_loops", "n_half", "n_free_dimers", "n_vertices",
+                                               "n_net_components", "cycle_rank")] + [("rec", C.c_int64 * 4)]
+
+    def as_dict(self) -> dict:
+        d = {name: int(getattr(self, name)) for name, _ in self._fields_[:-1]}
+        d["rec"] = [int(x) for x in self.rec]
+        return d
+
+
 DD_ROW = 416     # KMC_DD_ROW: one exchanged protein (48 doubles + 8 int32)
 DD_JCAP = 256    # KMC_DD_JCAP
 DD_XCAP = 64     # KMC_DD_XCAP

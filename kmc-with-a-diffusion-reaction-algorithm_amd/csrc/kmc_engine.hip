@@ -23,6 +23,7 @@
 #include "kmc_dynamics.hip"
 #include "kmc_kinetics.hip"
 #include "kmc_coag.hip"
+#include "kmc_rings.hip"
 
 using namespace kmcd;
 
@@ -157,6 +158,7 @@ struct __attribute__((visibility("hidden"))) kmc_sim {
   TrkState trk;
   KinState kin;
   CfState cf;
+  RgState rg;
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   double an_ms = 0.0;
 };

@@ -27,6 +27,7 @@
 #include "kmc_math.h"
 #include "kmc_params_check.h"
 #include "kmc_philox.h"
+#include "kmc_rings.h"
 #include "kmc_state_hash.h"
 #include "kmc_structure.h"
 
@@ -1559,6 +1560,195 @@ int kmc_host_cf_sample(const kmc_params* p, const kmc_cf_view* view, const kmc_c
   copy(to->n_s, t->n_s, n1);
   copy(to->expo, t->expo, n1);
   if (to->expo2 && to->expo2 != t->expo2) std::copy(t->expo2, t->expo2 + n2, to->expo2);
+  return KMC_OK;
+}
+
+// Ligand network and rings (include/kmc.h), sequential: the
+// hops, their checks and the chord rule are kmc_rings.h's, the ones the device
+// evaluates; the adjacency is by reference index, and a ring is counted from
+// its smallest ligand by a recursive walk.
+extern "C++" {
+namespace {
+
+struct RgHost {
+  std::vector<int32_t> lig, site;  // [nb][3]: the hop's 1-based ligand number and site, 0: none
+  int64_t hist[16];
+  kmc_net_out out;
+};
+
+int rg_host_network(const kmc_params* p, const kmc_state_view* v, RgHost* g, std::string* err) {
+  if (!p || !v || !v->a_int || !v->b_int || p->n_a < 0 || p->n_b < 0) {
+    *err = "rings: params and state are needed";
+    return KMC_ERR_ARG;
+  }
+  const int na = p->n_a, nb = p->n_b, n = na + nb;
+  const size_t NA = (size_t)na;
+  g->lig.assign(3 * (size_t)nb, 0);
+  g->site.assign(3 * (size_t)nb, 0);
+  std::fill(g->hist, g->hist + 16, (int64_t)0);
+  std::memset(&g->out, 0, sizeof g->out);
+  for (int i = 0; i < na; ++i) {
+    const int32_t v2 = v->a_int[2 * NA + i], v3 = v->a_int[4 * NA + i];
+    bool ok = kmcr::receptor_links_ok(v2, v3, i + 1, na, nb);
+    if (ok && v3 != 0) {
+      const int32_t p2 = v->a_int[2 * NA + (v3 - 1)], p3 = v->a_int[4 * NA + (v3 - 1)];
+      ok = p3 == i + 1;
+      if (ok && v2 == 0 && p2 == 0 && i + 1 < v3) g->out.n_free_dimers += 1;
+    }
+    if (!ok) {
+      *err = "rings: a bond link of receptor " + std::to_string(i + 1) + " is of the wrong kind or not returned";
+      return KMC_ERR_STATE;
+    }
+    g->out.rec[kmcr::rec_bin(v2, v3)] += 1;
+  }
+  std::vector<uint8_t> vertex((size_t)nb, 0);
+  for (int b = 0; b < nb; ++b) {
+    kmcr::Hops h;
+    kmcr::hops(v->a_int, v->b_int, na, nb, b, h);
+    if (h.bad) {
+      *err = "rings: a link followed from ligand " + std::to_string(b + 1) + " is of the wrong kind or the bridge is asymmetric";
+      return KMC_ERR_STATE;
+    }
+    int occ = 0, ends = 0;
+    for (int e = 0; e < 3; ++e) {
+      occ += h.r[e] != 0;
+      if (h.r2[e] != 0 && h.l[e] == 0) g->out.n_half += 1;
+      if (h.l[e] == 0) continue;
+      ++ends;
+      g->lig[3 * (size_t)b + e] = h.l[e];
+      g->site[3 * (size_t)b + e] = h.s2[e];
+      if (kmcr::first_end(b + 1, e + 2, h.l[e], h.s2[e])) {
+        g->out.n_bridges += 1;
+        g->out.n_loops += h.l[e] == b + 1;
+      }
+    }
+    g->hist[occ * 4 + ends] += 1;
+    vertex[b] = ends >= 1;
+    g->out.n_vertices += ends >= 1;
+  }
+  // the components of the whole bond graph (kmc_host_census' walk; every link was checked above) that hold a bridge
+  std::vector<uint8_t> seen((size_t)n, 0);
+  std::vector<int32_t> queue;
+  for (int r = 0; r < n; ++r) {
+    if (seen[r]) continue;
+    queue.assign(1, r);
+    seen[r] = 1;
+    bool holds = false;
+    for (size_t q = 0; q < queue.size(); ++q) {
+      const int x = queue[q];
+      int32_t nei[3] = {0, 0, 0};
+      if (x < na) {
+        nei[0] = v->a_int[2 * NA + x];
+        nei[1] = v->a_int[4 * NA + x];
+      } else {
+        holds = holds || vertex[x - na];
+        for (int j = 2; j <= 4; ++j) nei[j - 2] = v->b_int[(size_t)(4 + j - 1) * nb + (x - na)];
+      }
+      for (int e = 0; e < 3; ++e)
+        if (nei[e] != 0 && !seen[nei[e] - 1]) {
+          seen[nei[e] - 1] = 1;
+          queue.push_back(nei[e] - 1);
+        }
+    }
+    g->out.n_net_components += holds;
+  }
+  g->out.cycle_rank = g->out.n_bridges - g->out.n_vertices + g->out.n_net_components;
+  return KMC_OK;
+}
+
+// the walk of one (root, s_first < s_last): simple paths over ligands above the root, closed through s_last
+struct RgWalk {
+  const RgHost& g;
+  int nb, max_len;
+  int64_t* counts;   // [2][RG_MAX + 1]
+  uint32_t* member;  // [2][nb] or null
+  int root = 0, sb = 0;
+  int32_t path[RG_MAX];
+  int in[RG_MAX], out[RG_MAX];
+
+  void close(int L) {
+    auto vert = [&](int j) { return path[j]; };
+    auto off = [&](int i) { return g.lig[3 * (size_t)(path[i] - 1) + kmcr::off_site(in[i], out[i]) - 2]; };
+    const bool chordless = kmcr::chordless(L, vert, off);
+    counts[L] += 1;
+    if (chordless) counts[RG_MAX + 1 + L] += 1;
+    if (!member) return;
+    for (int i = 0; i < L; ++i) {
+      member[path[i] - 1] |= 1u << L;
+      if (chordless) member[(size_t)nb + path[i] - 1] |= 1u << L;
+    }
+  }
+  // ligand v entered by site s at depth k < max_len (at most max_len - 1 levels of recursion)
+  void visit(int32_t v, int s, int k) {
+    path[k] = v;
+    in[k] = s;
+    for (int c = 2; c <= 4; ++c) {
+      if (c == s) continue;
+      const int32_t w = g.lig[3 * (size_t)(v - 1) + c - 2];
+      const int ws = g.site[3 * (size_t)(v - 1) + c - 2];
+      if (w == 0) continue;
+      out[k] = c;
+      if (w == root) {
+        if (ws == sb) close(k + 1);
+        continue;
+      }
+      if (w < root || k + 1 >= max_len) continue;
+      bool seen = false;
+      for (int j = 1; j <= k; ++j) seen = seen || path[j] == w;
+      if (!seen) visit(w, ws, k + 1);
+    }
+  }
+  void from(int32_t r, int sa, int sb_) {
+    root = r;
+    sb = sb_;
+    path[0] = r;
+    in[0] = sb_;
+    out[0] = sa;
+    const int32_t w = g.lig[3 * (size_t)(r - 1) + sa - 2];
+    const int ws = g.site[3 * (size_t)(r - 1) + sa - 2];
+    if (w == 0) return;
+    if (w == r) {
+      if (ws == sb) close(1);
+      return;
+    }
+    if (w > r && max_len >= 2) visit(w, ws, 1);
+  }
+};
+
+}  // namespace
+}  // extern "C++"
+
+int kmc_host_network(const kmc_params* p, const kmc_state_view* v, kmc_net_out* out, int64_t* lig_hist,
+                     int32_t* adj_lig, int32_t* adj_site) {
+  RgHost g;
+  const int rc = rg_host_network(p, v, &g, &g_host_err);
+  if (rc != KMC_OK) return rc;
+  if (out) *out = g.out;
+  if (lig_hist) std::copy(g.hist, g.hist + 16, lig_hist);
+  if (adj_lig) std::copy(g.lig.begin(), g.lig.end(), adj_lig);
+  if (adj_site) std::copy(g.site.begin(), g.site.end(), adj_site);
+  return KMC_OK;
+}
+
+int kmc_host_rings(const kmc_params* p, const kmc_state_view* v, int32_t max_len, int64_t* counts, uint32_t* member,
+                   kmc_net_out* out) {
+  if (!counts || max_len < 1 || max_len > RG_MAX) {
+    g_host_err = "rings: counts is needed, 1 <= max_len <= 12";
+    return KMC_ERR_ARG;
+  }
+  RgHost g;
+  const int rc = rg_host_network(p, v, &g, &g_host_err);
+  if (rc != KMC_OK) return rc;
+  const int nb = p->n_b;
+  std::fill(counts, counts + 2 * (RG_MAX + 1), (int64_t)0);
+  if (member) std::fill(member, member + 2 * (size_t)nb, 0u);
+  RgWalk w{g, nb, max_len, counts, member};
+  for (int r = 1; r <= nb; ++r) {
+    w.from(r, 2, 3);
+    w.from(r, 2, 4);
+    w.from(r, 3, 4);
+  }
+  if (out) *out = g.out;
   return KMC_OK;
 }
 

@@ -1,6 +1,6 @@
 // kmc_observe.hip — the host side of the read-only layers over the committed
-// state (DESIGN.md §10-§16): their C-ABI calls, one section a layer, over the
-// kernels and the state structs of kmc_analysis.hip ... kmc_coag.hip.  Nothing
+// state (DESIGN.md §10-§17): their C-ABI calls, one section a layer, over the
+// kernels and the state structs of kmc_analysis.hip ... kmc_rings.hip.  Nothing
 // here writes a buffer a step reads, so the trajectory, the step counter and
 // clusters_valid stay as they are.
 //
@@ -1276,6 +1276,123 @@ int kmc_cf_put(kmc_sim* s, const kmc_cf_view* v, int64_t last_step) {
 
 int kmc_cf_end(kmc_sim* s) {
   return s ? rec_end(s, s->cf) : KMC_ERR_ARG;
+}
+
+// ---------------------------------------------------------------- ligand network and rings
+// kmc_rings.hip: read-only like the analysis above, on scratch of its own.
+
+static_assert(KMC_RING_MAX == RG_MAX, "kmc.h and kmc_rings.h agree on the longest ring");
+static_assert(sizeof(kmc_net_out) == 11 * sizeof(int64_t), "kmc_net_out layout");
+
+// The component labels (on the layer's own buffers), the adjacency with its
+// bins, counters and worklist and, for max_len > 0, the rings, left on the
+// device: five launches, or six.  The stream is not waited for.
+static int rg_run(kmc_sim* s, int max_len, bool members) {
+  const int N = s->K.N, NA = s->K.NA, NB = s->K.NB;
+  RgState& r = s->rg;
+  if (!r.out) {
+    int rc = KMC_OK;
+    rc |= dalloc(s, &r.parent, (size_t)N);
+    rc |= dalloc(s, &r.label, (size_t)N);
+    rc |= dalloc(s, &r.cnt, (size_t)N);
+    rc |= dalloc(s, &r.flag, (size_t)N);
+    rc |= dalloc(s, &r.an_out, 1);
+    rc |= dalloc(s, &r.rows, (size_t)NB);
+    rc |= dalloc(s, &r.work, (size_t)NB);
+    rc |= dalloc(s, &r.member, 2 * (size_t)NB);
+    rc |= dalloc(s, &r.out, 1);
+    if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "rings: scratch allocation failed");
+  }
+  hipStream_t st = s->stream;
+  HIPCHK(s, hipMemsetAsync(r.an_out, 0, sizeof(AnOut), st));
+  HIPCHK(s, hipMemsetAsync(r.out, 0, sizeof(RgOut), st));
+  HIPCHK(s, hipMemsetAsync(r.flag, 0, sizeof(int32_t) * (size_t)N, st));
+  if (members && NB > 0) HIPCHK(s, hipMemsetAsync(r.member, 0, sizeof(uint32_t) * 2 * (size_t)NB, st));
+  const unsigned g = (unsigned)((N + AN_T - 1) / AN_T);
+  if (g) {
+    k_an_init<<<g, AN_T, 0, st>>>(r.parent, r.cnt, N);
+    k_an_hook<<<g, AN_T, 0, st>>>(s->K, s->d, r.parent, r.an_out);
+    k_an_flatten<<<g, AN_T, 0, st>>>(r.parent, r.label, N, r.an_out);
+    k_rg_adj<<<(unsigned)((std::max(NA, NB) + RG_T - 1) / RG_T), RG_T, 0, st>>>(s->K, s->d, r.label, r.flag, r.rows,
+                                                                                r.work, r.out);
+  }
+  if (max_len > 0 && NB > 0) {
+    // a task a lane, three tasks a worklist entry; the worklist's length is known on the device only
+    const unsigned gr = (unsigned)std::min<int64_t>(RG_WG_MAX, (3 * (int64_t)NB + RG_T - 1) / RG_T);
+    k_rg_rings<<<gr, RG_T, 0, st>>>(NB, max_len, r.rows, r.work, members ? r.member : nullptr, r.out);
+  }
+  HIPCHK(s, hipGetLastError());
+  return KMC_OK;
+}
+
+// the device's verdict of the last call and its counters
+static int rg_result(kmc_sim* s, RgOut* o, kmc_net_out* out) {
+  AnOut a;
+  HIPCHK(s, hipMemcpy(&a, s->rg.an_out, sizeof a, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(o, s->rg.out, sizeof *o, hipMemcpyDeviceToHost));
+  if (a.err || o->err)
+    return fail(s, KMC_ERR_STATE, "rings: a bond link of the wrong kind, an asymmetric bridge or a link that leaves the state");
+  if (out) {
+    const unsigned long long* c = o->bins + 20;
+    out->n_bridges = (int64_t)c[RG_BRIDGES];
+    out->n_loops = (int64_t)c[RG_LOOPS];
+    out->n_half = (int64_t)c[RG_HALF];
+    out->n_free_dimers = (int64_t)c[RG_FREE_DIMERS];
+    out->n_vertices = (int64_t)c[RG_VERTICES];
+    out->n_net_components = (int64_t)c[RG_COMPONENTS];
+    out->cycle_rank = out->n_bridges - out->n_vertices + out->n_net_components;
+    for (int k = 0; k < 4; ++k) out->rec[k] = (int64_t)o->bins[16 + k];
+  }
+  return KMC_OK;
+}
+
+int kmc_network(kmc_sim* s, kmc_net_out* out, int64_t* lig_hist, int32_t* adj_lig, int32_t* adj_site) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = rg_run(s, 0, false);
+  if (rc == KMC_OK) rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  RgOut o;
+  rc = rg_result(s, &o, out);
+  if (rc != KMC_OK) return rc;
+  if (lig_hist)
+    for (int k = 0; k < 16; ++k) lig_hist[k] = (int64_t)o.bins[k];
+  const size_t NB = (size_t)s->K.NB;
+  if ((adj_lig || adj_site) && NB) {
+    std::vector<int4> rows(NB);
+    HIPCHK(s, hipMemcpy(rows.data(), s->rg.rows, sizeof(int4) * NB, hipMemcpyDeviceToHost));
+    auto ref = [&](size_t slot) { return (size_t)((uint32_t)rows[slot].w >> 8); };  // checked by the kernel: < NB
+    for (size_t b = 0; b < NB; ++b) {
+      const int32_t l[3] = {rows[b].x, rows[b].y, rows[b].z};  // slots + 1 in [0, NB]
+      for (int e = 0; e < 3; ++e) {
+        if (adj_lig) adj_lig[3 * ref(b) + e] = l[e] ? (int32_t)ref((size_t)l[e] - 1) + 1 : 0;
+        if (adj_site) adj_site[3 * ref(b) + e] = l[e] ? (int32_t)(((uint32_t)rows[b].w >> (2 * e)) & 3u) + 2 : 0;
+      }
+    }
+  }
+  return KMC_OK;
+}
+
+int64_t kmc_rings_hops(const kmc_sim* s) { return s ? s->rg.hops : 0; }
+
+int kmc_rings(kmc_sim* s, int32_t max_len, int64_t* counts, uint32_t* member, kmc_net_out* out) {
+  if (!s) return KMC_ERR_ARG;
+  if (!counts || max_len < 1 || max_len > RG_MAX)
+    return fail(s, KMC_ERR_ARG, "rings: counts is needed, 1 <= max_len <= " + std::to_string(RG_MAX));
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = rg_run(s, max_len, member != nullptr);
+  if (rc == KMC_OK) rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  RgOut o;
+  rc = rg_result(s, &o, out);
+  if (rc != KMC_OK) return rc;
+  for (int k = 0; k < 2 * (RG_MAX + 1); ++k) counts[k] = (int64_t)(&o.counts[0][0])[k];
+  s->rg.hops = (int64_t)o.hops;
+  const size_t NB = (size_t)s->K.NB;
+  if (member && NB) HIPCHK(s, hipMemcpy(member, s->rg.member, sizeof(uint32_t) * 2 * NB, hipMemcpyDeviceToHost));
+  return KMC_OK;
 }
 
 }  // extern "C"

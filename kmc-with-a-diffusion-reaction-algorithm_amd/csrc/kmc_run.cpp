@@ -40,6 +40,13 @@
 //                              step row bin count      (row = min(neighbours, 15), bin of |psi|)
 //                            and one line
 //                              step sum n_sel n_with sum_nn sum_pc sum_ps sum_m
+//           [--rings MAXLEN FILE]  every out_interval, the rings of the ligand network of up to
+//                            MAXLEN bridges (kmc_rings; 1 <= MAXLEN <= 12), appended like the
+//                            census: one line
+//                              step len all chordless     (per length with a ring)
+//                            and one line
+//                              step net n_bridges n_loops n_half n_free_dimers n_vertices
+//                                   n_net_components cycle_rank
 //           [--dyn EVERY RMAX NBINS FILE]  displacement tracking (kmc_track_*): the origin is
 //                            the state the process starts or resumes from (the tracker is
 //                            not checkpointed: a resume starts a new origin, every line
@@ -121,7 +128,8 @@ int main(int argc, char** argv) {
   kmc_params p;
   kmc_params_default(&p);
   int device = 0;
-  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path, psi_path, kin_path, cf_path;
+  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path, psi_path, kin_path, cf_path, rings_path;
+  int rings_max = 0;
   int psi_which = -1, psi_fold = 0, psi_nbins = 0;
   double psi_rcut = 0.0;
   int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0, geom_max = 0, sq_hmax = 0, sq_kmax = 0;
@@ -191,6 +199,14 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--rings") {
+      rings_max = atoi(next().c_str());
+      rings_path = next();
+      if (rings_max < 1 || rings_max > KMC_RING_MAX) {
+        fprintf(stderr, "kmc_run: bad --rings %d\n", rings_max);
+        return 2;
+      }
+    }
     else if (a == "--dyn") {
       dyn_every = atoll(next().c_str());
       dyn_rmax = atof(next().c_str());
@@ -257,6 +273,7 @@ int main(int argc, char** argv) {
     if (!geom_path.empty()) truncate(geom_path.c_str());
     if (!sq_path.empty()) truncate(sq_path.c_str());
     if (!psi_path.empty()) truncate(psi_path.c_str());
+    if (!rings_path.empty()) truncate(rings_path.c_str());
     if (!kin_path.empty()) truncate(kin_path.c_str());
     if (!cf_path.empty()) truncate(cf_path.c_str());
     rc = kmc_init_random(s);
@@ -414,6 +431,22 @@ int main(int argc, char** argv) {
         fprintf(f, "%lld sum %lld %lld %lld %lld %lld %lld\n", (long long)step, (long long)bo.n_sel,
                 (long long)bo.n_with, (long long)bo.sum_nn, (long long)bo.sum_pc, (long long)bo.sum_ps,
                 (long long)bo.sum_m);
+        fclose(f);
+      }
+      if (!rings_path.empty()) {
+        int64_t rc_counts[2][KMC_RING_MAX + 1];
+        kmc_net_out net;
+        rc = kmc_rings(s, rings_max, &rc_counts[0][0], nullptr, &net);
+        if (rc) return die(s, rc, "rings");
+        f = fopen(rings_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, rings_path.c_str());
+        for (int len = 1; len <= rings_max; ++len)
+          if (rc_counts[0][len])
+            fprintf(f, "%lld %d %lld %lld\n", (long long)step, len, (long long)rc_counts[0][len],
+                    (long long)rc_counts[1][len]);
+        fprintf(f, "%lld net %lld %lld %lld %lld %lld %lld %lld\n", (long long)step, (long long)net.n_bridges,
+                (long long)net.n_loops, (long long)net.n_half, (long long)net.n_free_dimers, (long long)net.n_vertices,
+                (long long)net.n_net_components, (long long)net.cycle_rank);
         fclose(f);
       }
       if (!dyn_path.empty()) {

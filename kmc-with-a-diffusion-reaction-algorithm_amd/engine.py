@@ -141,6 +141,14 @@ def load_library(path: Optional[str] = None):
     L.kmc_bond_order_corr.argtypes = [C.c_void_p] + bo_corr
     L.kmc_host_bond_order.argtypes = [P(capi.Params), P(capi.StateView)] + bo_local
     L.kmc_host_bond_order_corr.argtypes = [P(capi.Params), P(capi.StateView)] + bo_corr
+    net = [P(capi.NetOut), C.c_void_p, C.c_void_p, C.c_void_p]  # out, lig_hist, adj_lig, adj_site
+    rings = [C.c_int32, C.c_void_p, C.c_void_p, P(capi.NetOut)]  # max_len, counts, member, out
+    L.kmc_network.argtypes = [C.c_void_p] + net
+    L.kmc_rings.argtypes = [C.c_void_p] + rings
+    L.kmc_rings_hops.restype = C.c_int64
+    L.kmc_rings_hops.argtypes = [C.c_void_p]
+    L.kmc_host_network.argtypes = [P(capi.Params), P(capi.StateView)] + net
+    L.kmc_host_rings.argtypes = [P(capi.Params), P(capi.StateView)] + rings
     for f in ("kmc_host_math", "kmc_device_math"):
         getattr(L, f).argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
@@ -291,6 +299,43 @@ def host_bond_order_corr(params: capi.Params, hs: capi.HostState, which, fold: i
                                                         *_bo_args(which, fold, r_cut, mode, select), float(r_max),
                                                         int(nbins), corr.ctypes.data))
     return corr
+
+
+def _net_call(f, head, n_b):
+    """One kmc_network / kmc_host_network call: rc and (capi.NetOut, lig_hist[4, 4] int64, adj_lig[n_b, 3] int32,
+    adj_site[n_b, 3] int32)."""
+    out = capi.NetOut()
+    hist = np.zeros((4, 4), dtype=np.int64)
+    adj_lig, adj_site = np.zeros((n_b, 3), dtype=np.int32), np.zeros((n_b, 3), dtype=np.int32)
+    rc = f(*head, C.byref(out), hist.ctypes.data, adj_lig.ctypes.data if n_b else None,
+           adj_site.ctypes.data if n_b else None)
+    return rc, (out, hist, adj_lig, adj_site)
+
+
+def _rings_call(f, head, n_b, max_len, members):
+    """One kmc_rings / kmc_host_rings call: rc and (counts[2, RING_MAX + 1] int64, capi.NetOut) or, with members,
+    (counts, member[2, n_b] uint32, capi.NetOut)."""
+    out = capi.NetOut()
+    counts = np.zeros((2, capi.RING_MAX + 1), dtype=np.int64)
+    member = np.zeros((2, n_b), dtype=np.uint32)
+    rc = f(*head, int(max_len), counts.ctypes.data, member.ctypes.data if members and n_b else None, C.byref(out))
+    return rc, ((counts, member, out) if members else (counts, out))
+
+
+def host_network(params: capi.Params, hs: capi.HostState):
+    """The ligand network of a host state, sequentially (kmc_host_network): as Simulation.network."""
+    v = hs.view()
+    rc, res = _net_call(load_library().kmc_host_network, (C.byref(params), C.byref(v)), params.n_b)
+    _host_check(rc)
+    return res
+
+
+def host_rings(params: capi.Params, hs: capi.HostState, max_len: int = 8, members: bool = False):
+    """The rings of a host state's ligand network, sequentially (kmc_host_rings): as Simulation.rings."""
+    v = hs.view()
+    rc, res = _rings_call(load_library().kmc_host_rings, (C.byref(params), C.byref(v)), params.n_b, max_len, members)
+    _host_check(rc)
+    return res
 
 
 class HostKinetics:
@@ -593,10 +638,37 @@ class Simulation:
                                                        float(r_max), int(nbins), corr.ctypes.data))
         return corr
 
+    # ---- ligand network and its rings in the current state (kmc_rings.hip)
+    def network(self):
+        """(capi.NetOut, lig_hist[4, 4] int64, adj_lig[n_b, 3] int32, adj_site[n_b, 3] int32) — kmc_network: the
+        counters of the ligand – receptor = receptor – ligand bridges (bridges, loops, half bridges, free cis dimers,
+        network ligands and components, cycle rank) with the receptors' valency bins rec[(nei2 != 0) + 2 (nei3 !=
+        0)]; the ligands by [occupied sites, bridge ends]; and per ligand (reference index) and site - 2 the ligand
+        bridged to it (1-based ligand number, 0: none) and the site it arrives at.  Exact integers; the counters and
+        the bins are additive over replicas (analysis.reduce_counts)."""
+        rc, res = _net_call(load_library().kmc_network, (self._h,), self.params.n_b)
+        self._check(rc)
+        return res
+
+    def rings(self, max_len: int = 8, members: bool = False):
+        """(counts[2, RING_MAX + 1] int64, capi.NetOut) — kmc_rings: counts[0, L] the closed rings of L bridges over L
+        distinct ligands, counts[1, L] the chordless ones, for 1 <= L <= max_len <= capi.RING_MAX (the other entries
+        are zero).  With members: (counts, member[2, n_b] uint32, NetOut), bit L of member[0 / 1, b] set iff ligand b
+        (reference index) lies on such a ring of length L.  Additive over replicas (analysis.reduce_counts);
+        analysis.ring_stats turns counts and the NetOut into the hexagon fraction and the ring densities."""
+        rc, res = _rings_call(load_library().kmc_rings, (self._h,), self.params.n_b, max_len, members)
+        self._check(rc)
+        return res
+
+    @property
+    def rings_hops(self) -> int:
+        """Adjacency rows the last rings call gathered along its paths (kmc_rings_hops): its work, beside analysis_ms."""
+        return int(load_library().kmc_rings_hops(self._h))
+
     @property
     def analysis_ms(self) -> float:
         """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / unwrap /
-        cluster_* / structure_factor / bond_order / bond_order_corr call."""
+        cluster_* / structure_factor / bond_order / bond_order_corr / network / rings call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
     # ---- displacement tracking since a time origin (kmc_dynamics.hip; DESIGN.md §11)
