@@ -932,6 +932,153 @@ int kmc_host_network(const kmc_params* p, const kmc_state_view* v, kmc_net_out* 
 int kmc_host_rings(const kmc_params* p, const kmc_state_view* v, int32_t max_len, int64_t* counts, uint32_t* member,
                    kmc_net_out* out);
 
+/* Multi-origin lag correlator: the mean-squared displacement,
+ * the non-Gaussian parameter and the self-intermediate scattering function by
+ * lag time, averaged over every time origin the run offers.  Where the tracker
+ * (§11) relates every sample to the one origin of kmc_track_begin, this
+ * recorder keeps rings of origins at log-spaced strides (a multiple-tau, or
+ * order-n, correlator) and correlates the current positions with each stored
+ * origin at every update.  Like the tracker it reads the CURRENT state,
+ * launches nothing inside kmc_step and leaves the state, the step counter and
+ * kmc_get_clusters' validity untouched; its arrays are indexed by reference
+ * index i = 0..N-1 (receptors first), a protein's position is (x, y) of its
+ * bead [1][1].  It is independent of the tracker: both may run on one handle.
+ * All results are integers: the device, kmc_host_lag_* and the tests agree by
+ * equality, no order of summation exists, and the tables of replicas (and of
+ * consecutive recorders) add.
+ *
+ * Definitions — the device, kmc_host_lag_* and the tests share them:
+ *   integer coords  X = (int64) round(x * 1024.0), BX = (int64) round(box_x *
+ *                   1024.0); the same in y (§12's 2^-10 A).  KMC_ERR_ARG when
+ *                   BX < 1 or BY < 1.
+ *   minimum image   of a difference d with box B: m = d mod B (floor modulus),
+ *                   m -= B when 2 m >= B — the folding of the structure
+ *                   factor's axis phase.
+ *   configuration   (kmc_lag_config) every >= 1 steps between updates; levels
+ *                   L in 1..KMC_LAG_MAX_LEVELS; slots P even in
+ *                   2..KMC_LAG_MAX_SLOTS; max_jump in A, <= 0 meaning min(box)
+ *                   / 4, else at most min(box) / 2 (as §11's); max_disp in A,
+ *                   <= 0 meaning 16384, else at most 16384; nq in
+ *                   0..KMC_LAG_MAX_Q multipliers h[k] in 1..64.  J = (int64)
+ *                   round(max_jump * 1024.0), F = (int64) round(max_disp *
+ *                   1024.0) <= 2^24.
+ *   per protein     prev = (X, Y) at the last update; the unwrapped U (int64
+ *                   x 2); the three links as the tracker names them (receptor:
+ *                   nei2 as reference index + 1, nei4, nei3 as reference index
+ *                   + 1; ligand: nei2..4 as reference index + 1) as of the
+ *                   last update; last_event (int32).
+ *   kmc_lag_begin   is update n = 0: U = prev = (X, Y), the links are the
+ *                   current ones, last_event = 0, and U is stored as the origin
+ *                   of update 0 in slot 0 of every level.  The table is zeroed.
+ *                   The rings — levels * slots * 16 bytes per protein — and the
+ *                   rest are allocated here and freed by kmc_lag_end /
+ *                   kmc_destroy; a failed allocation is KMC_ERR_HIP with the
+ *                   recorder off.
+ *   kmc_lag_update  n >= 1, legal only when kmc_current_step() == the step of
+ *                   the last update + every (else KMC_ERR_ARG, nothing
+ *                   changes).  Per protein:
+ *                     1. d = minimum image of (X - prev.X); the same in y;
+ *                     2. U += d; prev = (X, Y);
+ *                     3. last_event = n when |dx| >= J or |dy| >= J or any of
+ *                        the three links differs from the stored ones; the
+ *                        stored links become the current ones;
+ *                     4. the class is that of the CURRENT state, §11's five:
+ *                        0 receptor without a link, 1 receptor with only a cis
+ *                        partner, 2 receptor with a ligand, 3 ligand without a
+ *                        link, 4 ligand with a link.
+ *                   Level l (0 <= l < L) fires when n mod 2^l == 0.  With t =
+ *                   n >> l it correlates with the origin of update n - j 2^l,
+ *                   which sits in slot (t - j) mod P, for every j in J(l) with
+ *                   j <= t: J(0) = 1..P, J(l >= 1) = P/2 + 1..P (the smaller j
+ *                   of a higher level repeat lags the level below holds).
+ *                   Afterwards the level stores U in slot t mod P.
+ *   rows            pair (l, j) has row j - 1 at level 0 and P + (l - 1) P/2 +
+ *                   (j - P/2 - 1) above; rows = P + (L - 1) P/2 <=
+ *                   KMC_LAG_MAX_ROWS; its lag is j 2^l updates.
+ *   pair term       of protein i against the origin U_k stored at update n_k:
+ *                   Dx = U.x - U_k.x, Dy = U.y - U_k.y.  FAR when |Dx| >= F or
+ *                   |Dy| >= F: the pair counts in n_far[row][class] and nowhere
+ *                   else.  Otherwise q = Dx^2 + Dy^2 (< 2^49, in units of 2^-20
+ *                   A^2), and the pair is CLEAN when last_event[i] <= n_k:
+ *                   neither a jump nor a change of links was seen at an update
+ *                   after the origin was stored, so a clean pair's class is its
+ *                   class at the origin too.  Per (row, class): n_all += 1,
+ *                   m2_all += q; for a clean pair n_clean += 1, m2_clean += q,
+ *                   m4_clean += q^2, and for each k < nq
+ *                     fs[k] += (int64) round(cos_x * 2^30) + (int64) round(
+ *                              cos_y * 2^30),
+ *                   cos_x the cosine of the structure factor's axis phase 2 pi
+ *                   ((h[k] Dx) mod BX folded into [-BX/2, BX/2)) / BX in double
+ *                   (the library's cos), cos_y the same of (h[k], Dy, BY).
+ *                   n_pairs[row] counts the (origin, update) pairs filed.
+ *                   The F bound keeps every kmc_i128 from overflowing below
+ *                   2^29 terms at the bound (q^2 < 2^98); overflow is not
+ *                   checked.
+ *                   CAVEAT: a bond that opens and closes again with the same
+ *                   partner between two updates is not seen, as in §11.
+ *   kmc_lag_sample  copies the table [rows][KMC_LAG_CLASSES] and n_pairs[rows]
+ *                   (either may be NULL) out, with the configuration in effect,
+ *                   J, F, BX, BY, rows, origin_step, last_step and n_updates.
+ *                   The table accumulates from begin until end.
+ *   kmc_lag_arrays  U [N][2] and last_event [N] (either may be NULL) by
+ *                   reference index: diagnostics and tests.
+ *   kmc_lag_end     drops the recorder and frees its memory; idempotent.
+ * kmc_analysis_ms covers the last call.  The recorder is not checkpointed.
+ * kmc_host_lag_*: the same from host state views, sequentially, no device; the
+ * caller owns the arrays of the kmc_lag_view (ring [L][P][N][2], table [rows]
+ * [5], n_pairs [rows]) and the kmc_lag_out that carries the recorder between
+ * the calls.
+ * KMC_ERR_ARG for a null / out-of-range argument (odd slots, a NaN or too large
+ * max_jump / max_disp, h out of range), a handle without state, a decomposed
+ * window, an update off the stride and a recorder that was not begun;
+ * kmc_set_state, kmc_load_*, kmc_init_random and kmc_dd_set_state drop the
+ * recorder. */
+#define KMC_LAG_MAX_LEVELS 20
+#define KMC_LAG_MAX_SLOTS 16
+#define KMC_LAG_MAX_Q 4
+#define KMC_LAG_CLASSES 5
+#define KMC_LAG_MAX_ROWS 168
+typedef struct kmc_lag_config {
+  int32_t every, levels, slots, nq;
+  double max_jump, max_disp;
+  int32_t h[KMC_LAG_MAX_Q];
+} kmc_lag_config;
+typedef struct kmc_lag_info {
+  int64_t n_updates; /* n of this update */
+  int64_t n_tasks;   /* (level, j) pairs it filed */
+  int64_t n_events;  /* proteins with last_event = n */
+} kmc_lag_info;
+typedef struct kmc_lag_cell {
+  int64_t n_all, n_clean, n_far;
+  kmc_i128 m2_all, m2_clean, m4_clean, fs[KMC_LAG_MAX_Q];
+} kmc_lag_cell;
+typedef struct kmc_lag_out {
+  kmc_lag_config cfg; /* as in effect: max_jump and max_disp resolved */
+  int64_t J, F, BX, BY;
+  int64_t origin_step, last_step, n_updates;
+  int64_t rows;
+} kmc_lag_out;
+typedef struct kmc_lag_view {
+  int64_t* prev;        /* [N][2] */
+  int64_t* U;           /* [N][2] */
+  int32_t* links;       /* [3][N] */
+  int32_t* last_event;  /* [N] */
+  int64_t* ring;        /* [levels][slots][N][2] */
+  kmc_lag_cell* table;  /* [rows][KMC_LAG_CLASSES] */
+  int64_t* n_pairs;     /* [rows] */
+} kmc_lag_view;
+int kmc_lag_begin(kmc_sim* s, const kmc_lag_config* cfg);
+int kmc_lag_update(kmc_sim* s, kmc_lag_info* info);
+int kmc_lag_sample(kmc_sim* s, kmc_lag_out* out, kmc_lag_cell* table /* [rows][5] */, int64_t* n_pairs /* [rows] */);
+int kmc_lag_arrays(kmc_sim* s, int64_t* U /* [N][2] */, int32_t* last_event /* [N] */);
+int kmc_lag_end(kmc_sim* s);
+int kmc_host_lag_begin(const kmc_params* p, const kmc_state_view* v, const kmc_lag_config* cfg,
+                       const kmc_lag_view* view, kmc_lag_out* acc);
+int kmc_host_lag_update(const kmc_params* p, const kmc_state_view* v, const kmc_lag_view* view, kmc_lag_out* acc,
+                        kmc_lag_info* info);
+int kmc_host_lag_sample(const kmc_params* p, const kmc_lag_view* view, const kmc_lag_out* acc, kmc_lag_out* out,
+                        kmc_lag_cell* table, int64_t* n_pairs);
+
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */
 int kmc_format_bond_line(const kmc_params* p, const kmc_obs* o, char* buf, size_t n);   /* main.cpp:2251 */

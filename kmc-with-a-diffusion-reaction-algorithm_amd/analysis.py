@@ -449,3 +449,41 @@ def ring_stats(counts, net) -> dict:
 
     return dict(hexagon_fraction=ratio(2 * int(chordless[6]), nv), rings_per_vertex=ratio(total, nv),
                 mean_ring_length=ratio(lengths, total), rings_per_cycle=ratio(total, rank))
+
+
+def lag_curves(sample, time_step: float) -> dict:
+    """MSD, alpha_2 and F_s by lag time from a lag_sample (a capi.LagSample; sum samples over replicas or windows
+    first: reduce_counts on counts(), then from_counts).  Per row r and class c, over the clean pairs:
+      tau[r]        = lag[r] * every * time_step,
+      msd[r, c]     = m2_clean / (2^20 n_clean)                          (A^2),
+      alpha2[r, c]  = <q^2> / (2 <q>^2) - 1 = m4_clean n_clean / (2 m2_clean^2) - 1   (the two-dimensional form),
+      fs[r, c, k]   = fs / (2 * 2^30 * n_clean): the mean of cos(q_k dx) and cos(q_k dy), q[k] = (2 pi h_k / box_x,
+                      2 pi h_k / box_y) with the box as the recorder saw it (BX, BY / 1024),
+      clean_fraction[r, c] = n_clean / (n_all + n_far), of every pair filed,
+      msd_all[r, c] = m2_all / (2^20 n_all), the pairs with events included,
+    and n_clean, n_pairs as float arrays.  Zeros where a denominator is zero.  The integer sums are divided whole
+    (Python ints), so no sum is rounded before its quotient is."""
+    s = sample
+    rows, nq = s.rows, s.nq
+    shape = (rows, capi.LAG_CLASSES)
+    out = dict(tau=np.asarray(s.lags, dtype=np.float64) * float(s.every) * float(time_step),
+               msd=np.zeros(shape), msd_all=np.zeros(shape), alpha2=np.zeros(shape), fs=np.zeros(shape + (nq,)),
+               clean_fraction=np.zeros(shape), n_clean=np.zeros(shape),
+               n_pairs=np.array([float(x) for x in s.n_pairs]),
+               q=np.array([[2.0 * np.pi * h * 1024.0 / s.BX, 2.0 * np.pi * h * 1024.0 / s.BY] for h in s.h]).reshape(nq, 2))
+    for r in range(rows):
+        for c in range(capi.LAG_CLASSES):
+            n, na, nf = int(s.n_clean[r, c]), int(s.n_all[r, c]), int(s.n_far[r, c])
+            m2, m4 = int(s.m2_clean[r, c]), int(s.m4_clean[r, c])
+            out["n_clean"][r, c] = n
+            if na:
+                out["msd_all"][r, c] = int(s.m2_all[r, c]) / (na << 20)
+            if na + nf:
+                out["clean_fraction"][r, c] = n / (na + nf)
+            if n:
+                out["msd"][r, c] = m2 / (n << 20)
+                for k in range(nq):
+                    out["fs"][r, c, k] = int(s.fs[r, c, k]) / (n << 31)
+            if m2:
+                out["alpha2"][r, c] = (m4 * n) / (2 * m2 * m2) - 1.0
+    return out

@@ -483,6 +483,154 @@ class NetOut(C.Structure):
         return d
 
 
+LAG_MAX_LEVELS, LAG_MAX_SLOTS, LAG_MAX_Q, LAG_CLASSES, LAG_MAX_ROWS = 20, 16, 4, 5, 168  # KMC_LAG_*
+
+
+class LagConfig(C.Structure):
+    """kmc_lag_config — the lag correlator's configuration."""
+
+    _fields_ = [("every", C.c_int32), ("levels", C.c_int32), ("slots", C.c_int32), ("nq", C.c_int32),
+                ("max_jump", C.c_double), ("max_disp", C.c_double), ("h", C.c_int32 * LAG_MAX_Q)]
+
+
+def lag_config(every: int, levels: int, slots: int, max_jump: float = 0.0, max_disp: float = 0.0, h=()) -> LagConfig:
+    """A LagConfig from its parts; h: the multipliers of F_s (nq = len(h))."""
+    h = [int(x) for x in h]
+    if len(h) > LAG_MAX_Q:
+        raise ValueError("lag: at most %d multipliers" % LAG_MAX_Q)
+    c = LagConfig(int(every), int(levels), int(slots), len(h), float(max_jump), float(max_disp))
+    for k, x in enumerate(h):
+        c.h[k] = x
+    return c
+
+
+class LagInfo(C.Structure):
+    """kmc_lag_info — one update: its number n, the (level, j) pairs filed, the proteins with an event."""
+
+    _fields_ = [(name, C.c_int64) for name in ("n_updates", "n_tasks", "n_events")]
+
+
+class LagOut(C.Structure):
+    """kmc_lag_out — the configuration in effect, the integer bounds and box, the steps and the update count."""
+
+    _fields_ = [("cfg", LagConfig)] + [(name, C.c_int64) for name in (
+        "J", "F", "BX", "BY", "origin_step", "last_step", "n_updates", "rows")]
+
+
+class LagView(C.Structure):
+    """kmc_lag_view — caller-owned arrays of the recorder on the host."""
+
+    _fields_ = [("prev", C.POINTER(C.c_int64)), ("U", C.POINTER(C.c_int64)), ("links", C.POINTER(C.c_int32)),
+                ("last_event", C.POINTER(C.c_int32)), ("ring", C.POINTER(C.c_int64)), ("table", C.c_void_p),
+                ("n_pairs", C.POINTER(C.c_int64))]
+
+
+# kmc_lag_cell as a numpy record
+LAG_CELL_DTYPE = np.dtype([("n_all", "<i8"), ("n_clean", "<i8"), ("n_far", "<i8"), ("m2_all", I128_DTYPE),
+                           ("m2_clean", I128_DTYPE), ("m4_clean", I128_DTYPE), ("fs", I128_DTYPE, (LAG_MAX_Q,))])
+assert LAG_CELL_DTYPE.itemsize == 136
+LAG_COUNTS = ("n_all", "n_clean", "n_far")
+LAG_SUMS = ("m2_all", "m2_clean", "m4_clean")
+LAG_LIMBS = 4  # a 128-bit sum as four 32-bit limbs, the top one signed: limbs add without a carry
+
+
+def lag_rows(levels: int, slots: int) -> int:
+    return slots + (levels - 1) * (slots // 2)
+
+
+def lag_row_lags(levels: int, slots: int) -> np.ndarray:
+    """The lag of every row in updates: j at level 0, j 2^l above."""
+    lags = list(range(1, slots + 1))
+    for l in range(1, levels):
+        lags += [j << l for j in range(slots // 2 + 1, slots + 1)]
+    return np.array(lags, dtype=np.int64)
+
+
+def _i128_ints(a: np.ndarray) -> np.ndarray:
+    out = np.empty(a.shape, dtype=object)
+    for idx in np.ndindex(a.shape):
+        out[idx] = (int(a[idx]["hi"]) << 64) + int(a[idx]["lo"])
+    return out
+
+
+class LagSample:
+    """One kmc_lag_sample: the configuration and steps (as attributes and in .out), n_pairs [rows] and, as arrays of
+    Python ints (the 128-bit sums whole): n_all, n_clean, n_far, m2_all, m2_clean, m4_clean [rows, 5] and
+    fs [rows, 5, nq].  counts() / from_counts(): the sample as one int64 vector that adds (analysis.reduce_counts)."""
+
+    def __init__(self, out: LagOut, table: np.ndarray, n_pairs: np.ndarray):
+        self.out = out
+        self.every, self.levels, self.slots, self.nq = out.cfg.every, out.cfg.levels, out.cfg.slots, out.cfg.nq
+        self.h = [int(out.cfg.h[k]) for k in range(self.nq)]
+        self.max_jump, self.max_disp = out.cfg.max_jump, out.cfg.max_disp
+        for name in ("J", "F", "BX", "BY", "origin_step", "last_step", "n_updates", "rows"):
+            setattr(self, name, int(getattr(out, name)))
+        self.lags = lag_row_lags(self.levels, self.slots)
+        self.n_pairs = np.array([int(x) for x in n_pairs], dtype=object)
+        for name in LAG_COUNTS:
+            setattr(self, name, table[name].astype(object))
+        for name in LAG_SUMS:
+            setattr(self, name, _i128_ints(table[name]))
+        self.fs = _i128_ints(table["fs"][:, :, :self.nq])
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name in LAG_COUNTS + LAG_SUMS + ("fs", "n_pairs")}
+
+    def counts(self) -> np.ndarray:
+        """[rows + rows * 5 * (3 + 4 * (3 + nq))] int64: n_pairs, then per cell the counts and every sum's limbs."""
+        v = [int(x) for x in self.n_pairs]
+        for r in range(self.rows):
+            for c in range(LAG_CLASSES):
+                v += [int(getattr(self, name)[r, c]) for name in LAG_COUNTS]
+                for x in [getattr(self, name)[r, c] for name in LAG_SUMS] + list(self.fs[r, c]):
+                    x = int(x)
+                    v += [x >> 32 * k & 0xFFFFFFFF for k in range(LAG_LIMBS - 1)] + [x >> 32 * (LAG_LIMBS - 1)]
+        return np.array(v, dtype=np.int64)
+
+    def from_counts(self, counts) -> "LagSample":
+        """A sample of this one's configuration holding the (summed) counts() vector."""
+        import copy
+        s = copy.copy(self)
+        it = iter(int(x) for x in np.asarray(counts).ravel())
+        s.n_pairs = np.array([next(it) for _ in range(self.rows)], dtype=object)
+        shape = (self.rows, LAG_CLASSES)
+        for name in LAG_COUNTS + LAG_SUMS:
+            setattr(s, name, np.zeros(shape, dtype=object))
+        s.fs = np.zeros(shape + (self.nq,), dtype=object)
+        limbs = lambda: sum(next(it) << 32 * k for k in range(LAG_LIMBS))
+        for r in range(self.rows):
+            for c in range(LAG_CLASSES):
+                for name in LAG_COUNTS:
+                    getattr(s, name)[r, c] = next(it)
+                for name in LAG_SUMS:
+                    getattr(s, name)[r, c] = limbs()
+                for k in range(self.nq):
+                    s.fs[r, c, k] = limbs()
+        return s
+
+
+class LagArrays:
+    """numpy-backed kmc_lag_view for n proteins: prev, U [n, 2], links [3, n], last_event [n], ring [levels, slots, n, 2],
+    table [rows, 5] (LAG_CELL_DTYPE), n_pairs [rows]."""
+
+    def __init__(self, n: int, levels: int, slots: int):
+        rows = lag_rows(levels, slots)
+        self.prev = np.zeros((n, 2), dtype=np.int64)
+        self.U = np.zeros((n, 2), dtype=np.int64)
+        self.links = np.zeros((3, n), dtype=np.int32)
+        self.last_event = np.zeros(n, dtype=np.int32)
+        self.ring = np.zeros((levels, slots, n, 2), dtype=np.int64)
+        self.table = np.zeros((rows, LAG_CLASSES), dtype=LAG_CELL_DTYPE)
+        self.n_pairs = np.zeros(rows, dtype=np.int64)
+
+    def view(self) -> LagView:
+        v = LagView()
+        for name, ptr in LagView._fields_:
+            a = getattr(self, name)
+            setattr(v, name, a.ctypes.data if ptr is C.c_void_p else a.ctypes.data_as(ptr))
+        return v
+
+
 DD_ROW = 416     # KMC_DD_ROW: one exchanged protein (48 doubles + 8 int32)
 DD_JCAP = 256    # KMC_DD_JCAP
 DD_XCAP = 64     # KMC_DD_XCAP

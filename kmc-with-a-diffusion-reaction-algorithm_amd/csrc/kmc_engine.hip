@@ -24,6 +24,7 @@
 #include "kmc_kinetics.hip"
 #include "kmc_coag.hip"
 #include "kmc_rings.hip"
+#include "kmc_lagcorr.hip"
 
 using namespace kmcd;
 
@@ -159,6 +160,7 @@ struct __attribute__((visibility("hidden"))) kmc_sim {
   KinState kin;
   CfState cf;
   RgState rg;
+  LagState lag;
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   double an_ms = 0.0;
 };
@@ -808,6 +810,7 @@ static int set_state_impl(kmc_sim* s, const kmc_state_view* v) {
   s->trk.rec.on = false;  // the tracker's origin described another state
   s->kin.rec.on = false;  // and so did the kinetics recorder's links
   s->cf.rec.on = false;   // and the growth recorder's bonds and clusters
+  s->lag.rec.on = false;  // and the lag correlator's origins
   return KMC_OK;
 }
 

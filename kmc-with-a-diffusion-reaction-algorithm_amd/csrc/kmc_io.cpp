@@ -24,6 +24,7 @@
 #include "kmc_coag.h"
 #include "kmc_host.h"
 #include "kmc_kinetics.h"
+#include "kmc_lagcorr.h"
 #include "kmc_math.h"
 #include "kmc_params_check.h"
 #include "kmc_philox.h"
@@ -1749,6 +1750,167 @@ int kmc_host_rings(const kmc_params* p, const kmc_state_view* v, int32_t max_len
     w.from(r, 3, 4);
   }
   if (out) *out = g.out;
+  return KMC_OK;
+}
+
+// Lag correlator (include/kmc.h): kmc_lag_*'s definitions on
+// host state views, one protein after the other and one task after the other;
+// the schedule and the pair term are kmc_lagcorr.h's, the ones the device
+// evaluates.  Every sum is taken whole, in __int128.
+extern "C++" {
+namespace {
+
+bool lag_view_ok(const kmc_lag_view* w) {
+  return w && w->prev && w->U && w->links && w->last_event && w->ring && w->table && w->n_pairs;
+}
+
+// protein i's (0-based reference index) integer position and links as the tracker names them
+void lag_host_cur(const kmc_params* p, const kmc_state_view* v, int i, int64_t X[2], int32_t l[3]) {
+  const int na = p->n_a, nb = p->n_b, n = na + nb;
+  auto ref = [&](int32_t x) { return x >= 1 && x <= n ? x : 0; };
+  if (i < na) {
+    for (int c = 0; c < 2; ++c) X[c] = (int64_t)kmcm::round_(v->ra[RA(na, 1, 1, c, i)] * 1024.0);
+    l[0] = ref(v->a_int[2 * (size_t)na + i]);
+    l[1] = v->a_int[3 * (size_t)na + i];
+    l[2] = ref(v->a_int[4 * (size_t)na + i]);
+  } else {
+    const int b = i - na;
+    for (int c = 0; c < 2; ++c) X[c] = (int64_t)kmcm::round_(v->rb[RB(nb, 1, 1, c, b)] * 1024.0);
+    for (int j = 2; j <= 4; ++j) l[j - 2] = ref(v->b_int[(size_t)(4 + j - 1) * nb + b]);
+  }
+}
+
+void lag_add(kmc_i128* w, __int128 x) {
+  const unsigned __int128 u = ((unsigned __int128)(uint64_t)w->hi << 64 | w->lo) + (unsigned __int128)x;
+  w->lo = (uint64_t)u;
+  w->hi = (int64_t)(uint64_t)(u >> 64);
+}
+
+}  // namespace
+}  // extern "C++"
+
+int kmc_host_lag_begin(const kmc_params* p, const kmc_state_view* v, const kmc_lag_config* cfg,
+                       const kmc_lag_view* view, kmc_lag_out* acc) {
+  if (!p || !v || !v->ra || !v->rb || !v->a_int || !v->b_int || !cfg || !lag_view_ok(view) || !acc) {
+    g_host_err = "lag: params, state, the configuration, the view's seven arrays and acc are needed";
+    return KMC_ERR_ARG;
+  }
+  kmc_lag_config c = *cfg;
+  for (int k = std::max(0, std::min(c.nq, LAG_MAX_Q)); k < LAG_MAX_Q; ++k) c.h[k] = 0;
+  int64_t J, F, BX, BY;
+  const char* bad =
+      kmcl::check(c.every, c.levels, c.slots, c.nq, c.h, p->box_x, p->box_y, &c.max_jump, &c.max_disp, &J, &F, &BX, &BY);
+  if (bad) {
+    g_host_err = bad;
+    return KMC_ERR_ARG;
+  }
+  const size_t N = (size_t)p->n_a + (size_t)p->n_b;
+  const int L = c.levels, P = c.slots, rows = kmcl::rows(L, P);
+  for (size_t i = 0; i < N; ++i) {
+    int64_t X[2];
+    int32_t l[3];
+    lag_host_cur(p, v, (int)i, X, l);
+    for (int k = 0; k < 2; ++k) view->prev[2 * i + k] = view->U[2 * i + k] = X[k];
+    for (int k = 0; k < 3; ++k) view->links[(size_t)k * N + i] = l[k];
+    view->last_event[i] = 0;
+    for (int lv = 0; lv < L; ++lv)
+      for (int k = 0; k < 2; ++k) view->ring[((size_t)(lv * P) * N + i) * 2 + k] = X[k];
+  }
+  std::memset(view->table, 0, sizeof(kmc_lag_cell) * (size_t)rows * LAG_CLASSES);
+  std::fill(view->n_pairs, view->n_pairs + rows, (int64_t)0);
+  std::memset(acc, 0, sizeof *acc);
+  acc->cfg = c;
+  acc->J = J;
+  acc->F = F;
+  acc->BX = BX;
+  acc->BY = BY;
+  acc->origin_step = acc->last_step = v->step;
+  acc->rows = rows;
+  return KMC_OK;
+}
+
+int kmc_host_lag_update(const kmc_params* p, const kmc_state_view* v, const kmc_lag_view* view, kmc_lag_out* acc,
+                        kmc_lag_info* info) {
+  if (!p || !v || !v->ra || !v->rb || !v->a_int || !v->b_int || !lag_view_ok(view) || !acc) {
+    g_host_err = "lag: params, state, the view's seven arrays and acc are needed";
+    return KMC_ERR_ARG;
+  }
+  if (v->step != acc->last_step + acc->cfg.every || acc->n_updates >= INT32_MAX) {
+    g_host_err = "lag: an update is due " + std::to_string(acc->cfg.every) + " steps after the last one";
+    return KMC_ERR_ARG;
+  }
+  const size_t N = (size_t)p->n_a + (size_t)p->n_b;
+  const int L = acc->cfg.levels, P = acc->cfg.slots, nq = acc->cfg.nq;
+  const int64_t n = acc->n_updates + 1;
+  kmcl::Task tasks[LAG_MAX_ROWS];
+  const int nt = kmcl::tasks(n, L, P, tasks);
+  int64_t n_events = 0;
+  for (size_t i = 0; i < N; ++i) {
+    int64_t X[2], d[2];
+    int32_t l[3];
+    lag_host_cur(p, v, (int)i, X, l);
+    d[0] = kmcl::min_image(X[0] - view->prev[2 * i], acc->BX);
+    d[1] = kmcl::min_image(X[1] - view->prev[2 * i + 1], acc->BY);
+    int64_t U[2];
+    for (int k = 0; k < 2; ++k) {
+      U[k] = view->U[2 * i + k] += d[k];
+      view->prev[2 * i + k] = X[k];
+    }
+    bool ev = std::llabs(d[0]) >= acc->J || std::llabs(d[1]) >= acc->J;
+    for (int k = 0; k < 3; ++k) {
+      int32_t* q = &view->links[(size_t)k * N + i];
+      ev = ev || *q != l[k];
+      *q = l[k];
+    }
+    if (ev) {
+      view->last_event[i] = (int32_t)n;
+      ++n_events;
+    }
+    const int c = kmcl::cls(i < (size_t)p->n_a, l);
+    for (int t = 0; t < nt; ++t) {
+      const int64_t* O = &view->ring[((size_t)tasks[t].ring * N + i) * 2];
+      const int64_t Dx = U[0] - O[0], Dy = U[1] - O[1];
+      kmc_lag_cell* cell = &view->table[(size_t)tasks[t].row * LAG_CLASSES + c];
+      if (kmcl::far(Dx, Dy, acc->F)) {
+        cell->n_far += 1;
+        continue;
+      }
+      const uint64_t q = kmcl::sq(Dx, Dy);
+      cell->n_all += 1;
+      lag_add(&cell->m2_all, (__int128)q);
+      if (view->last_event[i] > tasks[t].nk) continue;
+      cell->n_clean += 1;
+      lag_add(&cell->m2_clean, (__int128)q);
+      uint64_t a2, ab, b2;
+      kmcl::split(q, &a2, &ab, &b2);
+      lag_add(&cell->m4_clean, (__int128)kmcl::m4(a2, ab, b2));
+      for (int k = 0; k < nq; ++k)
+        lag_add(&cell->fs[k], (__int128)kmcl::fs_term(acc->cfg.h[k], Dx, Dy, acc->BX, acc->BY));
+    }
+    for (int lv = 0; lv < L && kmcl::fires(n, lv); ++lv)
+      for (int k = 0; k < 2; ++k) view->ring[((size_t)kmcl::store_ring(n, lv, P) * N + i) * 2 + k] = U[k];
+  }
+  for (int t = 0; t < nt; ++t) view->n_pairs[tasks[t].row] += 1;
+  acc->last_step = v->step;
+  acc->n_updates = n;
+  if (info) {
+    info->n_updates = n;
+    info->n_tasks = nt;
+    info->n_events = n_events;
+  }
+  return KMC_OK;
+}
+
+int kmc_host_lag_sample(const kmc_params* p, const kmc_lag_view* view, const kmc_lag_out* acc, kmc_lag_out* out,
+                        kmc_lag_cell* table, int64_t* n_pairs) {
+  if (!p || !lag_view_ok(view) || !acc || !out) {
+    g_host_err = "lag sample: params, the view's seven arrays, acc and out are needed";
+    return KMC_ERR_ARG;
+  }
+  const kmc_lag_out a = *acc;  // (out may be acc itself)
+  *out = a;
+  if (table && table != view->table) std::copy(view->table, view->table + (size_t)a.rows * LAG_CLASSES, table);
+  if (n_pairs && n_pairs != view->n_pairs) std::copy(view->n_pairs, view->n_pairs + a.rows, n_pairs);
   return KMC_OK;
 }
 

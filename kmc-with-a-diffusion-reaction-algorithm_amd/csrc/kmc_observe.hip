@@ -1,6 +1,6 @@
 // kmc_observe.hip — the host side of the read-only layers over the committed
-// state (DESIGN.md §10-§17): their C-ABI calls, one section a layer, over the
-// kernels and the state structs of kmc_analysis.hip ... kmc_rings.hip.  Nothing
+// state (DESIGN.md §10-§18): their C-ABI calls, one section a layer, over the
+// kernels and the state structs of kmc_analysis.hip ... kmc_lagcorr.hip.  Nothing
 // here writes a buffer a step reads, so the trajectory, the step counter and
 // clusters_valid stay as they are.
 //
@@ -1393,6 +1393,157 @@ int kmc_rings(kmc_sim* s, int32_t max_len, int64_t* counts, uint32_t* member, km
   const size_t NB = (size_t)s->K.NB;
   if (member && NB) HIPCHK(s, hipMemcpy(member, s->rg.member, sizeof(uint32_t) * 2 * NB, hipMemcpyDeviceToHost));
   return KMC_OK;
+}
+
+// ---------------------------------------------------------------- lag correlator
+// kmc_lagcorr.hip: a recorder of its own over the committed state, independent
+// of the tracker; its calls write only LagState's buffers.  Unlike the other
+// recorders its memory depends on the configuration (the rings): begin
+// allocates it, end frees it.
+
+static_assert(KMC_LAG_MAX_LEVELS == LAG_MAX_LEVELS && KMC_LAG_MAX_SLOTS == LAG_MAX_SLOTS && KMC_LAG_MAX_Q == LAG_MAX_Q &&
+                  KMC_LAG_CLASSES == LAG_CLASSES && KMC_LAG_MAX_ROWS == LAG_MAX_ROWS,
+              "kmc.h and kmc_lagcorr.h agree");
+static_assert(sizeof(kmc_lag_cell) == sizeof(lag_u64) * LAG_CELL, "a table cell is LAG_CELL words");
+static_assert(offsetof(kmc_lag_cell, m2_all) == 24 && offsetof(kmc_lag_cell, m4_clean) == 56 &&
+                  offsetof(kmc_lag_cell, fs) == 72,
+              "kmc_lag_cell is the layout lag_flush adds into");
+
+static const char* const LAG_OFF = "lag: not begun (kmc_lag_begin; a new state drops the recorder)";
+
+int kmc_lag_begin(kmc_sim* s, const kmc_lag_config* cfg) {
+  if (!s) return KMC_ERR_ARG;
+  if (!cfg) return fail(s, KMC_ERR_ARG, "lag: the configuration is needed");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  kmc_lag_config c = *cfg;
+  for (int k = std::max(0, std::min(c.nq, LAG_MAX_Q)); k < LAG_MAX_Q; ++k) c.h[k] = 0;
+  int64_t J, F, BX, BY;
+  const char* bad = kmcl::check(c.every, c.levels, c.slots, c.nq, c.h, s->K.box_x, s->K.box_y, &c.max_jump, &c.max_disp,
+                                &J, &F, &BX, &BY);
+  if (bad) return fail(s, KMC_ERR_ARG, bad);
+  // a recorder that was on ends here, whatever becomes of this call
+  rc = rec_end(s, s->lag);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  const int L = c.levels, P = c.slots, rows = kmcl::rows(L, P);
+  Scratch& g = s->lag.scratch;
+  rc = KMC_OK;
+  rc |= salloc(s, g, &s->lag.dev.prev, N);
+  rc |= salloc(s, g, &s->lag.dev.U, N);
+  rc |= salloc(s, g, &s->lag.dev.links, 3 * N);
+  rc |= salloc(s, g, &s->lag.dev.last_event, N);
+  rc |= salloc(s, g, &s->lag.dev.cls, N);
+  rc |= salloc(s, g, &s->lag.tasks, (size_t)LAG_MAX_ROWS);
+  rc |= salloc(s, g, &s->lag.table, (size_t)rows * LAG_CLASSES * LAG_CELL);
+  rc |= salloc(s, g, &s->lag.n_events, 1);
+  if (rc == KMC_OK) rc |= salloc(s, g, &s->lag.dev.ring, (size_t)L * P * N);
+  if (rc != KMC_OK) {
+    scratch_drop(s, s->lag);
+    return fail(s, KMC_ERR_HIP, "lag: allocation failed (the rings take levels * slots * 16 bytes per protein)");
+  }
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  if (N > 0) k_lag_begin<<<(unsigned)((N + LAG_T - 1) / LAG_T), LAG_T, 0, s->stream>>>(s->K, s->d, s->lag.dev, L, P);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  s->lag.cfg = c;
+  LagArgs& a = s->lag.a;
+  a.BX = BX;
+  a.BY = BY;
+  a.J = J;
+  a.F = F;
+  a.L = L;
+  a.P = P;
+  a.nq = c.nq;
+  for (int k = 0; k < LAG_MAX_Q; ++k) a.h[k] = c.h[k];
+  s->lag.rec = Recorder{true, s->step_done, s->step_done, 0};
+  return KMC_OK;
+}
+
+int kmc_lag_update(kmc_sim* s, kmc_lag_info* info) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = rec_check(s, s->lag.rec, LAG_OFF);
+  if (rc != KMC_OK) return rc;
+  LagState& g = s->lag;
+  if (s->step_done != g.rec.last + g.cfg.every)
+    return fail(s, KMC_ERR_ARG, "lag: an update is due " + std::to_string(g.cfg.every) + " steps after the last one");
+  if (g.rec.updates >= INT32_MAX) return fail(s, KMC_ERR_ARG, "lag: the update counter is full");
+  const int64_t n = g.rec.updates + 1;
+  kmcl::Task tasks[LAG_MAX_ROWS];
+  const int nt = kmcl::tasks(n, g.a.L, g.a.P, tasks);
+  g.a.n = (int)n;
+  g.a.ntasks = nt;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  const int nblk = (N + LAG_T - 1) / LAG_T;
+  HIPCHK(s, hipMemcpyAsync(g.tasks, tasks, sizeof(kmcl::Task) * (size_t)nt, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(s, hipMemsetAsync(g.n_events, 0, sizeof(lag_u64), s->stream));
+  if (nblk > 0) {
+    const size_t lds = sizeof(lag_u64) * (size_t)(std::min(nt, LAG_CHUNK) * LAG_CLASSES * LAG_W);
+    k_lag_update<<<(unsigned)std::min(nblk, AN_WG_MAX), LAG_T, lds, s->stream>>>(s->K, s->d, g.dev, g.a, g.tasks, nblk,
+                                                                                g.table, g.n_events);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);  // (waits: tasks is read by the copy until here)
+  if (rc != KMC_OK) {
+    g.rec.on = false;  // the per-protein state may be half advanced
+    return rc;
+  }
+  for (int t = 0; t < nt; ++t) g.n_pairs[tasks[t].row] += 1;
+  g.rec.last = s->step_done;
+  g.rec.updates = n;
+  if (info) {
+    lag_u64 ne = 0;
+    HIPCHK(s, hipMemcpy(&ne, g.n_events, sizeof ne, hipMemcpyDeviceToHost));
+    info->n_updates = n;
+    info->n_tasks = nt;
+    info->n_events = (int64_t)ne;
+  }
+  return KMC_OK;
+}
+
+int kmc_lag_sample(kmc_sim* s, kmc_lag_out* out, kmc_lag_cell* table, int64_t* n_pairs) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "lag sample: out is needed");
+  int rc = rec_check(s, s->lag.rec, LAG_OFF);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = an_end(s);  // (no device work: the time of this call is that of its copy's wait)
+  if (rc != KMC_OK) return rc;
+  const LagState& g = s->lag;
+  const int rows = kmcl::rows(g.a.L, g.a.P);
+  std::memset(out, 0, sizeof *out);
+  out->cfg = g.cfg;
+  out->J = g.a.J;
+  out->F = g.a.F;
+  out->BX = g.a.BX;
+  out->BY = g.a.BY;
+  out->origin_step = g.rec.origin;
+  out->last_step = g.rec.last;
+  out->n_updates = g.rec.updates;
+  out->rows = rows;
+  if (table)
+    HIPCHK(s, hipMemcpy(table, g.table, sizeof(kmc_lag_cell) * (size_t)rows * LAG_CLASSES, hipMemcpyDeviceToHost));
+  if (n_pairs) std::copy(g.n_pairs, g.n_pairs + rows, n_pairs);
+  return KMC_OK;
+}
+
+int kmc_lag_arrays(kmc_sim* s, int64_t* U, int32_t* last_event) {
+  if (!s) return KMC_ERR_ARG;
+  const int rc = rec_check(s, s->lag.rec, LAG_OFF);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  static_assert(sizeof(longlong2) == 2 * sizeof(int64_t), "U [N][2] is the device's longlong2 [N]");
+  if (U && N) HIPCHK(s, hipMemcpy(U, s->lag.dev.U, sizeof(longlong2) * N, hipMemcpyDeviceToHost));
+  if (last_event && N) HIPCHK(s, hipMemcpy(last_event, s->lag.dev.last_event, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_lag_end(kmc_sim* s) {
+  return s ? rec_end(s, s->lag) : KMC_ERR_ARG;
 }
 
 }  // extern "C"

@@ -76,6 +76,16 @@
 //                              frag step a b count
 //                              pieces step k mergers fragmentations       (non-zero rows)
 //                              sizes step s n_s expo merge_product frag_parent (non-zero rows)
+//           [--lag EVERY LEVELS SLOTS FILE]  multi-origin lag correlator (kmc_lag_*): the recorder
+//                            begins where the process starts or resumes (it is not checkpointed: a
+//                            new origin, every line carries it); kmc_step runs in pieces that end
+//                            where an update is due, EVERY steps after the last one (the stride runs
+//                            on across the output steps); every out_interval FILE gets, since that
+//                            origin, one line
+//                              lag step origin n_updates every levels slots J F BX BY
+//                            and per non-empty cell (the 128-bit sums in decimal)
+//                              cell step origin row lag class n_pairs n_all n_clean n_far m2_all
+//                                   m2_clean m4_clean
 #include <sys/stat.h>
 
 #include <cstdio>
@@ -87,6 +97,19 @@
 #include "../../include/kmc.h"
 
 namespace {
+
+// a kmc_i128 in decimal
+std::string dec128(kmc_i128 w) {
+  unsigned __int128 u = (unsigned __int128)(uint64_t)w.hi << 64 | w.lo;
+  const bool neg = w.hi < 0;
+  if (neg) u = ~u + 1;
+  std::string d;
+  do {
+    d.insert(d.begin(), (char)('0' + (int)(u % 10)));
+    u /= 10;
+  } while (u);
+  return neg ? "-" + d : d;
+}
 
 bool set_field(kmc_params* p, const std::string& k, const std::string& v) {
   double d = strtod(v.c_str(), nullptr);
@@ -128,7 +151,7 @@ int main(int argc, char** argv) {
   kmc_params p;
   kmc_params_default(&p);
   int device = 0;
-  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path, psi_path, kin_path, cf_path, rings_path;
+  std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path, psi_path, kin_path, cf_path, rings_path, lag_path;
   int rings_max = 0;
   int psi_which = -1, psi_fold = 0, psi_nbins = 0;
   double psi_rcut = 0.0;
@@ -136,6 +159,8 @@ int main(int argc, char** argv) {
   double rdf_rmax = 0.0, dyn_rmax = 0.0;
   int64_t dyn_every = 0, kin_every = 0, cf_every = 0;
   int cf_smax = 0;
+  kmc_lag_config lag_cfg;
+  std::memset(&lag_cfg, 0, sizeof lag_cfg);
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -234,6 +259,17 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--lag") {
+      lag_cfg.every = atoi(next().c_str());
+      lag_cfg.levels = atoi(next().c_str());
+      lag_cfg.slots = atoi(next().c_str());
+      lag_path = next();
+      if (lag_cfg.every < 1 || lag_cfg.levels < 1 || lag_cfg.levels > KMC_LAG_MAX_LEVELS || lag_cfg.slots < 2 ||
+          lag_cfg.slots > KMC_LAG_MAX_SLOTS || lag_cfg.slots % 2) {
+        fprintf(stderr, "kmc_run: bad --lag %d %d %d\n", lag_cfg.every, lag_cfg.levels, lag_cfg.slots);
+        return 2;
+      }
+    }
     else if (a == "--set") {
       std::string kv = next();
       size_t eq = kv.find('=');
@@ -276,6 +312,7 @@ int main(int argc, char** argv) {
     if (!rings_path.empty()) truncate(rings_path.c_str());
     if (!kin_path.empty()) truncate(kin_path.c_str());
     if (!cf_path.empty()) truncate(cf_path.c_str());
+    if (!lag_path.empty()) truncate(lag_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
   }
@@ -307,13 +344,18 @@ int main(int argc, char** argv) {
     rc = kmc_cf_begin(s, cf_smax);
     if (rc) return die(s, rc, "growth begin");
   }
+  int64_t lag_left = lag_cfg.every;  // steps until the correlator's next update: its stride runs on across the intervals
+  if (!lag_path.empty()) {
+    rc = kmc_lag_begin(s, &lag_cfg);
+    if (rc) return die(s, rc, "lag begin");
+  }
   int64_t step = kmc_current_step(s);
   while (step < p.simu_step) {
     int64_t next_out = (step / p.out_interval + 1) * p.out_interval;
     int64_t end = next_out < p.simu_step ? next_out : p.simu_step;
     int64_t n = end - step;
     obs.resize((size_t)n);
-    if (dyn_path.empty() && kin_path.empty() && cf_path.empty()) {
+    if (dyn_path.empty() && kin_path.empty() && cf_path.empty() && lag_path.empty()) {
       rc = kmc_step(s, n, obs.data());
       if (rc) return die(s, rc, "kmc_step");
     } else {
@@ -326,12 +368,14 @@ int main(int argc, char** argv) {
         if (dyn_left < m) m = dyn_left;
         if (kin_left < m) m = kin_left;
         if (cf_left < m) m = cf_left;
+        if (!lag_path.empty() && lag_left < m) m = lag_left;
         rc = kmc_step(s, m, obs.data() + done);
         if (rc) return die(s, rc, "kmc_step");
         done += m;
         dyn_left -= m;
         kin_left -= m;
         cf_left -= m;
+        lag_left -= m;
         if (!dyn_path.empty() && (dyn_left == 0 || done == n)) {
           rc = kmc_track_update(s, nullptr);
           if (rc) return die(s, rc, "track update");
@@ -346,6 +390,11 @@ int main(int argc, char** argv) {
           rc = kmc_cf_update(s, nullptr);
           if (rc) return die(s, rc, "growth update");
           cf_left = cf_every;
+        }
+        if (!lag_path.empty() && lag_left == 0) {
+          rc = kmc_lag_update(s, nullptr);
+          if (rc) return die(s, rc, "lag update");
+          lag_left = lag_cfg.every;
         }
       }
     }
@@ -527,6 +576,32 @@ int main(int argc, char** argv) {
           if (ns[q] || expo[q] || prod[q] || par[q])
             fprintf(f, "sizes %lld %zu %lld %lld %lld %lld\n", (long long)step, q, (long long)ns[q], (long long)expo[q],
                     (long long)prod[q], (long long)par[q]);
+        fclose(f);
+      }
+      if (!lag_path.empty()) {
+        kmc_lag_out k;
+        std::vector<kmc_lag_cell> table((size_t)KMC_LAG_MAX_ROWS * KMC_LAG_CLASSES);
+        int64_t n_pairs[KMC_LAG_MAX_ROWS];
+        rc = kmc_lag_sample(s, &k, table.data(), n_pairs);
+        if (rc) return die(s, rc, "lag sample");
+        f = fopen(lag_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, lag_path.c_str());
+        fprintf(f, "lag %lld %lld %lld %d %d %d %lld %lld %lld %lld\n", (long long)step, (long long)k.origin_step,
+                (long long)k.n_updates, k.cfg.every, k.cfg.levels, k.cfg.slots, (long long)k.J, (long long)k.F,
+                (long long)k.BX, (long long)k.BY);
+        const int P = k.cfg.slots;
+        for (int r = 0; r < (int)k.rows; ++r) {
+          const int lv = r < P ? 0 : 1 + (r - P) / (P / 2);
+          const int64_t lag = (int64_t)(r < P ? r + 1 : P / 2 + 1 + (r - P) % (P / 2)) << lv;
+          for (int c = 0; c < KMC_LAG_CLASSES; ++c) {
+            const kmc_lag_cell& w = table[(size_t)r * KMC_LAG_CLASSES + c];
+            if (!(w.n_all || w.n_far)) continue;
+            fprintf(f, "cell %lld %lld %d %lld %d %lld %lld %lld %lld %s %s %s\n", (long long)step,
+                    (long long)k.origin_step, r, (long long)lag, c, (long long)n_pairs[r], (long long)w.n_all,
+                    (long long)w.n_clean, (long long)w.n_far, dec128(w.m2_all).c_str(), dec128(w.m2_clean).c_str(),
+                    dec128(w.m4_clean).c_str());
+          }
+        }
         fclose(f);
       }
     }

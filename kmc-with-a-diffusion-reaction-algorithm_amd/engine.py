@@ -149,6 +149,17 @@ def load_library(path: Optional[str] = None):
     L.kmc_rings_hops.argtypes = [C.c_void_p]
     L.kmc_host_network.argtypes = [P(capi.Params), P(capi.StateView)] + net
     L.kmc_host_rings.argtypes = [P(capi.Params), P(capi.StateView)] + rings
+    L.kmc_lag_begin.argtypes = [C.c_void_p, P(capi.LagConfig)]
+    L.kmc_lag_update.argtypes = [C.c_void_p, P(capi.LagInfo)]
+    L.kmc_lag_sample.argtypes = [C.c_void_p, P(capi.LagOut), C.c_void_p, C.c_void_p]
+    L.kmc_lag_arrays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kmc_lag_end.argtypes = [C.c_void_p]
+    L.kmc_host_lag_begin.argtypes = [P(capi.Params), P(capi.StateView), P(capi.LagConfig), P(capi.LagView),
+                                     P(capi.LagOut)]
+    L.kmc_host_lag_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.LagView), P(capi.LagOut),
+                                      P(capi.LagInfo)]
+    L.kmc_host_lag_sample.argtypes = [P(capi.Params), P(capi.LagView), P(capi.LagOut), P(capi.LagOut), C.c_void_p,
+                                      C.c_void_p]
     for f in ("kmc_host_math", "kmc_device_math"):
         getattr(L, f).argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
@@ -403,6 +414,39 @@ class HostCoag:
                                                       C.byref(self.acc), C.byref(self.tables.view()), C.byref(out),
                                                       C.byref(t.view())))
         return out, t
+
+
+class HostLag:
+    """The lag correlator on host states, sequentially (kmc_host_lag_*): Simulation.lag_*'s counterpart without a
+    device.  The recorder begins at hs (update 0); update(hs) advances it to the state `every` steps later.
+    arrays (capi.LagArrays) holds its per-protein state, the rings and the table."""
+
+    def __init__(self, params: capi.Params, hs: capi.HostState, config: capi.LagConfig):
+        self.params = params
+        ok = 1 <= config.levels <= capi.LAG_MAX_LEVELS and 2 <= config.slots <= capi.LAG_MAX_SLOTS
+        self.arrays = capi.LagArrays(params.n_a + params.n_b, config.levels if ok else 1, config.slots if ok else 2)
+        self.acc = capi.LagOut()
+        v = hs.view()
+        _host_check(load_library().kmc_host_lag_begin(C.byref(params), C.byref(v), C.byref(config),
+                                                      C.byref(self.arrays.view()), C.byref(self.acc)))
+
+    def update(self, hs: capi.HostState) -> capi.LagInfo:
+        """Advance the recorder to hs (kmc_host_lag_update)."""
+        v = hs.view()
+        info = capi.LagInfo()
+        _host_check(load_library().kmc_host_lag_update(C.byref(self.params), C.byref(v), C.byref(self.arrays.view()),
+                                                       C.byref(self.acc), C.byref(info)))
+        return info
+
+    def sample(self) -> capi.LagSample:
+        """The table as of the last update — kmc_host_lag_sample; a copy."""
+        out = capi.LagOut()
+        table = np.zeros_like(self.arrays.table)
+        n_pairs = np.zeros_like(self.arrays.n_pairs)
+        _host_check(load_library().kmc_host_lag_sample(C.byref(self.params), C.byref(self.arrays.view()),
+                                                       C.byref(self.acc), C.byref(out), table.ctypes.data,
+                                                       n_pairs.ctypes.data))
+        return capi.LagSample(out, table, n_pairs)
 
 
 def host_dd_check(gid: np.ndarray, own: np.ndarray) -> int:
@@ -667,7 +711,7 @@ class Simulation:
 
     @property
     def analysis_ms(self) -> float:
-        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / unwrap /
+        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / lag_* / unwrap /
         cluster_* / structure_factor / bond_order / bond_order_corr / network / rings call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
@@ -822,6 +866,56 @@ class Simulation:
             done += n
             out = self.cf_update()
         return recs, out
+
+    # ---- multi-origin lag correlator since a begin (kmc_lagcorr.hip)
+    def lag_begin(self, config: capi.LagConfig) -> None:
+        """Start the lag correlator at the current state (update 0; capi.lag_config builds the configuration).  It
+        allocates levels * slots * 16 bytes per protein, freed by lag_end."""
+        self._check(load_library().kmc_lag_begin(self._h, C.byref(config)))
+
+    def lag_update(self) -> capi.LagInfo:
+        """Correlate the current positions with every stored origin that is due and store the new origins; legal
+        exactly `every` steps after the last update (or the begin)."""
+        info = capi.LagInfo()
+        self._check(load_library().kmc_lag_update(self._h, C.byref(info)))
+        return info
+
+    def lag_sample(self) -> capi.LagSample:
+        """The table accumulated since lag_begin — kmc_lag_sample; analysis.lag_curves turns it into MSD, alpha_2
+        and F_s by lag time."""
+        out = capi.LagOut()
+        self._check(load_library().kmc_lag_sample(self._h, C.byref(out), None, None))
+        table = np.zeros((int(out.rows), capi.LAG_CLASSES), dtype=capi.LAG_CELL_DTYPE)
+        n_pairs = np.zeros(int(out.rows), dtype=np.int64)
+        self._check(load_library().kmc_lag_sample(self._h, C.byref(out), table.ctypes.data, n_pairs.ctypes.data))
+        return capi.LagSample(out, table, n_pairs)
+
+    def lag_arrays(self):
+        """(U[N, 2] int64, last_event[N] int32) by reference index (kmc_lag_arrays): diagnostics and tests."""
+        n = self.params.n_a + self.params.n_b
+        U = np.zeros((n, 2), dtype=np.int64)
+        last_event = np.zeros(n, dtype=np.int32)
+        self._check(load_library().kmc_lag_arrays(self._h, U.ctypes.data, last_event.ctypes.data))
+        return U, last_event
+
+    def lag_end(self) -> None:
+        self._check(load_library().kmc_lag_end(self._h))
+
+    def run_lagged(self, nsteps: int):
+        """Advance nsteps steps, `every` of the begun recorder's configuration at a time, with a lag_update after
+        each piece (nsteps must be a multiple of every).  Returns (records[nsteps], the last capi.LagInfo or None)."""
+        out = capi.LagOut()
+        self._check(load_library().kmc_lag_sample(self._h, C.byref(out), None, None))
+        every = int(out.cfg.every)
+        if nsteps < 0 or nsteps % every:
+            raise ValueError("run_lagged: nsteps >= 0, a multiple of the recorder's every")
+        recs = np.zeros(nsteps, dtype=capi.OBS_DTYPE)
+        done, info = 0, None
+        while done < nsteps:
+            self.step(every, recs[done:done + every])
+            done += every
+            info = self.lag_update()
+        return recs, info
 
     @property
     def current_step(self) -> int:
