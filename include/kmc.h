@@ -1079,6 +1079,134 @@ int kmc_host_lag_update(const kmc_params* p, const kmc_state_view* v, const kmc_
 int kmc_host_lag_sample(const kmc_params* p, const kmc_lag_view* view, const kmc_lag_out* acc, kmc_lag_out* out,
                         kmc_lag_cell* table, int64_t* n_pairs);
 
+/* Orientation layer: the rotational counterpart of the lag
+ * correlator, and a one-shot census of the ligands' poses.  Every layer above
+ * reads one point per protein; this one reads the rigid bodies' own vectors.
+ * kmc_rot_* keeps rings of packed body vectors on §18's multiple-tau schedule
+ * and correlates the current vectors with each stored origin that is due: per
+ * lag, class and vector the counts and the exact sums of d = u(t) . u(0) and of
+ * d^2, from which C_1 and C_2 follow.  It reads the CURRENT state, launches
+ * nothing inside kmc_step and leaves the state, the step counter and
+ * kmc_get_clusters' validity untouched; it is independent of the tracker and
+ * of the lag correlator.  All results are integers: the device, kmc_host_rot_*
+ * and the tests agree by equality, and the tables of replicas (and of
+ * consecutive recorders) add.
+ *
+ * Definitions — the device, the host counterparts and the tests share them:
+ *   quantisation    q(x) = (int64) round(x * 1024.0) per bead coordinate; a
+ *                   vector is the difference of two quantised beads.
+ *   receptor        heading H = (q[3][2] - q[3][1]) in x and y, z = 0 by
+ *                   definition: the xy projection (receptors stay vertical).
+ *   ligand          axis N = q[1][2] - q[1][1] (v = 0), arm A = q[2][1] -
+ *                   q[1][1] (v = 1), and C = q[3][1] - q[1][1]; the handedness
+ *                   chi = sign(N . (A x C)), an exact integer below 2^51.
+ *   bad             a protein with a component of H (or of N, A, C) of
+ *                   magnitude >= 2^16 quanta.  No valid state has one
+ *                   (ra_radius <= 20, rb_radius <= 30: the longest vector is the
+ *                   arm, 2 * 30 / sqrt 3 A = 35 473 quanta).  Its packed words
+ *                   are KMC_ROT_BAD, its chi is 0, it counts in n_bad and files
+ *                   no pair; a pair with a bad origin is not filed either.
+ *   packing         x, y, z as three signed 21-bit fields of one 64-bit word
+ *                   (x lowest); bit 63 is clear.  vec holds the current words:
+ *                   [n_a] headings, then [n_b] axes, then [n_b] arms; a ring
+ *                   entry is one such array, 8 n_a + 16 n_b bytes.
+ *   configuration   (kmc_rot_config) every >= 1; levels in 1..
+ *                   KMC_LAG_MAX_LEVELS; slots even in 2..KMC_LAG_MAX_SLOTS.
+ *   schedule, rows  kmc_lag_update's: levels, slots, tasks and rows alike.
+ *   kmc_rot_begin   is update n = 0: the current words are stored as the origin
+ *                   of update 0 in slot 0 of every level; the links and chi are
+ *                   the current ones, last_event = 0, the table is zeroed.
+ *   kmc_rot_update  n >= 1, legal `every` steps after the last update.  Per
+ *                   protein: an EVENT is a change of any of its three links (as
+ *                   the tracker names them) since the last update or, for a
+ *                   ligand, a chi that differs from the last update's (a FLIP:
+ *                   the mirror reflection at z = 0 and z = box_z is no
+ *                   rotation); last_event = n then.  The class is the lag
+ *                   correlator's, of the CURRENT state.  A pair of protein i
+ *                   with the origin stored at update n_k is CLEAN when
+ *                   last_event[i] <= n_k.  There is no jump test and no minimum
+ *                   image: a rigid body is wrapped as a whole.  Per (row,
+ *                   class, v) with d = u_v(n) . u_v(n_k), |d| < 3 2^32:
+ *                   n_all += 1, s1_all += d; for a clean pair n_clean += 1,
+ *                   s1_clean += d, s2_clean += d^2 (< 2^68).  n_pairs[row]
+ *                   counts the (origin, update) pairs filed.  Afterwards every
+ *                   level that fired stores the current words.  info: n of this
+ *                   update, its tasks, the proteins with an event, the flips
+ *                   and the bad proteins of this update.
+ *   kmc_rot_sample  copies the table [rows][KMC_LAG_CLASSES][KMC_ROT_VECS]
+ *                   (v = 1 of the receptor classes stays zero) and n_pairs
+ *                   [rows] (either may be NULL) out.
+ *   kmc_rot_arrays  vec [n_a + 2 n_b], last_event [N] and chi [N] (0 for a
+ *                   receptor; each may be NULL) by reference index.
+ *   kmc_rot_end     drops the recorder and frees its memory; idempotent.
+ *   kmc_ligand_pose one-shot, no recorder: for every ligand that is not bad one
+ *                   count in hist[k][z bin][tilt bin] (hist [4][nz][nc], zeroed
+ *                   by the call; may be NULL), k = its occupied sites 0..3 (the
+ *                   links in range).  With BZ = q(box_z), Lq = q(rb_radius), Z
+ *                   = q(z of [1][1]): z bin = 0 for Z <= 0, nz - 1 for Z >= BZ,
+ *                   else min(nz - 1, Z nz / BZ); tilt bin = (N_z + Lq) nc /
+ *                   (2 Lq + 1) clamped to [0, nc - 1] (a laid-down ligand, N_z
+ *                   = Lq, lies in the top bin).  out: the ligands of chi = +1
+ *                   and chi = -1 per k, and n_bad.  1 <= nz, nc <=
+ *                   KMC_POSE_MAX_BINS.
+ * kmc_analysis_ms covers the last call.  The recorder is not checkpointed.
+ * kmc_host_rot_* / kmc_host_ligand_pose: the same from host state views,
+ * sequentially, no device; the caller owns the arrays of the kmc_rot_view.
+ * KMC_ERR_ARG for a null / out-of-range argument, a handle without state, a
+ * decomposed window, an update off the stride and a recorder that was not
+ * begun; a new state drops the recorder. */
+#define KMC_ROT_VECS 2
+#define KMC_ROT_BAD 0x8000000000000000ull
+#define KMC_POSE_MAX_BINS 64
+#define KMC_POSE_CLASSES 4
+typedef struct kmc_rot_config {
+  int32_t every, levels, slots;
+} kmc_rot_config;
+typedef struct kmc_rot_info {
+  int64_t n_updates; /* n of this update */
+  int64_t n_tasks;   /* (level, j) pairs it filed */
+  int64_t n_events;  /* proteins with last_event = n */
+  int64_t n_flips;   /* ligands whose chi changed */
+  int64_t n_bad;     /* bad proteins of this update */
+} kmc_rot_info;
+typedef struct kmc_rot_cell {
+  int64_t n_all, n_clean;
+  kmc_i128 s1_all, s1_clean, s2_clean;
+} kmc_rot_cell;
+typedef struct kmc_rot_out {
+  kmc_rot_config cfg;
+  int32_t pad_;
+  int64_t origin_step, last_step, n_updates;
+  int64_t rows;
+} kmc_rot_out;
+typedef struct kmc_rot_view {
+  uint64_t* vec;        /* [n_a + 2 n_b] */
+  int32_t* links;       /* [3][N] */
+  int32_t* last_event;  /* [N] */
+  int8_t* chi;          /* [N] */
+  uint64_t* ring;       /* [levels][slots][n_a + 2 n_b] */
+  kmc_rot_cell* table;  /* [rows][KMC_LAG_CLASSES][KMC_ROT_VECS] */
+  int64_t* n_pairs;     /* [rows] */
+} kmc_rot_view;
+typedef struct kmc_pose_out {
+  int64_t chi_pos[KMC_POSE_CLASSES], chi_neg[KMC_POSE_CLASSES];
+  int64_t n_bad;
+} kmc_pose_out;
+int kmc_rot_begin(kmc_sim* s, const kmc_rot_config* cfg);
+int kmc_rot_update(kmc_sim* s, kmc_rot_info* info);
+int kmc_rot_sample(kmc_sim* s, kmc_rot_out* out, kmc_rot_cell* table /* [rows][5][2] */, int64_t* n_pairs /* [rows] */);
+int kmc_rot_arrays(kmc_sim* s, uint64_t* vec /* [n_a + 2 n_b] */, int32_t* last_event /* [N] */, int8_t* chi /* [N] */);
+int kmc_rot_end(kmc_sim* s);
+int kmc_ligand_pose(kmc_sim* s, int32_t nz, int32_t nc, int64_t* hist /* [4][nz][nc] */, kmc_pose_out* out);
+int kmc_host_rot_begin(const kmc_params* p, const kmc_state_view* v, const kmc_rot_config* cfg,
+                       const kmc_rot_view* view, kmc_rot_out* acc);
+int kmc_host_rot_update(const kmc_params* p, const kmc_state_view* v, const kmc_rot_view* view, kmc_rot_out* acc,
+                        kmc_rot_info* info);
+int kmc_host_rot_sample(const kmc_params* p, const kmc_rot_view* view, const kmc_rot_out* acc, kmc_rot_out* out,
+                        kmc_rot_cell* table, int64_t* n_pairs);
+int kmc_host_ligand_pose(const kmc_params* p, const kmc_state_view* v, int32_t nz, int32_t nc, int64_t* hist,
+                         kmc_pose_out* out);
+
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */
 int kmc_format_bond_line(const kmc_params* p, const kmc_obs* o, char* buf, size_t n);   /* main.cpp:2251 */

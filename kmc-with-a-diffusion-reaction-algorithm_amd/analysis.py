@@ -487,3 +487,63 @@ def lag_curves(sample, time_step: float) -> dict:
             if m2:
                 out["alpha2"][r, c] = (m4 * n) / (2 * m2 * m2) - 1.0
     return out
+
+
+def rot_lengths(p) -> np.ndarray:
+    """|u|^2 [5, 2] in quanta^2 (2^-20 A^2) per class and vector from the nominal lengths of the parameters: R_A for a
+    heading, R_B for a ligand's axis, 2 R_B / sqrt 3 for its arm; 0 for v = 1 of a receptor class."""
+    ra2 = (float(p.ra_radius) * 1024.0) ** 2
+    rb2 = (float(p.rb_radius) * 1024.0) ** 2
+    return np.array([[ra2, 0.0]] * 3 + [[rb2, 4.0 * rb2 / 3.0]] * 2)
+
+
+def rot_curves(sample, p) -> dict:
+    """C_1 and C_2 by lag time from a rot_sample (a capi.RotSample; sum samples over replicas or windows first:
+    reduce_counts on counts(), then from_counts); p: the parameters (time_step, ra_radius, rb_radius).  Per row r,
+    class c and vector v (0: heading / axis, 1: arm), over the clean pairs, with d = u(t) . u(0):
+      tau[r]          = lag[r] * every * time_step,
+      c1[r, c, v]     = s1_clean / (n_clean |u|^2)                         = <cos>,
+      c2[r, c, v]     = 2 s2_clean / (n_clean |u|^4) - 1 for a heading (c < 3; two dimensions: <cos 2 phi>),
+                        (3 s2_clean / (n_clean |u|^4) - 1) / 2 for a ligand's vectors (<P_2(cos)>),
+      c1_all[r, c, v] = s1_all / (n_all |u|^2), the pairs with events (link changes, reflections) included,
+      clean_fraction[r, c, v] = n_clean / n_all,
+    and n_clean, n_pairs as float arrays.  Zeros where a denominator is zero.  |u| is the NOMINAL length (rot_lengths),
+    not the quantised one: each component of a vector is the difference of two coordinates rounded to 2^-10 A, off by
+    at most 2^-10 A, so d is off by at most 2 sqrt(3) 2^-10 |u| + 3 2^-20 A^2 and c1 of a pair at rest reads 1 within
+    2 sqrt(3) 2^-10 / |u| + 3 2^-20 / |u|^2 (2e-4 at R_A = 20 A).  The integer sums are divided whole (Python ints
+    to float once)."""
+    s = sample
+    shape = (s.rows, capi.LAG_CLASSES, capi.ROT_VECS)
+    u2 = rot_lengths(p)
+    out = dict(tau=np.asarray(s.lags, dtype=np.float64) * float(s.every) * float(p.time_step),
+               c1=np.zeros(shape), c2=np.zeros(shape), c1_all=np.zeros(shape), clean_fraction=np.zeros(shape),
+               n_clean=np.zeros(shape), n_pairs=np.array([float(x) for x in s.n_pairs]))
+    for r, c, v in np.ndindex(*shape):
+        n, na, L2 = int(s.n_clean[r, c, v]), int(s.n_all[r, c, v]), float(u2[c, v])
+        out["n_clean"][r, c, v] = n
+        if L2 == 0.0:
+            continue
+        if na:
+            out["c1_all"][r, c, v] = int(s.s1_all[r, c, v]) / (na * L2)
+            out["clean_fraction"][r, c, v] = n / na
+        if n:
+            out["c1"][r, c, v] = int(s.s1_clean[r, c, v]) / (n * L2)
+            m = int(s.s2_clean[r, c, v]) / (n * L2 * L2)
+            out["c2"][r, c, v] = 2.0 * m - 1.0 if c < 3 else (3.0 * m - 1.0) / 2.0
+    return out
+
+
+def pose_profile(hist, p) -> dict:
+    """The ligands' pose census (Simulation.ligand_pose's hist [4, nz, nc]) normalised: z[nz] the centres of the
+    height bins of bead [1][1] in A over [0, box_z], cos[nc] the centres of the tilt bins as N_z / R_B over [-1, 1]
+    (the integers N_z = -Lq .. Lq taken as unit cells around themselves, bin k covers (k .. k + 1) (2 Lq + 1) / nc - Lq
+    - 1/2 quanta, Lq = round(1024 R_B): the bins are symmetric about 0), n[4] the ligands per number of
+    occupied sites, pdf[4, nz, nc] = hist / n (zeros where n is zero), and its marginals pdf_z[4, nz], pdf_cos[4, nc]."""
+    h = np.asarray(hist, dtype=np.float64)
+    _, nz, nc = h.shape
+    lq = float(np.floor(float(p.rb_radius) * 1024.0 + 0.5))
+    edges = np.arange(nc + 1) * (2.0 * lq + 1.0) / nc - lq - 0.5
+    n = h.sum(axis=(1, 2))
+    pdf = np.divide(h, n[:, None, None], out=np.zeros_like(h), where=n[:, None, None] > 0)
+    return dict(z=(np.arange(nz) + 0.5) * float(p.box_z) / nz, cos=0.5 * (edges[:-1] + edges[1:]) / lq, n=n, pdf=pdf,
+                pdf_z=pdf.sum(axis=2), pdf_cos=pdf.sum(axis=1))

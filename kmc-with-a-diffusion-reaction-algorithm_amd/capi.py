@@ -631,6 +631,138 @@ class LagArrays:
         return v
 
 
+ROT_VECS, POSE_MAX_BINS, POSE_CLASSES = 2, 64, 4  # KMC_ROT_VECS, KMC_POSE_MAX_BINS, KMC_POSE_CLASSES
+ROT_BAD = 1 << 63                                  # KMC_ROT_BAD: the packed word of a bad protein's vector
+
+
+class RotConfig(C.Structure):
+    """kmc_rot_config — the orientation recorder's configuration."""
+
+    _fields_ = [("every", C.c_int32), ("levels", C.c_int32), ("slots", C.c_int32)]
+
+
+def rot_config(every: int, levels: int, slots: int) -> RotConfig:
+    return RotConfig(int(every), int(levels), int(slots))
+
+
+class RotInfo(C.Structure):
+    """kmc_rot_info — one update: its number n, the (level, j) pairs filed, the proteins with an event, the ligands
+    whose handedness flipped, the bad proteins."""
+
+    _fields_ = [(name, C.c_int64) for name in ("n_updates", "n_tasks", "n_events", "n_flips", "n_bad")]
+
+
+class RotOut(C.Structure):
+    """kmc_rot_out — the configuration, the steps and the update count."""
+
+    _fields_ = [("cfg", RotConfig), ("pad_", C.c_int32)] + [(name, C.c_int64) for name in (
+        "origin_step", "last_step", "n_updates", "rows")]
+
+
+class RotView(C.Structure):
+    """kmc_rot_view — caller-owned arrays of the recorder on the host."""
+
+    _fields_ = [("vec", C.POINTER(C.c_uint64)), ("links", C.POINTER(C.c_int32)), ("last_event", C.POINTER(C.c_int32)),
+                ("chi", C.POINTER(C.c_int8)), ("ring", C.POINTER(C.c_uint64)), ("table", C.c_void_p),
+                ("n_pairs", C.POINTER(C.c_int64))]
+
+
+class PoseOut(C.Structure):
+    """kmc_pose_out — the ligands of chi = +1 / -1 per number of occupied sites, and the bad ones."""
+
+    _fields_ = [("chi_pos", C.c_int64 * POSE_CLASSES), ("chi_neg", C.c_int64 * POSE_CLASSES), ("n_bad", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {"chi_pos": [int(x) for x in self.chi_pos], "chi_neg": [int(x) for x in self.chi_neg],
+                "n_bad": int(self.n_bad)}
+
+
+# kmc_rot_cell as a numpy record
+ROT_CELL_DTYPE = np.dtype([("n_all", "<i8"), ("n_clean", "<i8"), ("s1_all", I128_DTYPE), ("s1_clean", I128_DTYPE),
+                           ("s2_clean", I128_DTYPE)])
+assert ROT_CELL_DTYPE.itemsize == 64
+ROT_COUNTS = ("n_all", "n_clean")
+ROT_SUMS = ("s1_all", "s1_clean", "s2_clean")
+
+
+def rot_unpack(words) -> np.ndarray:
+    """[..., 3] int64 (x, y, z) of packed vector words (three signed 21-bit fields); a ROT_BAD word is not a vector."""
+    w = np.asarray(words, dtype=np.uint64)
+    f = [(w >> np.uint64(s) & np.uint64(0x1FFFFF)).astype(np.int64) for s in (0, 21, 42)]
+    return np.stack([np.where(x >= 1 << 20, x - (1 << 21), x) for x in f], axis=-1)
+
+
+class RotSample:
+    """One kmc_rot_sample: the configuration and steps (as attributes and in .out), n_pairs [rows] and, as arrays of
+    Python ints (the 128-bit sums whole): n_all, n_clean, s1_all, s1_clean, s2_clean [rows, 5, 2] (class, vector:
+    0 heading / axis, 1 arm).  counts() / from_counts(): the sample as one int64 vector that adds
+    (analysis.reduce_counts)."""
+
+    def __init__(self, out: RotOut, table: np.ndarray, n_pairs: np.ndarray):
+        self.out = out
+        self.every, self.levels, self.slots = out.cfg.every, out.cfg.levels, out.cfg.slots
+        for name in ("origin_step", "last_step", "n_updates", "rows"):
+            setattr(self, name, int(getattr(out, name)))
+        self.lags = lag_row_lags(self.levels, self.slots)
+        self.n_pairs = np.array([int(x) for x in n_pairs], dtype=object)
+        for name in ROT_COUNTS:
+            setattr(self, name, table[name].astype(object))
+        for name in ROT_SUMS:
+            setattr(self, name, _i128_ints(table[name]))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name in ROT_COUNTS + ROT_SUMS + ("n_pairs",)}
+
+    def counts(self) -> np.ndarray:
+        """[rows + rows * 5 * 2 * (2 + 4 * 3)] int64: n_pairs, then per cell the counts and every sum's limbs."""
+        v = [int(x) for x in self.n_pairs]
+        for idx in np.ndindex(self.rows, LAG_CLASSES, ROT_VECS):
+            v += [int(getattr(self, name)[idx]) for name in ROT_COUNTS]
+            for name in ROT_SUMS:
+                x = int(getattr(self, name)[idx])
+                v += [x >> 32 * k & 0xFFFFFFFF for k in range(LAG_LIMBS - 1)] + [x >> 32 * (LAG_LIMBS - 1)]
+        return np.array(v, dtype=np.int64)
+
+    def from_counts(self, counts) -> "RotSample":
+        """A sample of this one's configuration holding the (summed) counts() vector."""
+        import copy
+        s = copy.copy(self)
+        it = iter(int(x) for x in np.asarray(counts).ravel())
+        s.n_pairs = np.array([next(it) for _ in range(self.rows)], dtype=object)
+        shape = (self.rows, LAG_CLASSES, ROT_VECS)
+        for name in ROT_COUNTS + ROT_SUMS:
+            setattr(s, name, np.zeros(shape, dtype=object))
+        for idx in np.ndindex(*shape):
+            for name in ROT_COUNTS:
+                getattr(s, name)[idx] = next(it)
+            for name in ROT_SUMS:
+                getattr(s, name)[idx] = sum(next(it) << 32 * k for k in range(LAG_LIMBS))
+        return s
+
+
+class RotArrays:
+    """numpy-backed kmc_rot_view for n_a receptors and n_b ligands: vec [n_a + 2 n_b] (headings, axes, arms), links
+    [3, n], last_event [n], chi [n], ring [levels, slots, n_a + 2 n_b], table [rows, 5, 2] (ROT_CELL_DTYPE), n_pairs
+    [rows]."""
+
+    def __init__(self, n_a: int, n_b: int, levels: int, slots: int):
+        rows, n, w = lag_rows(levels, slots), n_a + n_b, n_a + 2 * n_b
+        self.vec = np.zeros(w, dtype=np.uint64)
+        self.links = np.zeros((3, n), dtype=np.int32)
+        self.last_event = np.zeros(n, dtype=np.int32)
+        self.chi = np.zeros(n, dtype=np.int8)
+        self.ring = np.zeros((levels, slots, w), dtype=np.uint64)
+        self.table = np.zeros((rows, LAG_CLASSES, ROT_VECS), dtype=ROT_CELL_DTYPE)
+        self.n_pairs = np.zeros(rows, dtype=np.int64)
+
+    def view(self) -> RotView:
+        v = RotView()
+        for name, ptr in RotView._fields_:
+            a = getattr(self, name)
+            setattr(v, name, a.ctypes.data if ptr is C.c_void_p else a.ctypes.data_as(ptr))
+        return v
+
+
 DD_ROW = 416     # KMC_DD_ROW: one exchanged protein (48 doubles + 8 int32)
 DD_JCAP = 256    # KMC_DD_JCAP
 DD_XCAP = 64     # KMC_DD_XCAP

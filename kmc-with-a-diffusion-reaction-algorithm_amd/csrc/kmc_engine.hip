@@ -25,6 +25,7 @@
 #include "kmc_coag.hip"
 #include "kmc_rings.hip"
 #include "kmc_lagcorr.hip"
+#include "kmc_orient.hip"
 
 using namespace kmcd;
 
@@ -161,6 +162,8 @@ struct __attribute__((visibility("hidden"))) kmc_sim {
   CfState cf;
   RgState rg;
   LagState lag;
+  RotState rot;
+  PoseState pose;
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   double an_ms = 0.0;
 };
@@ -811,6 +814,7 @@ static int set_state_impl(kmc_sim* s, const kmc_state_view* v) {
   s->kin.rec.on = false;  // and so did the kinetics recorder's links
   s->cf.rec.on = false;   // and the growth recorder's bonds and clusters
   s->lag.rec.on = false;  // and the lag correlator's origins
+  s->rot.rec.on = false;  // and the orientation recorder's
   return KMC_OK;
 }
 

@@ -25,6 +25,7 @@
 #include "kmc_host.h"
 #include "kmc_kinetics.h"
 #include "kmc_lagcorr.h"
+#include "kmc_orient.h"
 #include "kmc_math.h"
 #include "kmc_params_check.h"
 #include "kmc_philox.h"
@@ -1911,6 +1912,210 @@ int kmc_host_lag_sample(const kmc_params* p, const kmc_lag_view* view, const kmc
   *out = a;
   if (table && table != view->table) std::copy(view->table, view->table + (size_t)a.rows * LAG_CLASSES, table);
   if (n_pairs && n_pairs != view->n_pairs) std::copy(view->n_pairs, view->n_pairs + a.rows, n_pairs);
+  return KMC_OK;
+}
+
+// Orientation layer (include/kmc.h): kmc_rot_*'s and
+// kmc_ligand_pose's definitions on host state views, one protein after the
+// other; the vectors, the packing, the pair term and the bins are
+// kmc_orient.h's, the ones the device evaluates.  Every sum is taken whole.
+extern "C++" {
+namespace {
+
+bool rot_view_ok(const kmc_rot_view* w) {
+  return w && w->vec && w->links && w->last_event && w->chi && w->ring && w->table && w->n_pairs;
+}
+
+// protein i's packed words, handedness and links; false for a bad protein.  Z, Nz as rot_vectors' (kmc_orient.hip)
+bool rot_host_cur(const kmc_params* p, const kmc_state_view* v, int i, uint64_t w[2], int* chi, int32_t l[3], int64_t* Z,
+                  int64_t* Nz) {
+  const int na = p->n_a, nb = p->n_b;
+  int64_t X[2];
+  lag_host_cur(p, v, i, X, l);
+  *chi = 0;
+  *Z = *Nz = 0;
+  if (i < na) {
+    const double b31[2] = {v->ra[RA(na, 3, 1, 0, i)], v->ra[RA(na, 3, 1, 1, i)]};
+    const double b32[2] = {v->ra[RA(na, 3, 2, 0, i)], v->ra[RA(na, 3, 2, 1, i)]};
+    const kmco::V3 h = kmco::heading(b31, b32);
+    const bool ok = kmco::fits(h);
+    w[0] = ok ? kmco::pack(h) : ROT_BAD;
+    w[1] = 0;
+    return ok;
+  }
+  const int b = i - na;
+  double bead[4][3];
+  const int jk[4][2] = {{1, 1}, {1, 2}, {2, 1}, {3, 1}};
+  for (int m = 0; m < 4; ++m)
+    for (int c = 0; c < 3; ++c) bead[m][c] = v->rb[RB(nb, jk[m][0], jk[m][1], c, b)];
+  const kmco::Lig g = kmco::ligand(bead[0], bead[1], bead[2], bead[3]);
+  const bool ok = kmco::fits(g);
+  w[0] = ok ? kmco::pack(g.n) : ROT_BAD;
+  w[1] = ok ? kmco::pack(g.a) : ROT_BAD;
+  if (ok) *chi = kmco::chi(g.n, g.a, g.c);
+  *Z = kmco::q(bead[0][2]);
+  *Nz = g.n.z;
+  return ok;
+}
+
+size_t rot_at(size_t i, int v, size_t na, size_t nb) { return i < na ? i : na + (size_t)v * nb + (i - na); }
+
+}  // namespace
+}  // extern "C++"
+
+int kmc_host_rot_begin(const kmc_params* p, const kmc_state_view* v, const kmc_rot_config* cfg,
+                       const kmc_rot_view* view, kmc_rot_out* acc) {
+  if (!p || !v || !v->ra || !v->rb || !v->a_int || !v->b_int || !cfg || !rot_view_ok(view) || !acc) {
+    g_host_err = "rot: params, state, the configuration, the view's seven arrays and acc are needed";
+    return KMC_ERR_ARG;
+  }
+  const kmc_rot_config c = *cfg;
+  const char* bad = kmco::check(c.every, c.levels, c.slots);
+  if (bad) {
+    g_host_err = bad;
+    return KMC_ERR_ARG;
+  }
+  const size_t na = (size_t)p->n_a, nb = (size_t)p->n_b, N = na + nb, W = na + 2 * nb;
+  const int L = c.levels, P = c.slots, rows = kmcl::rows(L, P);
+  for (size_t i = 0; i < N; ++i) {
+    uint64_t w[2];
+    int chi;
+    int32_t l[3];
+    int64_t Z, Nz;
+    rot_host_cur(p, v, (int)i, w, &chi, l, &Z, &Nz);
+    for (int k = 0; k < (i < na ? 1 : 2); ++k) {
+      const size_t at = rot_at(i, k, na, nb);
+      view->vec[at] = w[k];
+      for (int lv = 0; lv < L; ++lv) view->ring[(size_t)(lv * P) * W + at] = w[k];
+    }
+    for (int k = 0; k < 3; ++k) view->links[(size_t)k * N + i] = l[k];
+    view->last_event[i] = 0;
+    view->chi[i] = (int8_t)chi;
+  }
+  std::memset(view->table, 0, sizeof(kmc_rot_cell) * (size_t)rows * LAG_CLASSES * ROT_VECS);
+  std::fill(view->n_pairs, view->n_pairs + rows, (int64_t)0);
+  std::memset(acc, 0, sizeof *acc);
+  acc->cfg = c;
+  acc->origin_step = acc->last_step = v->step;
+  acc->rows = rows;
+  return KMC_OK;
+}
+
+int kmc_host_rot_update(const kmc_params* p, const kmc_state_view* v, const kmc_rot_view* view, kmc_rot_out* acc,
+                        kmc_rot_info* info) {
+  if (!p || !v || !v->ra || !v->rb || !v->a_int || !v->b_int || !rot_view_ok(view) || !acc) {
+    g_host_err = "rot: params, state, the view's seven arrays and acc are needed";
+    return KMC_ERR_ARG;
+  }
+  if (v->step != acc->last_step + acc->cfg.every || acc->n_updates >= INT32_MAX) {
+    g_host_err = "rot: an update is due " + std::to_string(acc->cfg.every) + " steps after the last one";
+    return KMC_ERR_ARG;
+  }
+  const size_t na = (size_t)p->n_a, nb = (size_t)p->n_b, N = na + nb, W = na + 2 * nb;
+  const int L = acc->cfg.levels, P = acc->cfg.slots;
+  const int64_t n = acc->n_updates + 1;
+  kmcl::Task tasks[LAG_MAX_ROWS];
+  const int nt = kmcl::tasks(n, L, P, tasks);
+  int64_t n_events = 0, n_flips = 0, n_bad = 0;
+  for (size_t i = 0; i < N; ++i) {
+    uint64_t w[2];
+    int chi;
+    int32_t l[3];
+    int64_t Z, Nz;
+    const bool ok = rot_host_cur(p, v, (int)i, w, &chi, l, &Z, &Nz);
+    const int nv = i < na ? 1 : 2;
+    if (!ok) ++n_bad;
+    const bool flip = view->chi[i] != (int8_t)chi;
+    view->chi[i] = (int8_t)chi;
+    bool ev = flip;
+    for (int k = 0; k < 3; ++k) {
+      int32_t* q = &view->links[(size_t)k * N + i];
+      ev = ev || *q != l[k];
+      *q = l[k];
+    }
+    if (flip) ++n_flips;
+    if (ev) {
+      view->last_event[i] = (int32_t)n;
+      ++n_events;
+    }
+    const int c = kmcl::cls(i < na, l);
+    for (int k = 0; k < nv; ++k) {
+      const size_t at = rot_at(i, k, na, nb);
+      view->vec[at] = w[k];
+      const kmco::V3 u = kmco::unpack(w[k]);
+      for (int t = 0; ok && t < nt; ++t) {
+        const uint64_t o = view->ring[(size_t)tasks[t].ring * W + at];
+        if (o & ROT_BAD) continue;
+        const int64_t d = kmco::dot(u, kmco::unpack(o));
+        kmc_rot_cell* cell = &view->table[((size_t)tasks[t].row * LAG_CLASSES + c) * ROT_VECS + k];
+        cell->n_all += 1;
+        lag_add(&cell->s1_all, (__int128)d);
+        if (view->last_event[i] > tasks[t].nk) continue;
+        cell->n_clean += 1;
+        lag_add(&cell->s1_clean, (__int128)d);
+        uint64_t a2, ab, b2;
+        kmco::split(d, &a2, &ab, &b2);
+        lag_add(&cell->s2_clean, (__int128)kmco::sq(a2, ab, b2));
+      }
+      for (int lv = 0; lv < L && kmcl::fires(n, lv); ++lv) view->ring[(size_t)kmcl::store_ring(n, lv, P) * W + at] = w[k];
+    }
+  }
+  for (int t = 0; t < nt; ++t) view->n_pairs[tasks[t].row] += 1;
+  acc->last_step = v->step;
+  acc->n_updates = n;
+  if (info) {
+    info->n_updates = n;
+    info->n_tasks = nt;
+    info->n_events = n_events;
+    info->n_flips = n_flips;
+    info->n_bad = n_bad;
+  }
+  return KMC_OK;
+}
+
+int kmc_host_rot_sample(const kmc_params* p, const kmc_rot_view* view, const kmc_rot_out* acc, kmc_rot_out* out,
+                        kmc_rot_cell* table, int64_t* n_pairs) {
+  if (!p || !rot_view_ok(view) || !acc || !out) {
+    g_host_err = "rot sample: params, the view's seven arrays, acc and out are needed";
+    return KMC_ERR_ARG;
+  }
+  const kmc_rot_out a = *acc;  // (out may be acc itself)
+  *out = a;
+  if (table && table != view->table)
+    std::copy(view->table, view->table + (size_t)a.rows * LAG_CLASSES * ROT_VECS, table);
+  if (n_pairs && n_pairs != view->n_pairs) std::copy(view->n_pairs, view->n_pairs + a.rows, n_pairs);
+  return KMC_OK;
+}
+
+int kmc_host_ligand_pose(const kmc_params* p, const kmc_state_view* v, int32_t nz, int32_t nc, int64_t* hist,
+                         kmc_pose_out* out) {
+  if (!p || !v || !v->ra || !v->rb || !v->a_int || !v->b_int || !out) {
+    g_host_err = "pose: params, state and out are needed";
+    return KMC_ERR_ARG;
+  }
+  int64_t BZ, Lq;
+  const char* bad = kmco::pose_check(nz, nc, p->box_z, p->rb_radius, &BZ, &Lq);
+  if (bad) {
+    g_host_err = bad;
+    return KMC_ERR_ARG;
+  }
+  if (hist) std::fill(hist, hist + (size_t)POSE_CLASSES * nz * nc, (int64_t)0);
+  std::memset(out, 0, sizeof *out);
+  for (int b = 0; b < p->n_b; ++b) {
+    uint64_t w[2];
+    int chi;
+    int32_t l[3];
+    int64_t Z, Nz;
+    const bool ok = rot_host_cur(p, v, p->n_a + b, w, &chi, l, &Z, &Nz);
+    const int k = (l[0] != 0) + (l[1] != 0) + (l[2] != 0);
+    if (!ok) {
+      out->n_bad += 1;
+      continue;
+    }
+    if (chi > 0) out->chi_pos[k] += 1;
+    if (chi < 0) out->chi_neg[k] += 1;
+    if (hist) hist[((size_t)k * nz + kmco::pose_zbin(Z, BZ, nz)) * nc + kmco::pose_tbin(Nz, Lq, nc)] += 1;
+  }
   return KMC_OK;
 }
 

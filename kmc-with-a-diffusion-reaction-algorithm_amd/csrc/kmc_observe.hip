@@ -1,6 +1,6 @@
 // kmc_observe.hip — the host side of the read-only layers over the committed
-// state (DESIGN.md §10-§18): their C-ABI calls, one section a layer, over the
-// kernels and the state structs of kmc_analysis.hip ... kmc_lagcorr.hip.  Nothing
+// state (DESIGN.md §10-§19): their C-ABI calls, one section a layer, over the
+// kernels and the state structs of kmc_analysis.hip ... kmc_orient.hip.  Nothing
 // here writes a buffer a step reads, so the trajectory, the step counter and
 // clusters_valid stay as they are.
 //
@@ -1544,6 +1544,174 @@ int kmc_lag_arrays(kmc_sim* s, int64_t* U, int32_t* last_event) {
 
 int kmc_lag_end(kmc_sim* s) {
   return s ? rec_end(s, s->lag) : KMC_ERR_ARG;
+}
+
+// ---------------------------------------------------------------- orientation
+// kmc_orient.hip: the rotational recorder, on the lag correlator's schedule and
+// with its life cycle (begin allocates the rings, end frees them), and the
+// one-shot pose census, whose buffer stays with the handle.
+
+static_assert(KMC_ROT_VECS == ROT_VECS && KMC_ROT_BAD == ROT_BAD && KMC_POSE_MAX_BINS == POSE_MAX_BINS &&
+                  KMC_POSE_CLASSES == POSE_CLASSES,
+              "kmc.h and kmc_orient.h agree");
+static_assert(sizeof(kmc_rot_cell) == sizeof(lag_u64) * ROT_CELL, "a table cell is ROT_CELL words");
+static_assert(offsetof(kmc_rot_cell, s1_all) == 16 && offsetof(kmc_rot_cell, s1_clean) == 32 &&
+                  offsetof(kmc_rot_cell, s2_clean) == 48,
+              "kmc_rot_cell is the layout rot_flush adds into");
+static_assert(sizeof(kmc_pose_out) == sizeof(lag_u64) * (2 * POSE_CLASSES + 1), "kmc_pose_out is k_pose's nine counters");
+
+static const char* const ROT_OFF = "rot: not begun (kmc_rot_begin; a new state drops the recorder)";
+
+int kmc_rot_begin(kmc_sim* s, const kmc_rot_config* cfg) {
+  if (!s) return KMC_ERR_ARG;
+  if (!cfg) return fail(s, KMC_ERR_ARG, "rot: the configuration is needed");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const kmc_rot_config c = *cfg;
+  const char* bad = kmco::check(c.every, c.levels, c.slots);
+  if (bad) return fail(s, KMC_ERR_ARG, bad);
+  // a recorder that was on ends here, whatever becomes of this call
+  rc = rec_end(s, s->rot);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N, W = (size_t)s->K.NA + 2 * (size_t)s->K.NB;
+  const int L = c.levels, P = c.slots, rows = kmcl::rows(L, P);
+  Scratch& g = s->rot.scratch;
+  rc = KMC_OK;
+  rc |= salloc(s, g, &s->rot.dev.vec, W);
+  rc |= salloc(s, g, &s->rot.dev.links, 3 * N);
+  rc |= salloc(s, g, &s->rot.dev.last_event, N);
+  rc |= salloc(s, g, &s->rot.dev.chi, N);
+  rc |= salloc(s, g, &s->rot.dev.cls, N);
+  rc |= salloc(s, g, &s->rot.tasks, (size_t)LAG_MAX_ROWS);
+  rc |= salloc(s, g, &s->rot.table, (size_t)rows * LAG_CLASSES * ROT_VECS * ROT_CELL);
+  rc |= salloc(s, g, &s->rot.counts, 3);
+  if (rc == KMC_OK) rc |= salloc(s, g, &s->rot.dev.ring, (size_t)L * P * W);
+  if (rc != KMC_OK) {
+    scratch_drop(s, s->rot);
+    return fail(s, KMC_ERR_HIP, "rot: allocation failed (the rings take levels * slots * (8 n_a + 16 n_b) bytes)");
+  }
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  if (N > 0) k_rot_begin<<<(unsigned)((N + ROT_T - 1) / ROT_T), ROT_T, 0, s->stream>>>(s->K, s->d, s->rot.dev, L, P);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  s->rot.cfg = c;
+  s->rot.a.L = L;
+  s->rot.a.P = P;
+  s->rot.rec = Recorder{true, s->step_done, s->step_done, 0};
+  return KMC_OK;
+}
+
+int kmc_rot_update(kmc_sim* s, kmc_rot_info* info) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = rec_check(s, s->rot.rec, ROT_OFF);
+  if (rc != KMC_OK) return rc;
+  RotState& g = s->rot;
+  if (s->step_done != g.rec.last + g.cfg.every)
+    return fail(s, KMC_ERR_ARG, "rot: an update is due " + std::to_string(g.cfg.every) + " steps after the last one");
+  if (g.rec.updates >= INT32_MAX) return fail(s, KMC_ERR_ARG, "rot: the update counter is full");
+  const int64_t n = g.rec.updates + 1;
+  kmcl::Task tasks[LAG_MAX_ROWS];
+  const int nt = kmcl::tasks(n, g.a.L, g.a.P, tasks);
+  g.a.n = (int)n;
+  g.a.ntasks = nt;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N;
+  const int nblk = (N + ROT_T - 1) / ROT_T;
+  HIPCHK(s, hipMemcpyAsync(g.tasks, tasks, sizeof(kmcl::Task) * (size_t)nt, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(s, hipMemsetAsync(g.counts, 0, sizeof(lag_u64) * 3, s->stream));
+  if (nblk > 0) {
+    const size_t lds = sizeof(lag_u64) * (size_t)(std::min(nt, ROT_CHUNK) * ROT_TASK_W);
+    k_rot_update<<<(unsigned)std::min(nblk, AN_WG_MAX), ROT_T, lds, s->stream>>>(s->K, s->d, g.dev, g.a, g.tasks, nblk,
+                                                                                g.table, g.counts);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);  // (waits: tasks is read by the copy until here)
+  if (rc != KMC_OK) {
+    g.rec.on = false;  // the per-protein state may be half advanced
+    return rc;
+  }
+  for (int t = 0; t < nt; ++t) g.n_pairs[tasks[t].row] += 1;
+  g.rec.last = s->step_done;
+  g.rec.updates = n;
+  if (info) {
+    lag_u64 c[3] = {0, 0, 0};
+    HIPCHK(s, hipMemcpy(c, g.counts, sizeof c, hipMemcpyDeviceToHost));
+    info->n_updates = n;
+    info->n_tasks = nt;
+    info->n_events = (int64_t)c[0];
+    info->n_flips = (int64_t)c[1];
+    info->n_bad = (int64_t)c[2];
+  }
+  return KMC_OK;
+}
+
+int kmc_rot_sample(kmc_sim* s, kmc_rot_out* out, kmc_rot_cell* table, int64_t* n_pairs) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "rot sample: out is needed");
+  int rc = rec_check(s, s->rot.rec, ROT_OFF);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc == KMC_OK) rc = an_end(s);  // (no device work: the time of this call is that of its copy's wait)
+  if (rc != KMC_OK) return rc;
+  const RotState& g = s->rot;
+  const int rows = kmcl::rows(g.a.L, g.a.P);
+  std::memset(out, 0, sizeof *out);
+  out->cfg = g.cfg;
+  out->origin_step = g.rec.origin;
+  out->last_step = g.rec.last;
+  out->n_updates = g.rec.updates;
+  out->rows = rows;
+  if (table)
+    HIPCHK(s, hipMemcpy(table, g.table, sizeof(kmc_rot_cell) * (size_t)rows * LAG_CLASSES * ROT_VECS, hipMemcpyDeviceToHost));
+  if (n_pairs) std::copy(g.n_pairs, g.n_pairs + rows, n_pairs);
+  return KMC_OK;
+}
+
+int kmc_rot_arrays(kmc_sim* s, uint64_t* vec, int32_t* last_event, int8_t* chi) {
+  if (!s) return KMC_ERR_ARG;
+  const int rc = rec_check(s, s->rot.rec, ROT_OFF);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N, W = (size_t)s->K.NA + 2 * (size_t)s->K.NB;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  if (vec && W) HIPCHK(s, hipMemcpy(vec, s->rot.dev.vec, sizeof(lag_u64) * W, hipMemcpyDeviceToHost));
+  if (last_event && N) HIPCHK(s, hipMemcpy(last_event, s->rot.dev.last_event, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+  if (chi && N) HIPCHK(s, hipMemcpy(chi, s->rot.dev.chi, N, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_rot_end(kmc_sim* s) {
+  return s ? rec_end(s, s->rot) : KMC_ERR_ARG;
+}
+
+int kmc_ligand_pose(kmc_sim* s, int32_t nz, int32_t nc, int64_t* hist, kmc_pose_out* out) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "pose: out is needed");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  int64_t BZ, Lq;
+  const char* bad = kmco::pose_check(nz, nc, s->K.box_z, s->p.rb_radius, &BZ, &Lq);
+  if (bad) return fail(s, KMC_ERR_ARG, bad);
+  if (!s->pose.hist && dalloc(s, &s->pose.hist, (size_t)POSE_HIST_MAX + 2 * POSE_CLASSES + 1) != KMC_OK)
+    return fail(s, KMC_ERR_HIP, "pose: scratch allocation failed");
+  const size_t nbin = (size_t)POSE_CLASSES * nz * nc;
+  lag_u64* counts = s->pose.hist + POSE_HIST_MAX;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemsetAsync(s->pose.hist, 0, sizeof(lag_u64) * nbin, s->stream));
+  HIPCHK(s, hipMemsetAsync(counts, 0, sizeof(lag_u64) * (2 * POSE_CLASSES + 1), s->stream));
+  const int NB = s->K.NB, nblk = (NB + ROT_T - 1) / ROT_T;
+  if (nblk > 0)
+    k_pose<<<(unsigned)std::min(nblk, POSE_WG_MAX), ROT_T, sizeof(uint32_t) * nbin, s->stream>>>(
+        s->K, s->d, nz, nc, BZ, Lq, nblk, s->pose.hist, counts);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  static_assert(sizeof(lag_u64) == sizeof(int64_t), "the bins are copied out as they are");
+  if (hist) HIPCHK(s, hipMemcpy(hist, s->pose.hist, sizeof(lag_u64) * nbin, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(out, counts, sizeof *out, hipMemcpyDeviceToHost));
+  return KMC_OK;
 }
 
 }  // extern "C"

@@ -86,6 +86,14 @@
 //                            and per non-empty cell (the 128-bit sums in decimal)
 //                              cell step origin row lag class n_pairs n_all n_clean n_far m2_all
 //                                   m2_clean m4_clean
+//           [--rot EVERY LEVELS SLOTS FILE]  orientation recorder (kmc_rot_*), scheduled as --lag is and
+//                            with an origin of its own; every out_interval FILE gets, since that origin,
+//                              rot step origin n_updates every levels slots
+//                            and per non-empty cell (the 128-bit sums in decimal; v: 0 heading / axis, 1 arm)
+//                              cell step origin row lag class v n_pairs n_all n_clean s1_all s1_clean s2_clean
+//           [--pose NZ NC FILE]  ligand pose census (kmc_ligand_pose) of every output step:
+//                              pose step nz nc n_bad chi_pos[0..3] chi_neg[0..3]
+//                              bin step k zbin tiltbin count          (non-zero bins)
 #include <sys/stat.h>
 
 #include <cstdio>
@@ -161,6 +169,9 @@ int main(int argc, char** argv) {
   int cf_smax = 0;
   kmc_lag_config lag_cfg;
   std::memset(&lag_cfg, 0, sizeof lag_cfg);
+  std::string rot_path, pose_path;
+  kmc_rot_config rot_cfg = {0, 0, 0};
+  int pose_nz = 0, pose_nc = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -270,6 +281,26 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--rot") {
+      rot_cfg.every = atoi(next().c_str());
+      rot_cfg.levels = atoi(next().c_str());
+      rot_cfg.slots = atoi(next().c_str());
+      rot_path = next();
+      if (rot_cfg.every < 1 || rot_cfg.levels < 1 || rot_cfg.levels > KMC_LAG_MAX_LEVELS || rot_cfg.slots < 2 ||
+          rot_cfg.slots > KMC_LAG_MAX_SLOTS || rot_cfg.slots % 2) {
+        fprintf(stderr, "kmc_run: bad --rot %d %d %d\n", rot_cfg.every, rot_cfg.levels, rot_cfg.slots);
+        return 2;
+      }
+    }
+    else if (a == "--pose") {
+      pose_nz = atoi(next().c_str());
+      pose_nc = atoi(next().c_str());
+      pose_path = next();
+      if (pose_nz < 1 || pose_nz > KMC_POSE_MAX_BINS || pose_nc < 1 || pose_nc > KMC_POSE_MAX_BINS) {
+        fprintf(stderr, "kmc_run: bad --pose %d %d\n", pose_nz, pose_nc);
+        return 2;
+      }
+    }
     else if (a == "--set") {
       std::string kv = next();
       size_t eq = kv.find('=');
@@ -313,6 +344,8 @@ int main(int argc, char** argv) {
     if (!kin_path.empty()) truncate(kin_path.c_str());
     if (!cf_path.empty()) truncate(cf_path.c_str());
     if (!lag_path.empty()) truncate(lag_path.c_str());
+    if (!rot_path.empty()) truncate(rot_path.c_str());
+    if (!pose_path.empty()) truncate(pose_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
   }
@@ -349,13 +382,18 @@ int main(int argc, char** argv) {
     rc = kmc_lag_begin(s, &lag_cfg);
     if (rc) return die(s, rc, "lag begin");
   }
+  int64_t rot_left = rot_cfg.every;
+  if (!rot_path.empty()) {
+    rc = kmc_rot_begin(s, &rot_cfg);
+    if (rc) return die(s, rc, "rot begin");
+  }
   int64_t step = kmc_current_step(s);
   while (step < p.simu_step) {
     int64_t next_out = (step / p.out_interval + 1) * p.out_interval;
     int64_t end = next_out < p.simu_step ? next_out : p.simu_step;
     int64_t n = end - step;
     obs.resize((size_t)n);
-    if (dyn_path.empty() && kin_path.empty() && cf_path.empty() && lag_path.empty()) {
+    if (dyn_path.empty() && kin_path.empty() && cf_path.empty() && lag_path.empty() && rot_path.empty()) {
       rc = kmc_step(s, n, obs.data());
       if (rc) return die(s, rc, "kmc_step");
     } else {
@@ -369,6 +407,7 @@ int main(int argc, char** argv) {
         if (kin_left < m) m = kin_left;
         if (cf_left < m) m = cf_left;
         if (!lag_path.empty() && lag_left < m) m = lag_left;
+        if (!rot_path.empty() && rot_left < m) m = rot_left;
         rc = kmc_step(s, m, obs.data() + done);
         if (rc) return die(s, rc, "kmc_step");
         done += m;
@@ -376,6 +415,7 @@ int main(int argc, char** argv) {
         kin_left -= m;
         cf_left -= m;
         lag_left -= m;
+        rot_left -= m;
         if (!dyn_path.empty() && (dyn_left == 0 || done == n)) {
           rc = kmc_track_update(s, nullptr);
           if (rc) return die(s, rc, "track update");
@@ -395,6 +435,11 @@ int main(int argc, char** argv) {
           rc = kmc_lag_update(s, nullptr);
           if (rc) return die(s, rc, "lag update");
           lag_left = lag_cfg.every;
+        }
+        if (!rot_path.empty() && rot_left == 0) {
+          rc = kmc_rot_update(s, nullptr);
+          if (rc) return die(s, rc, "rot update");
+          rot_left = rot_cfg.every;
         }
       }
     }
@@ -602,6 +647,48 @@ int main(int argc, char** argv) {
                     dec128(w.m4_clean).c_str());
           }
         }
+        fclose(f);
+      }
+      if (!rot_path.empty()) {
+        kmc_rot_out k;
+        std::vector<kmc_rot_cell> table((size_t)KMC_LAG_MAX_ROWS * KMC_LAG_CLASSES * KMC_ROT_VECS);
+        int64_t n_pairs[KMC_LAG_MAX_ROWS];
+        rc = kmc_rot_sample(s, &k, table.data(), n_pairs);
+        if (rc) return die(s, rc, "rot sample");
+        f = fopen(rot_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, rot_path.c_str());
+        fprintf(f, "rot %lld %lld %lld %d %d %d\n", (long long)step, (long long)k.origin_step, (long long)k.n_updates,
+                k.cfg.every, k.cfg.levels, k.cfg.slots);
+        const int P = k.cfg.slots;
+        for (int r = 0; r < (int)k.rows; ++r) {
+          const int lv = r < P ? 0 : 1 + (r - P) / (P / 2);
+          const int64_t lag = (int64_t)(r < P ? r + 1 : P / 2 + 1 + (r - P) % (P / 2)) << lv;
+          for (int c = 0; c < KMC_LAG_CLASSES * KMC_ROT_VECS; ++c) {
+            const kmc_rot_cell& w = table[(size_t)r * KMC_LAG_CLASSES * KMC_ROT_VECS + c];
+            if (!w.n_all) continue;
+            fprintf(f, "cell %lld %lld %d %lld %d %d %lld %lld %lld %s %s %s\n", (long long)step,
+                    (long long)k.origin_step, r, (long long)lag, c / KMC_ROT_VECS, c % KMC_ROT_VECS,
+                    (long long)n_pairs[r], (long long)w.n_all, (long long)w.n_clean, dec128(w.s1_all).c_str(),
+                    dec128(w.s1_clean).c_str(), dec128(w.s2_clean).c_str());
+          }
+        }
+        fclose(f);
+      }
+      if (!pose_path.empty()) {
+        kmc_pose_out k;
+        std::vector<int64_t> bins((size_t)KMC_POSE_CLASSES * pose_nz * pose_nc);
+        rc = kmc_ligand_pose(s, pose_nz, pose_nc, bins.data(), &k);
+        if (rc) return die(s, rc, "pose");
+        f = fopen(pose_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, pose_path.c_str());
+        fprintf(f, "pose %lld %d %d %lld", (long long)step, pose_nz, pose_nc, (long long)k.n_bad);
+        for (int c = 0; c < KMC_POSE_CLASSES; ++c) fprintf(f, " %lld", (long long)k.chi_pos[c]);
+        for (int c = 0; c < KMC_POSE_CLASSES; ++c) fprintf(f, " %lld", (long long)k.chi_neg[c]);
+        fputc('\n', f);
+        for (size_t b = 0; b < bins.size(); ++b)
+          if (bins[b])
+            fprintf(f, "bin %lld %zu %zu %zu %lld\n", (long long)step, b / ((size_t)pose_nz * pose_nc),
+                    b / pose_nc % pose_nz, b % pose_nc, (long long)bins[b]);
         fclose(f);
       }
     }

@@ -160,6 +160,20 @@ def load_library(path: Optional[str] = None):
                                       P(capi.LagInfo)]
     L.kmc_host_lag_sample.argtypes = [P(capi.Params), P(capi.LagView), P(capi.LagOut), P(capi.LagOut), C.c_void_p,
                                       C.c_void_p]
+    L.kmc_rot_begin.argtypes = [C.c_void_p, P(capi.RotConfig)]
+    L.kmc_rot_update.argtypes = [C.c_void_p, P(capi.RotInfo)]
+    L.kmc_rot_sample.argtypes = [C.c_void_p, P(capi.RotOut), C.c_void_p, C.c_void_p]
+    L.kmc_rot_arrays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kmc_rot_end.argtypes = [C.c_void_p]
+    L.kmc_ligand_pose.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, P(capi.PoseOut)]
+    L.kmc_host_rot_begin.argtypes = [P(capi.Params), P(capi.StateView), P(capi.RotConfig), P(capi.RotView),
+                                     P(capi.RotOut)]
+    L.kmc_host_rot_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.RotView), P(capi.RotOut),
+                                      P(capi.RotInfo)]
+    L.kmc_host_rot_sample.argtypes = [P(capi.Params), P(capi.RotView), P(capi.RotOut), P(capi.RotOut), C.c_void_p,
+                                      C.c_void_p]
+    L.kmc_host_ligand_pose.argtypes = [P(capi.Params), P(capi.StateView), C.c_int32, C.c_int32, C.c_void_p,
+                                       P(capi.PoseOut)]
     for f in ("kmc_host_math", "kmc_device_math"):
         getattr(L, f).argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
@@ -449,6 +463,50 @@ class HostLag:
         return capi.LagSample(out, table, n_pairs)
 
 
+class HostRot:
+    """The orientation recorder on host states, sequentially (kmc_host_rot_*): Simulation.rot_*'s counterpart without
+    a device.  The recorder begins at hs (update 0); update(hs) advances it to the state `every` steps later.
+    arrays (capi.RotArrays) holds its per-protein state, the rings and the table."""
+
+    def __init__(self, params: capi.Params, hs: capi.HostState, config: capi.RotConfig):
+        self.params = params
+        ok = 1 <= config.levels <= capi.LAG_MAX_LEVELS and 2 <= config.slots <= capi.LAG_MAX_SLOTS
+        self.arrays = capi.RotArrays(params.n_a, params.n_b, config.levels if ok else 1, config.slots if ok else 2)
+        self.acc = capi.RotOut()
+        v = hs.view()
+        _host_check(load_library().kmc_host_rot_begin(C.byref(params), C.byref(v), C.byref(config),
+                                                      C.byref(self.arrays.view()), C.byref(self.acc)))
+
+    def update(self, hs: capi.HostState) -> capi.RotInfo:
+        """Advance the recorder to hs (kmc_host_rot_update)."""
+        v = hs.view()
+        info = capi.RotInfo()
+        _host_check(load_library().kmc_host_rot_update(C.byref(self.params), C.byref(v), C.byref(self.arrays.view()),
+                                                       C.byref(self.acc), C.byref(info)))
+        return info
+
+    def sample(self) -> capi.RotSample:
+        """The table as of the last update — kmc_host_rot_sample; a copy."""
+        out = capi.RotOut()
+        table = np.zeros_like(self.arrays.table)
+        n_pairs = np.zeros_like(self.arrays.n_pairs)
+        _host_check(load_library().kmc_host_rot_sample(C.byref(self.params), C.byref(self.arrays.view()),
+                                                       C.byref(self.acc), C.byref(out), table.ctypes.data,
+                                                       n_pairs.ctypes.data))
+        return capi.RotSample(out, table, n_pairs)
+
+
+def host_ligand_pose(params: capi.Params, hs: capi.HostState, nz: int, nc: int):
+    """(hist[4, nz, nc] int64, capi.PoseOut) of a host state, sequentially (kmc_host_ligand_pose)."""
+    ok = 1 <= nz <= capi.POSE_MAX_BINS and 1 <= nc <= capi.POSE_MAX_BINS
+    hist = np.zeros((capi.POSE_CLASSES, nz, nc) if ok else (1,), dtype=np.int64)
+    out = capi.PoseOut()
+    v = hs.view()
+    _host_check(load_library().kmc_host_ligand_pose(C.byref(params), C.byref(v), int(nz), int(nc), hist.ctypes.data,
+                                                    C.byref(out)))
+    return hist, out
+
+
 def host_dd_check(gid: np.ndarray, own: np.ndarray) -> int:
     """kmc_dd_set_state's argument check on the host: 0 or KMC_ERR_ARG."""
     gid = np.ascontiguousarray(gid, dtype=np.int32)
@@ -711,7 +769,7 @@ class Simulation:
 
     @property
     def analysis_ms(self) -> float:
-        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / lag_* / unwrap /
+        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / lag_* / rot_* / ligand_pose / unwrap /
         cluster_* / structure_factor / bond_order / bond_order_corr / network / rings call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
@@ -916,6 +974,67 @@ class Simulation:
             done += every
             info = self.lag_update()
         return recs, info
+
+    # ---- orientation: the rotational lag correlator and the ligands' poses (kmc_orient.hip)
+    def rot_begin(self, config: capi.RotConfig) -> None:
+        """Start the orientation recorder at the current state (update 0; capi.rot_config builds the configuration).
+        It allocates levels * slots * (8 n_a + 16 n_b) bytes, freed by rot_end."""
+        self._check(load_library().kmc_rot_begin(self._h, C.byref(config)))
+
+    def rot_update(self) -> capi.RotInfo:
+        """Correlate the current body vectors with every stored origin that is due and store the new origins; legal
+        exactly `every` steps after the last update (or the begin)."""
+        info = capi.RotInfo()
+        self._check(load_library().kmc_rot_update(self._h, C.byref(info)))
+        return info
+
+    def rot_sample(self) -> capi.RotSample:
+        """The table accumulated since rot_begin — kmc_rot_sample; analysis.rot_curves turns it into C_1 and C_2 by
+        lag time."""
+        out = capi.RotOut()
+        self._check(load_library().kmc_rot_sample(self._h, C.byref(out), None, None))
+        table = np.zeros((int(out.rows), capi.LAG_CLASSES, capi.ROT_VECS), dtype=capi.ROT_CELL_DTYPE)
+        n_pairs = np.zeros(int(out.rows), dtype=np.int64)
+        self._check(load_library().kmc_rot_sample(self._h, C.byref(out), table.ctypes.data, n_pairs.ctypes.data))
+        return capi.RotSample(out, table, n_pairs)
+
+    def rot_arrays(self):
+        """(vec[n_a + 2 n_b] uint64: packed headings, axes, arms (capi.rot_unpack); last_event[N] int32; chi[N] int8)
+        by reference index (kmc_rot_arrays): diagnostics and tests."""
+        n_a, n_b = self.params.n_a, self.params.n_b
+        vec = np.zeros(n_a + 2 * n_b, dtype=np.uint64)
+        last_event = np.zeros(n_a + n_b, dtype=np.int32)
+        chi = np.zeros(n_a + n_b, dtype=np.int8)
+        self._check(load_library().kmc_rot_arrays(self._h, vec.ctypes.data, last_event.ctypes.data, chi.ctypes.data))
+        return vec, last_event, chi
+
+    def rot_end(self) -> None:
+        self._check(load_library().kmc_rot_end(self._h))
+
+    def run_rotated(self, nsteps: int):
+        """Advance nsteps steps, `every` of the begun recorder's configuration at a time, with a rot_update after
+        each piece (nsteps must be a multiple of every).  Returns (records[nsteps], the last capi.RotInfo or None)."""
+        out = capi.RotOut()
+        self._check(load_library().kmc_rot_sample(self._h, C.byref(out), None, None))
+        every = int(out.cfg.every)
+        if nsteps < 0 or nsteps % every:
+            raise ValueError("run_rotated: nsteps >= 0, a multiple of the recorder's every")
+        recs = np.zeros(nsteps, dtype=capi.OBS_DTYPE)
+        done, info = 0, None
+        while done < nsteps:
+            self.step(every, recs[done:done + every])
+            done += every
+            info = self.rot_update()
+        return recs, info
+
+    def ligand_pose(self, nz: int, nc: int):
+        """(hist[4, nz, nc] int64, capi.PoseOut): the ligands of the current state by occupied sites, height of bead
+        [1][1] and z component of the axis (kmc_ligand_pose); analysis.pose_profile normalises it."""
+        ok = 1 <= nz <= capi.POSE_MAX_BINS and 1 <= nc <= capi.POSE_MAX_BINS
+        hist = np.zeros((capi.POSE_CLASSES, nz, nc) if ok else (1,), dtype=np.int64)
+        out = capi.PoseOut()
+        self._check(load_library().kmc_ligand_pose(self._h, int(nz), int(nc), hist.ctypes.data, C.byref(out)))
+        return hist, out
 
     @property
     def current_step(self) -> int:
