@@ -1265,7 +1265,10 @@ int kmc_host_dd_check(int32_t n, const int32_t* gid, const uint8_t* own);
  *   kmc_dd_jumpers    the owned proteins displaced more than S since then:
  *                     *n of them (may exceed cap), the first cap as (local
  *                     index, x of bead [1][1]).
- *   kmc_dd_counters   out[0] collisions between an owned and a halo unit,
+ *   kmc_dd_counters   out[0] collisions of a moved unit's member with a protein
+ *                     of the other ownership (owned against halo) whose unit
+ *                     moves later in the step, i.e. at its old position — every
+ *                     such pair, as the sequential loop would meet them;
  *                     out[1] bonds formed between an owned and a halo protein,
  *                     both since kmc_dd_set_state. */
 int kmc_dd_set_state(kmc_sim* s, const kmc_state_view* v, const int32_t* gid, const uint8_t* own,

@@ -793,7 +793,7 @@ class DDReport(C.Structure):
     def cross_bonds(self) -> np.ndarray:
         """[n, 2] local ids of the listed cross-slab bonds."""
         n = min(self.n_xb, DD_XCAP)
-        return np.ctypeslib.as_array(self.xb).reshape(DD_XCAP, 2)[:n].copy()
+        return np.ctypeslib.as_array(self.xb).reshape(-1, 2)[:n].copy()
 
 
 def default_params(**overrides) -> Params:

@@ -3681,8 +3681,13 @@ __device__ __forceinline__ void col_exact_one(const KParams& P, const Dev& d, co
   }
   if (!hit) return;
   if (bad_key(d, u) || bad_key(d, kq)) return;
-  if (P.dd && d.dd_own[u] != d.dd_own[kq]) atomicAdd(&d.ctl->dd_xcol, 1u);  // an owned unit against a halo unit
   if (kq >= u) {
+    // diagnostics of a decomposed trajectory: a member's proposal against a
+    // protein of the other ownership whose unit moves later (its old record).
+    // Counted here because the hit's relevance is already known and every
+    // such hit arrives — an entry of an earlier unit may be dropped once u is
+    // rejected — so the count is the sequential loop's (oracle: dd_count_collisions)
+    if (P.dd && kq > u && !isnew && d.dd_own[d.id_of[m]] != d.dd_own[d.id_of[q]]) atomicAdd(&d.ctl->dd_xcol, 1u);
     mark_rej(d, u, tag);
     return;
   }

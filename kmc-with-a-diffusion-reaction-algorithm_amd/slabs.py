@@ -489,7 +489,10 @@ class SlabRank:
         self.gather_every = gather_every  # assemble the global state every k steps (tests: 1)
         self.eng = None
         self.eng_ok = True
-        self.grow = 0  # output-list growth carried to the handles of a rebuild (kmc_list_growth)
+        # output-list growth carried to the handles of a rebuild (kmc_list_growth): the level a handle of this
+        # rank reported after an overflow, negative levels included; None until one overflows — a rebuilt
+        # handle then keeps the level its factory gave it
+        self.grow: Optional[int] = None
         self.plan: Optional[Plan] = None
         self.win: Optional[Window] = None
         self.step_no = 0
@@ -553,7 +556,7 @@ class SlabRank:
         q.n_a, q.n_b = w.n_a, w.n_b
         self.q = q
         self.eng = self.make_engine(q)
-        if self.grow:
+        if self.grow is not None:
             self.eng.set_list_growth(self.grow)
         t3 = time.perf_counter()
         self.eng.dd_set_state(ws, w.gids, w.own, ctl5)
@@ -638,15 +641,21 @@ class SlabRank:
 
     def _step(self) -> np.ndarray:
         rec = self._one()
-        tries = 0
+        tries = checks = 0
         while rec is None:  # a check failed on some slab: back to the step before, re-partition, retry
             tries += 1
             if tries > MAX_TRIES or self.halo > 64 * self.p.box_x:
                 raise SlabError(f"step {self.step_no + 1} does not pass its checks after {tries - 1} retries "
                                 f"(halo {self.halo:.0f} Å): {self.stats['why'][-3:]}")
             # a repeated failure, or one right after the partition (nothing to
-            # replay: the same partition would fail again), widens the halo
-            self._recover(widen=tries > 1 or not self.history)
+            # replay: the same partition would fail again), widens the halo;
+            # full lists alone do not — the rebuilt handles have larger ones,
+            # and the partition was not at fault
+            if self.stats["why"][-1][1] == "capacity":
+                self._recover(widen=False)
+            else:
+                checks += 1
+                self._recover(widen=checks > 1 or not self.history)
             rec = self._one()
         self._remember(rec)
         self.stats["steps"] += 1
@@ -736,7 +745,8 @@ class SlabRank:
             self.eng_ok = False
             if _engine_error(e) == capi.ERR_CAPACITY:
                 fail = True  # the lists were full: redo the step from the checkpoint with larger ones
-                self.grow = max(self.grow, int(getattr(self.eng, "list_growth", 0)))
+                level = int(getattr(self.eng, "list_growth", 0))  # already doubled by the failed step
+                self.grow = level if self.grow is None else max(self.grow, level)
             else:
                 err = f"rank {self.rank}: {e!r}"
         t1 = time.perf_counter()
@@ -758,7 +768,13 @@ class SlabRank:
             self.stats["exchanged"] += self.n_recv
             self.stats["verified"] += self.n_verify
             nj = rep.n_jump
-            jbad, jwarn = self._jumper_check(*rep.jumpers())
+            jids, jxs = rep.jumpers()
+            if nj > capi.DD_JCAP:
+                # the report lists the first KMC_DD_JCAP in no particular order:
+                # the whole list (the owned proteins have not moved since the
+                # step listed them), so that every jumper goes through J_A / J_B
+                jids, jxs = self.eng.dd_jumpers(self.S - self.lead)
+            jbad, jwarn = self._jumper_check(jids, jxs)
             xunits = self._cross_units(rep)
             if self.check:
                 from . import engine as _engine

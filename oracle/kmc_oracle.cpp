@@ -309,12 +309,29 @@ struct Oracle {
   // Does member m (at its R_new) collide with anything?  `unit` lists the
   // members of the unit being moved (their R_new are proposals and they are
   // not yet at their new cells).
-  // a collision found (decomposed trajectory: counted when it pairs an owned
-  // with a halo protein — diagnostics)
-  bool hit(int m, int q) {
-    if (!pair_collides(m, q)) return false;
-    if (dd && dd_own[m] != dd_own[q]) ++dd_xcol;
-    return true;
+  bool hit(int m, int q) { return pair_collides(m, q); }
+  // Decomposed trajectory, diagnostics (dd_xcol): the collisions of the unit
+  // being moved with proteins of the other ownership whose units have not
+  // moved yet this step (they stand at their old positions) — every member
+  // against every such protein, so that the count depends neither on where
+  // the search below stops nor on the order of the candidates.  The engine
+  // counts the same pairs (col_exact_one: a later unit's old record).
+  std::vector<uint8_t> dd_done;  // the protein's unit has been moved this step
+  void dd_count_collisions(const std::vector<int>& unit) {
+    if (!dd) return;
+    auto one = [&](int m, int q) {
+      if (dd_done[q] || dd_own[m] == dd_own[q]) return;
+      if (std::find(unit.begin(), unit.end(), q) != unit.end()) return;
+      if (pair_collides(m, q)) ++dd_xcol;
+    };
+    for (int m : unit) {
+      if (nbmode == 0) {
+        for (int q = 1; q <= N; ++q) one(m, q);
+      } else {
+        gather(Nx[I(m, 1, 1)], Ny[I(m, 1, 1)], cand);
+        for (int q : cand) one(m, q);
+      }
+    }
   }
   bool member_collides(int m, const std::vector<int>& unit) {
     if (nbmode == 0) {
@@ -334,6 +351,8 @@ struct Oracle {
     return false;
   }
   void unit_done(const std::vector<int>& unit) {
+    if (dd)
+      for (int q : unit) dd_done[q] = 1;
     if (nbmode == 0) return;
     for (int q : unit) {
       check_extent(q, true);
@@ -546,6 +565,7 @@ struct Oracle {
     for (auto& r : results) r.clear();
     std::fill(visited.begin(), visited.end(), 0);
     std::fill(moved.begin(), moved.end(), 0);
+    if (dd) dd_done.assign(N + 1, 0);
     for (int i = NA + 1; i <= N; ++i) {
       if (visited[i]) continue;
       std::vector<int>& res = results[i];
@@ -609,6 +629,7 @@ struct Oracle {
           }
           unit.assign(1, a);
           ev[EV_FREE_A]++;
+          dd_count_collisions(unit);
           if (member_collides(a, unit)) {
             revert(a);
             ev[EV_REJECT]++;
@@ -666,6 +687,7 @@ struct Oracle {
           double dist4 = P.cis_dist_cutoff / 2;
           if (!AreSame(dist1, dist3) || !AreSame(dist2, dist4)) snap_cis(a2, a);
           unit.assign({a, a2});
+          dd_count_collisions(unit);
           bool coll = member_collides(a, unit) || member_collides(a2, unit);
           ev[EV_DIMER]++;
           if (coll) {
@@ -982,6 +1004,7 @@ struct Oracle {
 
     // collision test + revert, main.cpp:1759-1860
     bool coll = false;
+    dd_count_collisions(res);
     for (int m : res)
       if (member_collides(m, res)) {
         coll = true;

@@ -6,7 +6,11 @@ neighbours' send buffers on the device; or one rank per process over
 torch.distributed).  Every step's bond.dat record and full-state hash must
 equal the keyed cell-list oracle's (tests/golden/slabs_20000_7000.npz,
 make_slab_fixture.py) — over all 500 steps, while units of different slabs
-collide, bond across the cuts and move to one owner."""
+collide, bond across the cuts and move to one owner.  The driver's recovery
+paths (rollback and replay, re-partition ahead of a jumper, cross-bond and
+output-list overflow, more jumpers than a report lists) run on a small box
+against the whole-box oracle; the window kernels' own checks are in
+test_gpu_dd.py."""
 import importlib
 import os
 import socket
@@ -15,6 +19,7 @@ import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
+from _dd import CountsJumpers, jumper_spy, run_and_compare, whole_box_small
 from _kmc import DENSE, PKG, engine, golden, params, workloads
 
 pytestmark = pytest.mark.gpu
@@ -160,3 +165,95 @@ def test_slabs_two_processes_gpu(tmp_path):
     assert np.array_equal(got["recs"], fx["obs"][:steps])
     assert int(got["hash"]) == int(fx["hashes"][steps - 1])
     assert int(got["xcol"]) > 0 and int(got["verified"]) > 0
+
+
+# ---- the driver's recovery paths on the device (the CPU twins over oracle
+# windows are in test_slabs.py): 2000 + 700 proteins, 4500 Å, seed 17, G = 2,
+# every step's record and state hash against the whole-box oracle
+def recover(steps, make=window_handle, **kw):
+    p, st, ref, hashes = whole_box_small(120)
+    ranks = run_and_compare(p, st, ref[:steps], hashes[:steps], 2, steps, make, **kw)
+    return ranks
+
+
+def closed(ranks):
+    for r in ranks:
+        r.close()
+    return ranks[0].stats
+
+
+def test_slabs_narrow_halo_rolls_back_gpu():
+    # band 180 Å, S = 20 Å, no re-partition ahead: checks fail on the device,
+    # each failure rolled back, replayed and retried
+    s = closed(recover(120, halo=360.0, lead=0.0))
+    print(s)
+    assert s["rollbacks"] > 0 and s["replayed"] > 0, s
+    assert {w[1] for w in s["why"]} & {"verify", "jumper"}, s["why"]
+
+
+def test_slabs_narrow_halo_repartitions_ahead_gpu():
+    s = closed(recover(120, halo=360.0))
+    print(s)
+    assert s["rebuild_jumpers"] > 0 and s["rollbacks"] == 0, s
+
+
+def test_slabs_cross_bond_list_overflow_gpu(monkeypatch):
+    # the driver sees a list of no entries: the cross-slab bond of step 57
+    # (one, listed by both windows) is "more than listed", so the joined unit
+    # cannot be found from the list and the trajectory re-partitions instead
+    monkeypatch.setattr(capi, "DD_XCAP", 0)
+    assert slabs.capi is capi
+    orig = slabs.SlabRank._cross_units
+    over = []
+
+    def spy(self, rep):
+        units = orig(self, rep)
+        if units is None:
+            over.append((self.step_no + 1, int(rep.n_xb)))
+        return units
+
+    monkeypatch.setattr(slabs.SlabRank, "_cross_units", spy)
+    s = closed(recover(80))
+    print(over, s)
+    assert over and all(n > capi.DD_XCAP for _, n in over)
+    assert s["rebuild_bond"] > 0 and s["transfers"] == 0, s
+
+
+# the smallest k for which a window's lists, 2^k times smaller than their
+# defaults, overflow within 40 steps while no step needs more than MAX_TRIES
+# doublings.  Measured on the MI355X over k = 1 … 9: k ≤ 8 never overflows; at
+# k = 9 both windows overflow in step 1 — one capacity retry, right after the
+# partition, both rebuilt handles at level −8, the halo still 900 Å
+LIST_SHRINK = 9
+
+
+def test_slabs_list_overflow_grows_and_keeps_the_halo_gpu():
+    def small_lists(q):
+        sim = engine.Simulation(q, device=0)
+        sim.set_list_growth(-LIST_SHRINK)
+        return sim
+
+    ranks = recover(40, make=small_lists)
+    levels = [r.eng.list_growth for r in ranks]
+    halos = [r.halo for r in ranks]
+    s = closed(ranks)
+    retries = sum(1 for w in s["why"] if w[1] == "capacity")
+    print(f"k={LIST_SHRINK}: capacity retries {retries}, levels {levels}, {s}")
+    assert retries > 0 and {w[1] for w in s["why"]} == {"capacity"}, s["why"]
+    assert max(levels) > -LIST_SHRINK, levels  # the grown level was carried to the handle in use
+    assert halos == [900.0, 900.0], halos      # full lists are no reason to widen the halo
+
+
+class CountingSim(CountsJumpers, engine.Simulation):
+    pass
+
+
+def test_slabs_every_listed_jumper_checked_gpu(monkeypatch):
+    # test_slabs.py's test on the device, where the report's KMC_DD_JCAP
+    # entries are whichever threads came first
+    calls = jumper_spy(monkeypatch)
+    s = closed(recover(60, make=lambda q: CountingSim(q, device=0), halo=900.0, lead=154.0))
+    assert calls and max(n for _, n in calls) > capi.DD_JCAP
+    short = [(checked, n) for checked, n in calls if checked != n]
+    assert not short, f"(ids checked, the report's n_jump): {short[:5]}"
+    assert s["jumpers"] > capi.DD_JCAP, s

@@ -16,44 +16,14 @@ import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
-from _kmc import DENSE, PKG, O, engine, params
-
-import importlib
-
-slabs = importlib.import_module(PKG + ".slabs")
-capi = importlib.import_module(PKG + ".capi")
-
-RATES = {k: v for k, v in DENSE.items() if not k.startswith("box")}
+from _dd import RATES, CountsJumpers, OracleWindow, capi, jumper_spy, scenario, slabs, whole_box
+from _kmc import O, engine, params
 
 
-class OracleWindow(O.Oracle):
-    """An oracle over one slab's window (cell-list mode)."""
-
-    def __init__(self, q):
-        super().__init__(q, rng_mode=O.RNG_KEYED, nbmode=O.NB_CELLS)
-
-    def step(self, n):
-        return super().step(n, want_hashes=False)[0]  # the records, as engine.Simulation.step
-
-    def close(self):
-        pass
-
-
-def scenario(n_a=4000, n_b=1500, L=6000.0, seed=9):
-    p = params(n_a=n_a, n_b=n_b, seed=seed, box_x=L, box_y=L, box_z=250.0, **RATES)
-    return p, engine.host_init_random(p)
-
-
-def whole_box(p, st, steps):
-    o = O.Oracle(p, nbmode=O.NB_CELLS)
-    o.set_state(st)
-    return o.step(steps)
-
-
-def run_and_compare(p, st, G, steps, halo=900.0, lead=None):
+def run_and_compare(p, st, G, steps, halo=900.0, lead=None, make=OracleWindow):
     ref, hashes = whole_box(p, st, steps)
     got_h = []
-    recs, ranks = slabs.run_local(p, st, G, steps, OracleWindow, halo=halo, gather_every=1, lead=lead,
+    recs, ranks = slabs.run_local(p, st, G, steps, make, halo=halo, gather_every=1, lead=lead,
                                   on_step=lambda me, k, rec: got_h.append(engine.state_hash(p, me.last_global)))
     bad = [k + 1 for k in range(steps) if recs[k] != ref[k] or got_h[k] != int(hashes[k])]
     assert not bad, f"G={G}: steps {bad[:10]} differ from the whole-box oracle"
@@ -91,6 +61,24 @@ def test_slabs_jumpers_repartition_ahead():
     p, st = scenario(2000, 700, 4500.0, seed=17)
     s = run_and_compare(p, st, 2, 120, halo=360.0)
     assert s["rebuild_jumpers"] > 0 and s["rollbacks"] == 0, s
+
+
+class CountingWindow(CountsJumpers, OracleWindow):
+    pass
+
+
+def test_slabs_every_listed_jumper_checked(monkeypatch):
+    # S − lead = 1 Å: after one step nearly every owned protein is listed, far
+    # more than a report holds (KMC_DD_JCAP entries, on the device in no
+    # particular order).  Each of them goes through the jumper checks — the
+    # driver fetches the whole list — and the run equals the whole box
+    calls = jumper_spy(monkeypatch)
+    p, st = scenario(2000, 700, 4500.0, seed=17)
+    s = run_and_compare(p, st, 2, 60, halo=900.0, lead=154.0, make=CountingWindow)
+    assert calls and max(n for _, n in calls) > capi.DD_JCAP
+    short = [(checked, n) for checked, n in calls if checked != n]
+    assert not short, f"(ids checked, the report's n_jump): {short[:5]}"
+    assert s["jumpers"] > capi.DD_JCAP, s
 
 
 def test_units_and_window_state():
