@@ -1207,6 +1207,117 @@ int kmc_host_rot_sample(const kmc_params* p, const kmc_rot_view* view, const kmc
 int kmc_host_ligand_pose(const kmc_params* p, const kmc_state_view* v, int32_t nz, int32_t nc, int64_t* hist,
                          kmc_pose_out* out);
 
+/* Pair dynamics: the two-body half of the dynamic set.  Part A
+ * is the van Hove function split into its distinct part G_d(r, t) — the
+ * density of OTHER proteins at distance r, now, from where a protein was at
+ * the origin — and its (folded) self part; part B is the spatial correlation of
+ * displacements C_u(r, t) = <u_i . u_j> over pairs that were r apart at the
+ * origin.  One origin, that of kmc_pd_begin.  Like the lag correlator it reads
+ * the CURRENT state, launches nothing inside kmc_step and leaves the state,
+ * the step counter and kmc_get_clusters' validity untouched; its arrays are
+ * indexed by reference index i = 0..N-1 (receptors first), a protein's
+ * position is (x, y) of its bead [1][1].  All results are integers: the
+ * device, kmc_host_pd_* and the tests agree by equality, and the tables of
+ * replicas (and of consecutive recorders sampled at the same lag) add.
+ *
+ * Definitions — the device, kmc_host_pd_* and the tests share them:
+ *   integer coords  kmc_lag_*'s: X = (int64) round(x * 1024.0), BX = (int64)
+ *                   round(box_x * 1024.0), the same in y; its minimum image;
+ *                   fold(X) = X mod BX, the floor modulus into [0, BX).
+ *                   KMC_ERR_ARG when BX < 1, BY < 1 or a box of 2^21 A or more.
+ *   configuration   (kmc_pd_config) every >= 1 steps between updates; nbins in
+ *                   1..KMC_PD_MAX_BINS; r_max > 0; max_jump and max_disp as
+ *                   kmc_lag_config's (<= 0: min(box) / 4 and 16384 A), J and F
+ *                   their integers, F <= 2^24.
+ *   bins            E[m] = (int64) round(m * (r_max / nbins) * 1024.0), m =
+ *                   0..nbins, strictly increasing (else KMC_ERR_ARG).  A pair
+ *                   with d2 = dx^2 + dy^2 (integers) is in bin k = #{m in
+ *                   1..nbins : E[m]^2 <= d2} and is counted when k < nbins.  No
+ *                   square root decides a bin.
+ *   search grid     ncx = floor(BX / E[nbins]), ncy alike, both >= 3 (else
+ *                   KMC_ERR_ARG), both capped at 2048; cell = floor(fold(X) *
+ *                   ncx / BX).  No result depends on it.
+ *   per protein     X0 = (X, Y) at kmc_pd_begin; prev, the unwrapped U and the
+ *                   step d = minimum image of (X - prev), U += d, prev = X of
+ *                   kmc_lag_update; flags |= KMC_PD_JUMPED (sticky) when |dx| >=
+ *                   J or |dy| >= J at an update; u = U - X0.  VALID: not jumped
+ *                   and |u.x| < F and |u.y| < F.  Links are not read.
+ *   kmc_pd_begin    is update 0: prev = U = X0 = (X, Y), flags = 0; the origin
+ *                   is binned once.  The scratch (109 bytes per protein and 12
+ *                   per cell) is allocated here and freed by kmc_pd_end /
+ *                   kmc_destroy; a failed allocation is KMC_ERR_HIP with the
+ *                   recorder off.
+ *   kmc_pd_update   the per-protein step, legal only when kmc_current_step() ==
+ *                   the step of the last update + every (else KMC_ERR_ARG,
+ *                   nothing changes).
+ *   kmc_pd_sample   the tables of the state as of the last update (species 0 =
+ *                   receptor, 1 = ligand):
+ *                   A. D = minimum image of (fold(U_j) - fold(X0_i)) per axis,
+ *                      d2 binned.  gd[2 species(i) + species(j)][k] counts every
+ *                      ORDERED pair i != j, gs[species(i)][k] counts i == j:
+ *                      the folded self part, the bin of the true displacement
+ *                      while |u| < box / 2.  No validity filter: a teleported
+ *                      protein is still where it is.
+ *                   B. over UNORDERED pairs i < j, D = minimum image of (X0_j -
+ *                      X0_i), d2 binned; kind 0 = AA, 1 = AB, 2 = BB.  Per (kind,
+ *                      k) a kmc_pd_cell: n_pairs (every pair), n_valid (both
+ *                      proteins valid), and over the valid pairs dot += u_i.x
+ *                      u_j.x + u_i.y u_j.y (|term| < 2^49) and sq += |u_i|^2 +
+ *                      |u_j|^2 (term < 2^50).  C_u = 2 dot / sq is 1 for rigid
+ *                      co-translation.
+ *                   Each call computes the tables anew (nothing accumulates);
+ *                   gd [4][nbins], gs [2][nbins], cu [3][nbins] may each be NULL,
+ *                   and with all three NULL only out is filled.
+ *   kmc_pd_arrays   U [N][2], X0 [N][2] and flags [N] (each may be NULL) by
+ *                   reference index: diagnostics and tests.
+ *   kmc_pd_end      drops the recorder and frees its memory; idempotent.
+ * kmc_analysis_ms covers the last call.  The recorder is not checkpointed.
+ * kmc_host_pd_*: the same from host state views, sequentially, no device, with
+ * a cell list of their own; the caller owns the arrays of the kmc_pd_view and
+ * the kmc_pd_out that carries the recorder between the calls.
+ * KMC_ERR_ARG for a null / out-of-range argument, a handle without state, a
+ * decomposed window, an update off the stride and a recorder that was not
+ * begun; kmc_set_state, kmc_load_*, kmc_init_random and kmc_dd_set_state drop
+ * the recorder. */
+#define KMC_PD_MAX_BINS 256
+#define KMC_PD_JUMPED 1
+typedef struct kmc_pd_config {
+  int32_t every, nbins;
+  double r_max, max_jump, max_disp;
+} kmc_pd_config;
+typedef struct kmc_pd_info {
+  int64_t n_updates; /* n of this update */
+  int64_t n_jumped;  /* proteins whose flags hold KMC_PD_JUMPED after it */
+} kmc_pd_info;
+typedef struct kmc_pd_cell {
+  int64_t n_pairs, n_valid;
+  kmc_i128 dot, sq;
+} kmc_pd_cell;
+typedef struct kmc_pd_out {
+  kmc_pd_config cfg; /* as in effect: max_jump and max_disp resolved */
+  int64_t J, F, BX, BY;
+  int64_t ncx, ncy;
+  int64_t origin_step, last_step, n_updates;
+} kmc_pd_out;
+typedef struct kmc_pd_view {
+  int64_t* prev;  /* [N][2] */
+  int64_t* U;     /* [N][2] */
+  int64_t* X0;    /* [N][2] */
+  uint8_t* flags; /* [N] */
+} kmc_pd_view;
+int kmc_pd_begin(kmc_sim* s, const kmc_pd_config* cfg);
+int kmc_pd_update(kmc_sim* s, kmc_pd_info* info);
+int kmc_pd_sample(kmc_sim* s, kmc_pd_out* out, int64_t* gd /* [4][nbins] */, int64_t* gs /* [2][nbins] */,
+                  kmc_pd_cell* cu /* [3][nbins] */);
+int kmc_pd_arrays(kmc_sim* s, int64_t* U /* [N][2] */, int64_t* X0 /* [N][2] */, uint8_t* flags /* [N] */);
+int kmc_pd_end(kmc_sim* s);
+int kmc_host_pd_begin(const kmc_params* p, const kmc_state_view* v, const kmc_pd_config* cfg, const kmc_pd_view* view,
+                      kmc_pd_out* acc);
+int kmc_host_pd_update(const kmc_params* p, const kmc_state_view* v, const kmc_pd_view* view, kmc_pd_out* acc,
+                       kmc_pd_info* info);
+int kmc_host_pd_sample(const kmc_params* p, const kmc_pd_view* view, const kmc_pd_out* acc, kmc_pd_out* out,
+                       int64_t* gd, int64_t* gs, kmc_pd_cell* cu);
+
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */
 int kmc_format_bond_line(const kmc_params* p, const kmc_obs* o, char* buf, size_t n);   /* main.cpp:2251 */

@@ -10,12 +10,14 @@ off-rates, the rebinding fraction and the Kaplan–Meier survival of bond
 lifetimes from the bond kinetics recorder (kin_sample), the coagulation and
 fragmentation kernels K(a, b), F(a, b) and the growth modes from the cluster
 growth recorder (cf_sample), the hexagon fraction and ring densities of the
-ligand network from the ring counts (rings), and the replica sums of integer histograms,
+ligand network from the ring counts (rings), the distinct van Hove function
+G_d(r, t) and the displacement correlation C_u(r, t) from the pair dynamics
+(pd_sample), and the replica sums of integer histograms,
 float64 sums and geometry tables.
 
 The counts and sums themselves come from libkmc (kmc_analysis.hip,
 kmc_dynamics.hip, kmc_geometry.hip, kmc_structure.hip, kmc_bondorder.hip,
-kmc_kinetics.hip, kmc_coag.hip, kmc_rings.hip);
+kmc_kinetics.hip, kmc_coag.hip, kmc_rings.hip, kmc_pairdyn.hip);
 nothing here touches a trajectory.
 """
 from __future__ import annotations
@@ -547,3 +549,43 @@ def pose_profile(hist, p) -> dict:
     pdf = np.divide(h, n[:, None, None], out=np.zeros_like(h), where=n[:, None, None] > 0)
     return dict(z=(np.arange(nz) + 0.5) * float(p.box_z) / nz, cos=0.5 * (edges[:-1] + edges[1:]) / lq, n=n, pdf=pdf,
                 pdf_z=pdf.sum(axis=2), pdf_cos=pdf.sum(axis=1))
+
+
+def van_hove_distinct(sample, p):
+    """(r[nbins], gd[4, nbins], gs[2, nbins]) from a capi.PdSample: r the bin centres in A; gd the distinct part of the
+    van Hove function G_d(r, t) per ordered kind 2 species(i) + species(j), normalised like rdf — the count over the
+    ordered pairs n_i (n_j - [same species]) times the exact annulus area over the box area, the ideal density of the
+    j species — so that G_d(r, 0) is g(r); gs the (folded) self part as the fraction of the species' proteins per
+    bin.  Zeros where there is no pair."""
+    nb = sample.nbins
+    edges = np.arange(nb + 1, dtype=np.float64) * (sample.r_max / nb)
+    area = np.pi * (edges[1:] ** 2 - edges[:-1] ** 2)
+    n = (float(p.n_a), float(p.n_b))
+    gd = np.zeros((4, nb))
+    for si in range(2):
+        for sj in range(2):
+            ideal = n[si] * (n[sj] - (si == sj)) * area / (float(p.box_x) * float(p.box_y))
+            c = np.array([int(x) for x in sample.gd[2 * si + sj]], dtype=np.float64)
+            gd[2 * si + sj] = np.divide(c, ideal, out=np.zeros(nb), where=ideal > 0)
+    gs = np.zeros((2, nb))
+    for s in range(2):
+        if n[s] > 0:
+            gs[s] = np.array([int(x) for x in sample.gs[s]], dtype=np.float64) / n[s]
+    return 0.5 * (edges[:-1] + edges[1:]), gd, gs
+
+
+def displacement_corr(sample):
+    """(r[nbins], cu[3, nbins], valid[3, nbins]) from a capi.PdSample: C_u = 2 dot / sq per kind (AA, AB, BB), which is
+    1 for rigid co-translation, by the pair distance at the origin, and the valid fraction n_valid / n_pairs; zeros
+    where a denominator is zero."""
+    nb = sample.nbins
+    edges = np.arange(nb + 1, dtype=np.float64) * (sample.r_max / nb)
+    cu, valid = np.zeros((3, nb)), np.zeros((3, nb))
+    for kind in range(3):
+        for k in range(nb):
+            sq, n = int(sample.sq[kind, k]), int(sample.n_pairs[kind, k])
+            if sq:
+                cu[kind, k] = 2 * int(sample.dot[kind, k]) / sq
+            if n:
+                valid[kind, k] = int(sample.n_valid[kind, k]) / n
+    return 0.5 * (edges[:-1] + edges[1:]), cu, valid

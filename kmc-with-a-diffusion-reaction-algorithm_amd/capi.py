@@ -631,6 +631,116 @@ class LagArrays:
         return v
 
 
+PD_MAX_BINS, PD_JUMPED = 256, 1  # KMC_PD_MAX_BINS, KMC_PD_JUMPED
+
+
+class PdConfig(C.Structure):
+    """kmc_pd_config — the pair dynamics' configuration."""
+
+    _fields_ = [("every", C.c_int32), ("nbins", C.c_int32), ("r_max", C.c_double), ("max_jump", C.c_double),
+                ("max_disp", C.c_double)]
+
+
+def pd_config(every: int, nbins: int, r_max: float, max_jump: float = 0.0, max_disp: float = 0.0) -> PdConfig:
+    return PdConfig(int(every), int(nbins), float(r_max), float(max_jump), float(max_disp))
+
+
+class PdInfo(C.Structure):
+    """kmc_pd_info — one update: its number n and the proteins flagged jumped after it."""
+
+    _fields_ = [(name, C.c_int64) for name in ("n_updates", "n_jumped")]
+
+
+class PdOut(C.Structure):
+    """kmc_pd_out — the configuration in effect, the integer bounds and box, the search grid, the steps."""
+
+    _fields_ = [("cfg", PdConfig)] + [(name, C.c_int64) for name in (
+        "J", "F", "BX", "BY", "ncx", "ncy", "origin_step", "last_step", "n_updates")]
+
+
+class PdView(C.Structure):
+    """kmc_pd_view — caller-owned arrays of the recorder on the host."""
+
+    _fields_ = [("prev", C.POINTER(C.c_int64)), ("U", C.POINTER(C.c_int64)), ("X0", C.POINTER(C.c_int64)),
+                ("flags", C.POINTER(C.c_uint8))]
+
+
+# kmc_pd_cell as a numpy record
+PD_CELL_DTYPE = np.dtype([("n_pairs", "<i8"), ("n_valid", "<i8"), ("dot", I128_DTYPE), ("sq", I128_DTYPE)])
+assert PD_CELL_DTYPE.itemsize == 48
+PD_COUNTS = ("n_pairs", "n_valid")
+PD_SUMS = ("dot", "sq")
+
+
+class PdSample:
+    """One kmc_pd_sample: the configuration and steps (as attributes and in .out) and, as arrays of Python ints,
+    gd [4, nbins] (kind 2 species(i) + species(j)), gs [2, nbins] and part B's n_pairs, n_valid, dot, sq [3, nbins]
+    (AA, AB, BB; the 128-bit sums whole).  lag_steps = last_step - origin_step.  counts() / from_counts(): the
+    sample as one int64 vector that adds (analysis.reduce_counts)."""
+
+    def __init__(self, out: PdOut, gd: np.ndarray, gs: np.ndarray, cu: np.ndarray):
+        self.out = out
+        self.every, self.nbins, self.r_max = out.cfg.every, out.cfg.nbins, out.cfg.r_max
+        self.max_jump, self.max_disp = out.cfg.max_jump, out.cfg.max_disp
+        for name in ("J", "F", "BX", "BY", "ncx", "ncy", "origin_step", "last_step", "n_updates"):
+            setattr(self, name, int(getattr(out, name)))
+        self.lag_steps = self.last_step - self.origin_step
+        self.gd = gd.astype(object)
+        self.gs = gs.astype(object)
+        for name in PD_COUNTS:
+            setattr(self, name, cu[name].astype(object))
+        for name in PD_SUMS:
+            setattr(self, name, _i128_ints(cu[name]))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name in ("gd", "gs") + PD_COUNTS + PD_SUMS}
+
+    def counts(self) -> np.ndarray:
+        """[nbins * (6 + 3 * (2 + 2 * 4))] int64: gd, gs, then per cell of part B the counts and both sums' limbs."""
+        v = [int(x) for x in self.gd.ravel()] + [int(x) for x in self.gs.ravel()]
+        for kind in range(3):
+            for k in range(self.nbins):
+                v += [int(getattr(self, name)[kind, k]) for name in PD_COUNTS]
+                for name in PD_SUMS:
+                    x = int(getattr(self, name)[kind, k])
+                    v += [x >> 32 * m & 0xFFFFFFFF for m in range(LAG_LIMBS - 1)] + [x >> 32 * (LAG_LIMBS - 1)]
+        return np.array(v, dtype=np.int64)
+
+    def from_counts(self, counts) -> "PdSample":
+        """A sample of this one's configuration holding the (summed) counts() vector."""
+        import copy
+        s = copy.copy(self)
+        it = iter(int(x) for x in np.asarray(counts).ravel())
+        nb = self.nbins
+        s.gd = np.array([next(it) for _ in range(4 * nb)], dtype=object).reshape(4, nb)
+        s.gs = np.array([next(it) for _ in range(2 * nb)], dtype=object).reshape(2, nb)
+        for name in PD_COUNTS + PD_SUMS:
+            setattr(s, name, np.zeros((3, nb), dtype=object))
+        for kind in range(3):
+            for k in range(nb):
+                for name in PD_COUNTS:
+                    getattr(s, name)[kind, k] = next(it)
+                for name in PD_SUMS:
+                    getattr(s, name)[kind, k] = sum(next(it) << 32 * m for m in range(LAG_LIMBS))
+        return s
+
+
+class PdArrays:
+    """numpy-backed kmc_pd_view for n proteins: prev, U, X0 [n, 2] int64 and flags [n] uint8."""
+
+    def __init__(self, n: int):
+        self.prev = np.zeros((n, 2), dtype=np.int64)
+        self.U = np.zeros((n, 2), dtype=np.int64)
+        self.X0 = np.zeros((n, 2), dtype=np.int64)
+        self.flags = np.zeros(n, dtype=np.uint8)
+
+    def view(self) -> PdView:
+        v = PdView()
+        for name, ptr in PdView._fields_:
+            setattr(v, name, getattr(self, name).ctypes.data_as(ptr))
+        return v
+
+
 ROT_VECS, POSE_MAX_BINS, POSE_CLASSES = 2, 64, 4  # KMC_ROT_VECS, KMC_POSE_MAX_BINS, KMC_POSE_CLASSES
 ROT_BAD = 1 << 63                                  # KMC_ROT_BAD: the packed word of a bad protein's vector
 

@@ -26,6 +26,7 @@
 #include "kmc_rings.hip"
 #include "kmc_lagcorr.hip"
 #include "kmc_orient.hip"
+#include "kmc_pairdyn.hip"
 
 using namespace kmcd;
 
@@ -163,6 +164,7 @@ struct __attribute__((visibility("hidden"))) kmc_sim {
   RgState rg;
   LagState lag;
   RotState rot;
+  PdState pd;
   PoseState pose;
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   double an_ms = 0.0;
@@ -815,6 +817,7 @@ static int set_state_impl(kmc_sim* s, const kmc_state_view* v) {
   s->cf.rec.on = false;   // and the growth recorder's bonds and clusters
   s->lag.rec.on = false;  // and the lag correlator's origins
   s->rot.rec.on = false;  // and the orientation recorder's
+  s->pd.rec.on = false;   // and the pair dynamics' origin
   return KMC_OK;
 }
 

@@ -27,6 +27,7 @@
 #include "kmc_lagcorr.h"
 #include "kmc_orient.h"
 #include "kmc_math.h"
+#include "kmc_pairdyn.h"
 #include "kmc_params_check.h"
 #include "kmc_philox.h"
 #include "kmc_rings.h"
@@ -2115,6 +2116,193 @@ int kmc_host_ligand_pose(const kmc_params* p, const kmc_state_view* v, int32_t n
     if (chi > 0) out->chi_pos[k] += 1;
     if (chi < 0) out->chi_neg[k] += 1;
     if (hist) hist[((size_t)k * nz + kmco::pose_zbin(Z, BZ, nz)) * nc + kmco::pose_tbin(Nz, Lq, nc)] += 1;
+  }
+  return KMC_OK;
+}
+
+// Pair dynamics (include/kmc.h): kmc_pd_*'s definitions on host
+// state views, one protein and one pair after the other; the fold, the cell,
+// the bin, the validity and the terms are kmc_pairdyn.h's, the ones the device
+// evaluates.  The sample sorts both point sets by cell (a counting sort of its
+// own) and walks the 3 x 3 block for part A and the half shell for part B.
+extern "C++" {
+namespace {
+
+bool pd_view_ok(const kmc_pd_view* w) { return w && w->prev && w->U && w->X0 && w->flags; }
+
+// the configuration in acc resolved again: the grid and the edges (they were checked at begin)
+const char* pd_grid(const kmc_params* p, const kmc_pd_out* acc, kmcp::Grid* G, int64_t* E) {
+  double mj = acc->cfg.max_jump, md = acc->cfg.max_disp;
+  return kmcp::check(acc->cfg.every, acc->cfg.nbins, acc->cfg.r_max, p->box_x, p->box_y, &mj, &md, G, E);
+}
+
+// points sorted by cell: start[ncell + 1], order[N] (the point indices of cell c are order[start[c] .. start[c + 1]))
+struct PdCells {
+  std::vector<int32_t> start, order, cx, cy;
+  std::vector<int64_t> fx, fy;
+  void build(const int64_t* X, size_t N, const kmcp::Grid& G) {
+    const size_t ncell = (size_t)G.ncx * G.ncy;
+    start.assign(ncell + 1, 0);
+    order.resize(N);
+    cx.resize(N);
+    cy.resize(N);
+    fx.resize(N);
+    fy.resize(N);
+    for (size_t i = 0; i < N; ++i) {
+      fx[i] = kmcp::fold(X[2 * i], G.BX);
+      fy[i] = kmcp::fold(X[2 * i + 1], G.BY);
+      cx[i] = kmcp::cell(fx[i], G.ncx, G.BX);
+      cy[i] = kmcp::cell(fy[i], G.ncy, G.BY);
+      start[(size_t)cy[i] * G.ncx + cx[i] + 1] += 1;
+    }
+    for (size_t c = 0; c < ncell; ++c) start[c + 1] += start[c];
+    std::vector<int32_t> at(start.begin(), start.end() - 1);
+    for (size_t i = 0; i < N; ++i) order[at[(size_t)cy[i] * G.ncx + cx[i]]++] = (int32_t)i;
+  }
+};
+
+}  // namespace
+}  // extern "C++"
+
+int kmc_host_pd_begin(const kmc_params* p, const kmc_state_view* v, const kmc_pd_config* cfg, const kmc_pd_view* view,
+                      kmc_pd_out* acc) {
+  if (!p || !v || !v->ra || !v->rb || !v->a_int || !v->b_int || !cfg || !pd_view_ok(view) || !acc) {
+    g_host_err = "pd: params, state, the configuration, the view's four arrays and acc are needed";
+    return KMC_ERR_ARG;
+  }
+  kmc_pd_config c = *cfg;
+  kmcp::Grid G;
+  int64_t E[PD_MAX_BINS + 1];
+  const char* bad = kmcp::check(c.every, c.nbins, c.r_max, p->box_x, p->box_y, &c.max_jump, &c.max_disp, &G, E);
+  if (bad) {
+    g_host_err = bad;
+    return KMC_ERR_ARG;
+  }
+  const size_t N = (size_t)p->n_a + (size_t)p->n_b;
+  for (size_t i = 0; i < N; ++i) {
+    int64_t X[2];
+    int32_t l[3];
+    lag_host_cur(p, v, (int)i, X, l);
+    for (int k = 0; k < 2; ++k) view->prev[2 * i + k] = view->U[2 * i + k] = view->X0[2 * i + k] = X[k];
+    view->flags[i] = 0;
+  }
+  std::memset(acc, 0, sizeof *acc);
+  acc->cfg = c;
+  acc->J = G.J;
+  acc->F = G.F;
+  acc->BX = G.BX;
+  acc->BY = G.BY;
+  acc->ncx = G.ncx;
+  acc->ncy = G.ncy;
+  acc->origin_step = acc->last_step = v->step;
+  return KMC_OK;
+}
+
+int kmc_host_pd_update(const kmc_params* p, const kmc_state_view* v, const kmc_pd_view* view, kmc_pd_out* acc,
+                       kmc_pd_info* info) {
+  if (!p || !v || !v->ra || !v->rb || !v->a_int || !v->b_int || !pd_view_ok(view) || !acc) {
+    g_host_err = "pd: params, state, the view's four arrays and acc are needed";
+    return KMC_ERR_ARG;
+  }
+  if (v->step != acc->last_step + acc->cfg.every) {
+    g_host_err = "pd: an update is due " + std::to_string(acc->cfg.every) + " steps after the last one";
+    return KMC_ERR_ARG;
+  }
+  const size_t N = (size_t)p->n_a + (size_t)p->n_b;
+  int64_t n_jumped = 0;
+  for (size_t i = 0; i < N; ++i) {
+    int64_t X[2];
+    int32_t l[3];
+    lag_host_cur(p, v, (int)i, X, l);
+    const int64_t B[2] = {acc->BX, acc->BY};
+    for (int k = 0; k < 2; ++k) {
+      const int64_t d = kmcl::min_image(X[k] - view->prev[2 * i + k], B[k]);
+      view->U[2 * i + k] += d;
+      view->prev[2 * i + k] = X[k];
+      if (std::llabs(d) >= acc->J) view->flags[i] |= PD_JUMPED;
+    }
+    n_jumped += view->flags[i] & PD_JUMPED;
+  }
+  acc->last_step = v->step;
+  acc->n_updates += 1;
+  if (info) {
+    info->n_updates = acc->n_updates;
+    info->n_jumped = n_jumped;
+  }
+  return KMC_OK;
+}
+
+int kmc_host_pd_sample(const kmc_params* p, const kmc_pd_view* view, const kmc_pd_out* acc, kmc_pd_out* out, int64_t* gd,
+                       int64_t* gs, kmc_pd_cell* cu) {
+  if (!p || !pd_view_ok(view) || !acc || !out) {
+    g_host_err = "pd sample: params, the view's four arrays, acc and out are needed";
+    return KMC_ERR_ARG;
+  }
+  kmcp::Grid G;
+  int64_t E[PD_MAX_BINS + 1];
+  const char* bad = pd_grid(p, acc, &G, E);
+  if (bad) {
+    g_host_err = bad;
+    return KMC_ERR_ARG;
+  }
+  const kmc_pd_out a = *acc;  // (out may be acc itself)
+  *out = a;
+  if (!gd && !gs && !cu) return KMC_OK;
+  const int nb = G.nbins, na = p->n_a;
+  const size_t N = (size_t)p->n_a + (size_t)p->n_b;
+  uint64_t E2[PD_MAX_BINS + 1];
+  for (int m = 0; m <= nb; ++m) E2[m] = (uint64_t)E[m] * (uint64_t)E[m];
+  if (gd) std::fill(gd, gd + 4 * (size_t)nb, (int64_t)0);
+  if (gs) std::fill(gs, gs + 2 * (size_t)nb, (int64_t)0);
+  if (cu) std::memset(cu, 0, sizeof(kmc_pd_cell) * 3 * (size_t)nb);
+  PdCells o, w;
+  o.build(view->X0, N, G);
+  if (gd || gs) {
+    w.build(view->U, N, G);
+    for (size_t i = 0; i < N; ++i) {
+      const int si = (int)i >= na;
+      for (int q = 0; q < 9; ++q) {
+        const int jx = (o.cx[i] + q % 3 - 1 + G.ncx) % G.ncx, jy = (o.cy[i] + q / 3 - 1 + G.ncy) % G.ncy;
+        const size_t jc = (size_t)jy * G.ncx + jx;
+        for (int32_t t = w.start[jc]; t < w.start[jc + 1]; ++t) {
+          const size_t j = (size_t)w.order[t];
+          const int k = kmcp::bin(E2, nb, kmcp::d2(kmcl::min_image(w.fx[j] - o.fx[i], G.BX),
+                                                   kmcl::min_image(w.fy[j] - o.fy[i], G.BY)));
+          if (k >= nb) continue;
+          if (i == j) {
+            if (gs) gs[(size_t)si * nb + k] += 1;
+          } else if (gd) {
+            gd[(size_t)kmcp::kind_a(si, (int)j >= na) * nb + k] += 1;
+          }
+        }
+      }
+    }
+  }
+  if (cu) {
+    for (int cy = 0; cy < G.ncy; ++cy)
+      for (int cx = 0; cx < G.ncx; ++cx) {
+        const size_t c = (size_t)cy * G.ncx + cx;
+        for (int q = 0; q < 5; ++q) {
+          int ox, oy;
+          kmcp::half_shell(q, &ox, &oy);
+          const size_t jc = (size_t)((cy + oy + G.ncy) % G.ncy) * G.ncx + (cx + ox + G.ncx) % G.ncx;
+          for (int32_t ta = o.start[c]; ta < o.start[c + 1]; ++ta)
+            for (int32_t tb = q == 0 ? ta + 1 : o.start[jc]; tb < o.start[jc + 1]; ++tb) {
+              const size_t i = (size_t)o.order[ta], j = (size_t)o.order[tb];
+              const int k = kmcp::bin(E2, nb, kmcp::d2(kmcl::min_image(o.fx[j] - o.fx[i], G.BX),
+                                                       kmcl::min_image(o.fy[j] - o.fy[i], G.BY)));
+              if (k >= nb) continue;
+              kmc_pd_cell* cell = &cu[(size_t)kmcp::kind_b((int)i >= na, (int)j >= na) * nb + k];
+              cell->n_pairs += 1;
+              const int64_t uix = view->U[2 * i] - view->X0[2 * i], uiy = view->U[2 * i + 1] - view->X0[2 * i + 1];
+              const int64_t ujx = view->U[2 * j] - view->X0[2 * j], ujy = view->U[2 * j + 1] - view->X0[2 * j + 1];
+              if (!kmcp::valid(view->flags[i], uix, uiy, G.F) || !kmcp::valid(view->flags[j], ujx, ujy, G.F)) continue;
+              cell->n_valid += 1;
+              lag_add(&cell->dot, (__int128)kmcp::dot(uix, uiy, ujx, ujy));
+              lag_add(&cell->sq, (__int128)kmcp::sq(uix, uiy, ujx, ujy));
+            }
+        }
+      }
   }
   return KMC_OK;
 }

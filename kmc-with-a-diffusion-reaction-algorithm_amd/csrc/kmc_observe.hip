@@ -1,6 +1,6 @@
 // kmc_observe.hip — the host side of the read-only layers over the committed
-// state (DESIGN.md §10-§19): their C-ABI calls, one section a layer, over the
-// kernels and the state structs of kmc_analysis.hip ... kmc_orient.hip.  Nothing
+// state (DESIGN.md §10-§20): their C-ABI calls, one section a layer, over the
+// kernels and the state structs of kmc_analysis.hip ... kmc_pairdyn.hip.  Nothing
 // here writes a buffer a step reads, so the trajectory, the step counter and
 // clusters_valid stay as they are.
 //
@@ -1544,6 +1544,184 @@ int kmc_lag_arrays(kmc_sim* s, int64_t* U, int32_t* last_event) {
 
 int kmc_lag_end(kmc_sim* s) {
   return s ? rec_end(s, s->lag) : KMC_ERR_ARG;
+}
+
+// ---------------------------------------------------------------- pair dynamics
+// kmc_pairdyn.hip: a recorder with one origin, on the lag correlator's life
+// cycle (begin allocates, end frees).  Its update advances the per-protein
+// state only; the sample does the device work: it bins the current positions
+// and runs the two pair walks into tables it zeroed.
+
+static_assert(KMC_PD_MAX_BINS == PD_MAX_BINS && KMC_PD_JUMPED == PD_JUMPED, "kmc.h and kmc_pairdyn.h agree");
+static_assert(sizeof(kmc_pd_cell) == sizeof(pd_u64) * PD_CU_WORDS && offsetof(kmc_pd_cell, dot) == 16 &&
+                  offsetof(kmc_pd_cell, sq) == 32,
+              "kmc_pd_cell is the layout k_pd_walk adds into");
+
+static const char* const PD_OFF = "pd: not begun (kmc_pd_begin; a new state drops the recorder)";
+
+int kmc_pd_begin(kmc_sim* s, const kmc_pd_config* cfg) {
+  if (!s) return KMC_ERR_ARG;
+  if (!cfg) return fail(s, KMC_ERR_ARG, "pd: the configuration is needed");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  kmc_pd_config c = *cfg;
+  kmcp::Grid G;
+  int64_t E[PD_MAX_BINS + 1];
+  const char* bad = kmcp::check(c.every, c.nbins, c.r_max, s->K.box_x, s->K.box_y, &c.max_jump, &c.max_disp, &G, E);
+  if (bad) return fail(s, KMC_ERR_ARG, bad);
+  // a recorder that was on ends here, whatever becomes of this call
+  rc = rec_end(s, s->pd);
+  if (rc != KMC_OK) return rc;
+  // debug: the pair walks stage fewer points at a time
+  s->pd.chunk = (int)int_getenv("KMC_DEBUG_PD_CHUNK", PD_CHUNK, 1, PD_CHUNK);
+  const size_t N = (size_t)s->K.N, ncnt = (size_t)G.ncx * G.ncy + 1;
+  const int nb = G.nbins;
+  Scratch& g = s->pd.scratch;
+  Pd& D = s->pd.dev;
+  rc = KMC_OK;
+  rc |= salloc(s, g, &D.prev, N);
+  rc |= salloc(s, g, &D.U, N);
+  rc |= salloc(s, g, &D.X0, N);
+  rc |= salloc(s, g, &D.flags, N);
+  rc |= salloc(s, g, &D.opos, N);
+  rc |= salloc(s, g, &D.opt, N);
+  rc |= salloc(s, g, &D.npt, N);
+  rc |= salloc(s, g, &D.upl, N);
+  rc |= salloc(s, g, &D.cell, N);
+  rc |= salloc(s, g, &D.rank, N);
+  rc |= salloc(s, g, &D.ccnt, ncnt);
+  rc |= salloc(s, g, &D.ocstart, ncnt);
+  rc |= salloc(s, g, &D.ncstart, ncnt);
+  rc |= salloc(s, g, &D.part, (ncnt + SCAN_TILE - 1) / SCAN_TILE);
+  rc |= salloc(s, g, &D.E2, (size_t)nb + 1);
+  rc |= salloc(s, g, &D.out, (size_t)(PD_A_BINS + PD_B_KINDS * PD_CU_WORDS) * nb + 1);
+  if (rc != KMC_OK) {
+    scratch_drop(s, s->pd);
+    return fail(s, KMC_ERR_HIP, "pd: allocation failed (109 bytes per protein and 12 per cell of the search grid)");
+  }
+  pd_u64 E2[PD_MAX_BINS + 1];
+  for (int m = 0; m <= nb; ++m) E2[m] = (pd_u64)E[m] * (pd_u64)E[m];
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpyAsync(D.E2, E2, sizeof(pd_u64) * (size_t)(nb + 1), hipMemcpyHostToDevice, s->stream));
+  if (N > 0) {
+    const unsigned gr = (unsigned)((N + PD_T - 1) / PD_T);
+    k_pd_begin<<<gr, PD_T, 0, s->stream>>>(s->K, s->d, D, G);  // (ccnt is zero: salloc)
+    bins_scan(s, D.ccnt, D.ocstart, (int)ncnt, D.part);
+    k_pd_origin_scatter<<<gr, PD_T, 0, s->stream>>>((int)N, D, G);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);  // (waits: E2 is read by the copy until here)
+  if (rc != KMC_OK) {
+    scratch_drop(s, s->pd);
+    return rc;
+  }
+  s->pd.cfg = c;
+  s->pd.G = G;
+  s->pd.inv_dr = (float)((double)nb / (double)E[nb]);
+  s->pd.rec = Recorder{true, s->step_done, s->step_done, 0};
+  return KMC_OK;
+}
+
+int kmc_pd_update(kmc_sim* s, kmc_pd_info* info) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = rec_check(s, s->pd.rec, PD_OFF);
+  if (rc != KMC_OK) return rc;
+  PdState& g = s->pd;
+  if (s->step_done != g.rec.last + g.cfg.every)
+    return fail(s, KMC_ERR_ARG, "pd: an update is due " + std::to_string(g.cfg.every) + " steps after the last one");
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N, nblk = (N + PD_T - 1) / PD_T;
+  pd_u64* n_jumped = g.dev.out + (size_t)(PD_A_BINS + PD_B_KINDS * PD_CU_WORDS) * g.G.nbins;
+  HIPCHK(s, hipMemsetAsync(n_jumped, 0, sizeof(pd_u64), s->stream));
+  if (nblk > 0)
+    k_pd_update<<<(unsigned)std::min(nblk, AN_WG_MAX), PD_T, 0, s->stream>>>(s->K, s->d, g.dev, g.G, nblk, n_jumped);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) {
+    g.rec.on = false;  // the per-protein state may be half advanced
+    return rc;
+  }
+  g.rec.last = s->step_done;
+  g.rec.updates += 1;
+  if (info) {
+    pd_u64 nj = 0;
+    HIPCHK(s, hipMemcpy(&nj, n_jumped, sizeof nj, hipMemcpyDeviceToHost));
+    info->n_updates = g.rec.updates;
+    info->n_jumped = (int64_t)nj;
+  }
+  return KMC_OK;
+}
+
+int kmc_pd_sample(kmc_sim* s, kmc_pd_out* out, int64_t* gd, int64_t* gs, kmc_pd_cell* cu) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "pd sample: out is needed");
+  int rc = rec_check(s, s->pd.rec, PD_OFF);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  PdState& g = s->pd;
+  const kmcp::Grid& G = g.G;
+  const int N = s->K.N, nb = G.nbins, ncell = G.ncx * G.ncy;
+  const size_t nout = (size_t)(PD_A_BINS + PD_B_KINDS * PD_CU_WORDS) * nb;
+  const bool part_a = gd || gs, part_b = cu != nullptr;
+  hipStream_t st = s->stream;
+  if (part_a || part_b) HIPCHK(s, hipMemsetAsync(g.dev.out, 0, sizeof(pd_u64) * nout, st));
+  if ((part_a || part_b) && N > 0) {
+    const Pd& D = g.dev;
+    const unsigned gr = (unsigned)((N + PD_T - 1) / PD_T);
+    const unsigned gw = (unsigned)std::min((ncell + PD_WAVES - 1) / PD_WAVES, AN_WG_MAX);
+    HIPCHK(s, hipMemsetAsync(D.ccnt, 0, sizeof(int32_t) * (size_t)(ncell + 1), st));
+    k_pd_now<<<gr, PD_T, 0, st>>>(N, D, G);
+    bins_scan(s, D.ccnt, D.ncstart, ncell + 1, D.part);
+    k_pd_now_scatter<<<gr, PD_T, 0, st>>>(N, D, G);
+    const size_t fixed = sizeof(pd_u64) * (size_t)(nb + 1);
+    if (part_a)
+      k_pd_walk<false><<<gw, PD_T, sizeof(int4) * 2 * PD_WAVES * (size_t)g.chunk + fixed + sizeof(pd_u64) * PD_A_BINS * nb,
+                         st>>>(D, G, s->K.NA, g.chunk, g.inv_dr);
+    if (part_b)
+      k_pd_walk<true><<<gw, PD_T,
+                        sizeof(int4) * 4 * PD_WAVES * (size_t)g.chunk + fixed +
+                            sizeof(pd_u64) * PD_B_KINDS * PD_CU_WORDS * nb,
+                        st>>>(D, G, s->K.NA, g.chunk, g.inv_dr);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  std::memset(out, 0, sizeof *out);
+  out->cfg = g.cfg;
+  out->J = G.J;
+  out->F = G.F;
+  out->BX = G.BX;
+  out->BY = G.BY;
+  out->ncx = G.ncx;
+  out->ncy = G.ncy;
+  out->origin_step = g.rec.origin;
+  out->last_step = g.rec.last;
+  out->n_updates = g.rec.updates;
+  static_assert(sizeof(pd_u64) == sizeof(int64_t), "the bins are copied out as they are");
+  if (gd) HIPCHK(s, hipMemcpy(gd, g.dev.out, sizeof(pd_u64) * 4 * (size_t)nb, hipMemcpyDeviceToHost));
+  if (gs) HIPCHK(s, hipMemcpy(gs, g.dev.out + 4 * (size_t)nb, sizeof(pd_u64) * 2 * (size_t)nb, hipMemcpyDeviceToHost));
+  if (cu)
+    HIPCHK(s, hipMemcpy(cu, g.dev.out + (size_t)PD_A_BINS * nb, sizeof(kmc_pd_cell) * PD_B_KINDS * (size_t)nb,
+                        hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_pd_arrays(kmc_sim* s, int64_t* U, int64_t* X0, uint8_t* flags) {
+  if (!s) return KMC_ERR_ARG;
+  const int rc = rec_check(s, s->pd.rec, PD_OFF);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  if (U && N) HIPCHK(s, hipMemcpy(U, s->pd.dev.U, sizeof(longlong2) * N, hipMemcpyDeviceToHost));
+  if (X0 && N) HIPCHK(s, hipMemcpy(X0, s->pd.dev.X0, sizeof(longlong2) * N, hipMemcpyDeviceToHost));
+  if (flags && N) HIPCHK(s, hipMemcpy(flags, s->pd.dev.flags, N, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_pd_end(kmc_sim* s) {
+  return s ? rec_end(s, s->pd) : KMC_ERR_ARG;
 }
 
 // ---------------------------------------------------------------- orientation

@@ -91,6 +91,15 @@
 //                              rot step origin n_updates every levels slots
 //                            and per non-empty cell (the 128-bit sums in decimal; v: 0 heading / axis, 1 arm)
 //                              cell step origin row lag class v n_pairs n_all n_clean s1_all s1_clean s2_clean
+//           [--pd EVERY SAMPLE_EVERY RMAX NBINS FILE]  pair dynamics (kmc_pd_*): distinct van Hove and
+//                            displacement correlation against the origin where the process starts or
+//                            resumes (not checkpointed: a new origin, every line carries it); updates
+//                            every EVERY steps as --lag's, and after every SAMPLE_EVERY-th update FILE gets
+//                              pd step origin n_updates every nbins J F BX BY
+//                            and per non-empty cell (the 128-bit sums in decimal)
+//                              gd step origin kind k count             (kind = 2 species(i) + species(j))
+//                              gs step origin species k count
+//                              cu step origin kind k n_pairs n_valid dot sq   (kind: 0 AA, 1 AB, 2 BB)
 //           [--pose NZ NC FILE]  ligand pose census (kmc_ligand_pose) of every output step:
 //                              pose step nz nc n_bad chi_pos[0..3] chi_neg[0..3]
 //                              bin step k zbin tiltbin count          (non-zero bins)
@@ -117,6 +126,38 @@ std::string dec128(kmc_i128 w) {
     u /= 10;
   } while (u);
   return neg ? "-" + d : d;
+}
+
+// --pd: one sample's non-empty cells appended to path, every line with the current and the origin step
+int pd_append(kmc_sim* s, const char* path) {
+  kmc_pd_out k;
+  int rc = kmc_pd_sample(s, &k, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  const int nb = k.cfg.nbins;
+  std::vector<int64_t> gd((size_t)4 * nb), gs((size_t)2 * nb);
+  std::vector<kmc_pd_cell> cu((size_t)3 * nb);
+  rc = kmc_pd_sample(s, &k, gd.data(), gs.data(), cu.data());
+  if (rc) return rc;
+  FILE* f = fopen(path, "ab");
+  if (!f) return KMC_ERR_IO;
+  const long long step = (long long)k.last_step, o = (long long)k.origin_step;
+  fprintf(f, "pd %lld %lld %lld %d %d %lld %lld %lld %lld\n", step, o, (long long)k.n_updates, k.cfg.every, nb,
+          (long long)k.J, (long long)k.F, (long long)k.BX, (long long)k.BY);
+  for (int t = 0; t < 4; ++t)
+    for (int b = 0; b < nb; ++b)
+      if (gd[(size_t)t * nb + b]) fprintf(f, "gd %lld %lld %d %d %lld\n", step, o, t, b, (long long)gd[(size_t)t * nb + b]);
+  for (int t = 0; t < 2; ++t)
+    for (int b = 0; b < nb; ++b)
+      if (gs[(size_t)t * nb + b]) fprintf(f, "gs %lld %lld %d %d %lld\n", step, o, t, b, (long long)gs[(size_t)t * nb + b]);
+  for (int t = 0; t < 3; ++t)
+    for (int b = 0; b < nb; ++b) {
+      const kmc_pd_cell& w = cu[(size_t)t * nb + b];
+      if (w.n_pairs)
+        fprintf(f, "cu %lld %lld %d %d %lld %lld %s %s\n", step, o, t, b, (long long)w.n_pairs, (long long)w.n_valid,
+                dec128(w.dot).c_str(), dec128(w.sq).c_str());
+    }
+  fclose(f);
+  return KMC_OK;
 }
 
 bool set_field(kmc_params* p, const std::string& k, const std::string& v) {
@@ -171,6 +212,9 @@ int main(int argc, char** argv) {
   std::memset(&lag_cfg, 0, sizeof lag_cfg);
   std::string rot_path, pose_path;
   kmc_rot_config rot_cfg = {0, 0, 0};
+  std::string pd_path;
+  kmc_pd_config pd_cfg = {0, 0, 0.0, 0.0, 0.0};
+  int pd_sample_every = 0;
   int pose_nz = 0, pose_nc = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -281,6 +325,18 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--pd") {
+      pd_cfg.every = atoi(next().c_str());
+      pd_sample_every = atoi(next().c_str());
+      pd_cfg.r_max = strtod(next().c_str(), nullptr);
+      pd_cfg.nbins = atoi(next().c_str());
+      pd_path = next();
+      if (pd_cfg.every < 1 || pd_sample_every < 1 || !(pd_cfg.r_max > 0.0) || pd_cfg.nbins < 1 ||
+          pd_cfg.nbins > KMC_PD_MAX_BINS) {
+        fprintf(stderr, "kmc_run: bad --pd %d %d %g %d\n", pd_cfg.every, pd_sample_every, pd_cfg.r_max, pd_cfg.nbins);
+        return 2;
+      }
+    }
     else if (a == "--rot") {
       rot_cfg.every = atoi(next().c_str());
       rot_cfg.levels = atoi(next().c_str());
@@ -345,6 +401,7 @@ int main(int argc, char** argv) {
     if (!cf_path.empty()) truncate(cf_path.c_str());
     if (!lag_path.empty()) truncate(lag_path.c_str());
     if (!rot_path.empty()) truncate(rot_path.c_str());
+    if (!pd_path.empty()) truncate(pd_path.c_str());
     if (!pose_path.empty()) truncate(pose_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
@@ -387,13 +444,19 @@ int main(int argc, char** argv) {
     rc = kmc_rot_begin(s, &rot_cfg);
     if (rc) return die(s, rc, "rot begin");
   }
+  int64_t pd_left = pd_cfg.every;
+  if (!pd_path.empty()) {
+    rc = kmc_pd_begin(s, &pd_cfg);
+    if (rc) return die(s, rc, "pd begin");
+  }
   int64_t step = kmc_current_step(s);
   while (step < p.simu_step) {
     int64_t next_out = (step / p.out_interval + 1) * p.out_interval;
     int64_t end = next_out < p.simu_step ? next_out : p.simu_step;
     int64_t n = end - step;
     obs.resize((size_t)n);
-    if (dyn_path.empty() && kin_path.empty() && cf_path.empty() && lag_path.empty() && rot_path.empty()) {
+    if (dyn_path.empty() && kin_path.empty() && cf_path.empty() && lag_path.empty() && rot_path.empty() &&
+        pd_path.empty()) {
       rc = kmc_step(s, n, obs.data());
       if (rc) return die(s, rc, "kmc_step");
     } else {
@@ -408,6 +471,7 @@ int main(int argc, char** argv) {
         if (cf_left < m) m = cf_left;
         if (!lag_path.empty() && lag_left < m) m = lag_left;
         if (!rot_path.empty() && rot_left < m) m = rot_left;
+        if (!pd_path.empty() && pd_left < m) m = pd_left;
         rc = kmc_step(s, m, obs.data() + done);
         if (rc) return die(s, rc, "kmc_step");
         done += m;
@@ -416,6 +480,7 @@ int main(int argc, char** argv) {
         cf_left -= m;
         lag_left -= m;
         rot_left -= m;
+        pd_left -= m;
         if (!dyn_path.empty() && (dyn_left == 0 || done == n)) {
           rc = kmc_track_update(s, nullptr);
           if (rc) return die(s, rc, "track update");
@@ -440,6 +505,16 @@ int main(int argc, char** argv) {
           rc = kmc_rot_update(s, nullptr);
           if (rc) return die(s, rc, "rot update");
           rot_left = rot_cfg.every;
+        }
+        if (!pd_path.empty() && pd_left == 0) {
+          kmc_pd_info info;
+          rc = kmc_pd_update(s, &info);
+          if (rc) return die(s, rc, "pd update");
+          pd_left = pd_cfg.every;
+          if (info.n_updates % pd_sample_every == 0) {
+            rc = pd_append(s, pd_path.c_str());
+            if (rc) return die(s, rc, "pd sample");
+          }
         }
       }
     }

@@ -154,6 +154,15 @@ def load_library(path: Optional[str] = None):
     L.kmc_lag_sample.argtypes = [C.c_void_p, P(capi.LagOut), C.c_void_p, C.c_void_p]
     L.kmc_lag_arrays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.kmc_lag_end.argtypes = [C.c_void_p]
+    L.kmc_pd_begin.argtypes = [C.c_void_p, P(capi.PdConfig)]
+    L.kmc_pd_update.argtypes = [C.c_void_p, P(capi.PdInfo)]
+    L.kmc_pd_sample.argtypes = [C.c_void_p, P(capi.PdOut), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kmc_pd_arrays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kmc_pd_end.argtypes = [C.c_void_p]
+    L.kmc_host_pd_begin.argtypes = [P(capi.Params), P(capi.StateView), P(capi.PdConfig), P(capi.PdView), P(capi.PdOut)]
+    L.kmc_host_pd_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.PdView), P(capi.PdOut), P(capi.PdInfo)]
+    L.kmc_host_pd_sample.argtypes = [P(capi.Params), P(capi.PdView), P(capi.PdOut), P(capi.PdOut), C.c_void_p,
+                                     C.c_void_p, C.c_void_p]
     L.kmc_host_lag_begin.argtypes = [P(capi.Params), P(capi.StateView), P(capi.LagConfig), P(capi.LagView),
                                      P(capi.LagOut)]
     L.kmc_host_lag_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.LagView), P(capi.LagOut),
@@ -463,6 +472,43 @@ class HostLag:
         return capi.LagSample(out, table, n_pairs)
 
 
+def _pd_tables(nbins: int):
+    nb = max(1, min(int(nbins), capi.PD_MAX_BINS))
+    return (np.zeros((4, nb), dtype=np.int64), np.zeros((2, nb), dtype=np.int64),
+            np.zeros((3, nb), dtype=capi.PD_CELL_DTYPE))
+
+
+class HostPd:
+    """Pair dynamics on host states, sequentially (kmc_host_pd_*): Simulation.pd_*'s counterpart without a device.
+    The recorder begins at hs (update 0); update(hs) advances it to the state `every` steps later.  arrays
+    (capi.PdArrays) holds its per-protein state."""
+
+    def __init__(self, params: capi.Params, hs: capi.HostState, config: capi.PdConfig):
+        self.params = params
+        self.arrays = capi.PdArrays(params.n_a + params.n_b)
+        self.acc = capi.PdOut()
+        v = hs.view()
+        _host_check(load_library().kmc_host_pd_begin(C.byref(params), C.byref(v), C.byref(config),
+                                                     C.byref(self.arrays.view()), C.byref(self.acc)))
+
+    def update(self, hs: capi.HostState) -> capi.PdInfo:
+        """Advance the recorder to hs (kmc_host_pd_update)."""
+        v = hs.view()
+        info = capi.PdInfo()
+        _host_check(load_library().kmc_host_pd_update(C.byref(self.params), C.byref(v), C.byref(self.arrays.view()),
+                                                      C.byref(self.acc), C.byref(info)))
+        return info
+
+    def sample(self) -> capi.PdSample:
+        """The tables of the state as of the last update — kmc_host_pd_sample."""
+        out = capi.PdOut()
+        gd, gs, cu = _pd_tables(self.acc.cfg.nbins)
+        _host_check(load_library().kmc_host_pd_sample(C.byref(self.params), C.byref(self.arrays.view()),
+                                                      C.byref(self.acc), C.byref(out), gd.ctypes.data, gs.ctypes.data,
+                                                      cu.ctypes.data))
+        return capi.PdSample(out, gd, gs, cu)
+
+
 class HostRot:
     """The orientation recorder on host states, sequentially (kmc_host_rot_*): Simulation.rot_*'s counterpart without
     a device.  The recorder begins at hs (update 0); update(hs) advances it to the state `every` steps later.
@@ -769,7 +815,7 @@ class Simulation:
 
     @property
     def analysis_ms(self) -> float:
-        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / lag_* / rot_* / ligand_pose / unwrap /
+        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / lag_* / rot_* / pd_* / ligand_pose / unwrap /
         cluster_* / structure_factor / bond_order / bond_order_corr / network / rings call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
@@ -974,6 +1020,57 @@ class Simulation:
             done += every
             info = self.lag_update()
         return recs, info
+
+    # ---- pair dynamics since a begin: distinct van Hove and displacement correlation (kmc_pairdyn.hip)
+    def pd_begin(self, config: capi.PdConfig) -> None:
+        """Start the pair dynamics at the current state (update 0; capi.pd_config builds the configuration).  It
+        allocates 109 bytes per protein and 12 per cell of the search grid, freed by pd_end."""
+        self._check(load_library().kmc_pd_begin(self._h, C.byref(config)))
+
+    def pd_update(self) -> capi.PdInfo:
+        """Advance the unwrapped positions; legal exactly `every` steps after the last update (or the begin)."""
+        info = capi.PdInfo()
+        self._check(load_library().kmc_pd_update(self._h, C.byref(info)))
+        return info
+
+    def pd_sample(self) -> capi.PdSample:
+        """The tables of the state as of the last update — kmc_pd_sample; analysis.van_hove_distinct and
+        analysis.displacement_corr turn them into G_d(r, t) and C_u(r, t)."""
+        out = capi.PdOut()
+        self._check(load_library().kmc_pd_sample(self._h, C.byref(out), None, None, None))
+        gd, gs, cu = _pd_tables(out.cfg.nbins)
+        self._check(load_library().kmc_pd_sample(self._h, C.byref(out), gd.ctypes.data, gs.ctypes.data, cu.ctypes.data))
+        return capi.PdSample(out, gd, gs, cu)
+
+    def pd_arrays(self):
+        """(U[N, 2] int64, X0[N, 2] int64, flags[N] uint8: capi.PD_JUMPED) by reference index (kmc_pd_arrays)."""
+        n = self.params.n_a + self.params.n_b
+        U = np.zeros((n, 2), dtype=np.int64)
+        X0 = np.zeros((n, 2), dtype=np.int64)
+        flags = np.zeros(n, dtype=np.uint8)
+        self._check(load_library().kmc_pd_arrays(self._h, U.ctypes.data, X0.ctypes.data, flags.ctypes.data))
+        return U, X0, flags
+
+    def pd_end(self) -> None:
+        self._check(load_library().kmc_pd_end(self._h))
+
+    def run_paired(self, nsteps: int, sample_every: int):
+        """Advance nsteps steps, `every` of the begun recorder's configuration at a time, with a pd_update after each
+        piece and a pd_sample after every sample_every-th update (nsteps must be a multiple of every).  Returns
+        (records[nsteps], the list of capi.PdSample)."""
+        out = capi.PdOut()
+        self._check(load_library().kmc_pd_sample(self._h, C.byref(out), None, None, None))
+        every = int(out.cfg.every)
+        if nsteps < 0 or nsteps % every or sample_every < 1:
+            raise ValueError("run_paired: nsteps >= 0, a multiple of the recorder's every; sample_every >= 1")
+        recs = np.zeros(nsteps, dtype=capi.OBS_DTYPE)
+        done, samples = 0, []
+        while done < nsteps:
+            self.step(every, recs[done:done + every])
+            done += every
+            if self.pd_update().n_updates % sample_every == 0:
+                samples.append(self.pd_sample())
+        return recs, samples
 
     # ---- orientation: the rotational lag correlator and the ligands' poses (kmc_orient.hip; DESIGN.md §19)
     def rot_begin(self, config: capi.RotConfig) -> None:
