@@ -1318,6 +1318,160 @@ int kmc_host_pd_update(const kmc_params* p, const kmc_state_view* v, const kmc_p
 int kmc_host_pd_sample(const kmc_params* p, const kmc_pd_view* view, const kmc_pd_out* acc, kmc_pd_out* out,
                        int64_t* gd, int64_t* gs, kmc_pd_cell* cu);
 
+/* Body dynamics: how a cluster of s proteins moves and how long
+ * it keeps its identity, against the one origin of kmc_bd_begin.  A BODY is a
+ * connected component of the bond graph at the begin (kmc_components' labels,
+ * single proteins included); per body the sample reports the displacement of
+ * its centre, its rigid rotation and its fate, filed by (holds a ligand, size).
+ * Like the pair dynamics it reads the CURRENT state, launches nothing inside
+ * kmc_step and leaves the state, the step counter and kmc_get_clusters'
+ * validity untouched; arrays are indexed by reference index.  All results are
+ * integers: the device, kmc_host_bd_* and the tests agree by equality, and the
+ * tables of replicas (and of recorders sampled at the same lag) add.
+ *
+ * Definitions — the device, kmc_host_bd_* and the tests share them:
+ *   integer coords  kmc_lag_*'s, with its minimum image, J and F (max_jump <= 0:
+ *                   min(box) / 4, else at most min(box) / 2; max_disp <= 0:
+ *                   16384 A, else at most 16384 A, so F <= 2^24).  KMC_ERR_ARG
+ *                   for a box of 2^21 A or more.
+ *   configuration   (kmc_bd_config) every >= 1; 2 <= max_size <= KMC_BD_MAX_SIZE.
+ *   bodies          static for the recorder's life: the label (the smallest
+ *                   reference index r, the ROOT), n_r, n_l, n = n_r + n_l, hl =
+ *                   (n_l > 0), the spanning bits of kmc_unwrap, and per member
+ *                   D0_i = X0_i + shift_i * B - X0_r with kmc_unwrap's image
+ *                   shifts (zero in a spanning body, as it reports them).  WIDE
+ *                   (KMC_BD_WIDE in the body's bits) when some |D0| component is
+ *                   >= 2^24.
+ *   per protein     prev, U, X0 (= U at the begin) and the three links as
+ *                   kmc_lag_* stores them; flags, sticky: KMC_BD_JUMPED when
+ *                   |d| >= J on an axis at an update, KMC_BD_CHANGED when a link
+ *                   differed from the stored one at an update (the stored links
+ *                   then become the current ones); u = U - X0.
+ *   kmc_bd_begin    is update 0.  The scratch (189 bytes per protein) is
+ *                   allocated here and freed by kmc_bd_end / kmc_destroy; a
+ *                   failed allocation is KMC_ERR_HIP with the recorder off.
+ *   kmc_bd_update   legal only when kmc_current_step() == the step of the last
+ *                   update + every (else KMC_ERR_ARG, nothing changes).
+ *   kmc_bd_sample   legal only at the step of the last update (else
+ *                   KMC_ERR_ARG), so that the flags and the current components
+ *                   describe one state.  With L_i the current kmc_components
+ *                   label, a body is
+ *                     BROKEN   its members carry more than one L;
+ *                     INTACT   one L, and that component has n members now (the
+ *                              membership is then the same);
+ *                     GROWN    one L, and that component is larger;
+ *                     PRISTINE no member has a flag (on a trajectory this
+ *                              implies INTACT);
+ *                     VALID    PRISTINE and |u| < F on both axes for every member.
+ *                   Translation of a VALID body: Su = sum of u_i (n times the
+ *                   displacement of its centre), T = Su.x^2 + Su.y^2 < 2^111.
+ *                   Rotation of a VALID body with 2 <= n <= KMC_BD_ROT_MAX, no
+ *                   spanning bit and not WIDE (every other VALID body of n >= 2
+ *                   counts in n_rot_skipped): D_i = D0_i + u_i - u_r,
+ *                     C = sum D0_i . D_i,  S = sum (D0x_i Dy_i - D0y_i Dx_i),
+ *                   int64, |.| < 2^61 (|D0| < 2^24, |D| < 2^26: a term is below
+ *                   2^51, at most 1023 of them).  C = S = 0 counts in n_rot_null;
+ *                   otherwise phi = atan2((double) S, (double) C) in (-pi, pi]
+ *                   and c1 = (int64) round_(cos(phi) 2^30), c2 = (int64)
+ *                   round_(cos(2 phi) 2^30), p = (int64) round_(phi 2^24), p^2
+ *                   summed (kmc_math.h's atan2, cos and round_).
+ *   table           [2][max_size + 1] kmc_bd_cell by hl and k = min(n,
+ *                   max_size); row 0 stays zero, the last row is the overflow
+ *                   row.  n_bodies and sum_size are static; n_intact + n_grown +
+ *                   n_broken = n_bodies; m2 = sum of T over VALID bodies.  Each
+ *                   call computes the table anew; table may be NULL.
+ *   kmc_bd_bodies   one kmc_bd_body per body of at least min_size >= 1 members,
+ *                   sorted by label, kmc_cluster_list's capacity rule.  su is
+ *                   zero unless VALID, C and S unless the rot bit is set;
+ *                   cur_label is the smallest current label among the members,
+ *                   cur_size that component's size.
+ *   kmc_bd_arrays   U [N][2], X0 [N][2], flags [N], label [N] (1-based), D0
+ *                   [N][2]; each may be NULL.
+ *   kmc_bd_get      copies the per-protein state out: prev, U, links and flags
+ *                   are needed, X0, label, D0 and bits are filled when given.
+ *   kmc_bd_put      loads prev, U, links and flags into a recorder that was
+ *                   begun on the current state and sets the step of the last
+ *                   update to last_step <= kmc_current_step().  The bodies, X0
+ *                   and D0 stay those of the begin.  A recorder's per-protein
+ *                   state can be carried across a saved state this way, and a
+ *                   test can set U and the flags by hand under a hand-built graph.
+ *   kmc_bd_end      drops the recorder and frees its memory; idempotent.
+ * kmc_analysis_ms covers the last call.  kmc_host_bd_*: the same from host
+ * state views, sequentially, no device; the caller owns the eight arrays of
+ * the kmc_bd_view and the kmc_bd_out that carries the recorder between calls.
+ * KMC_ERR_ARG for a null / out-of-range argument, a handle without state, a
+ * decomposed window, an update off the stride, a sample off the last update's
+ * step and a recorder that was not begun; KMC_ERR_STATE and KMC_ERR_CAPACITY as
+ * kmc_unwrap; kmc_set_state, kmc_load_*, kmc_init_random and kmc_dd_set_state
+ * drop the recorder. */
+#define KMC_BD_MAX_SIZE 255
+#define KMC_BD_ROT_MAX 1023
+#define KMC_BD_JUMPED 1
+#define KMC_BD_CHANGED 2
+#define KMC_BD_WIDE 4 /* beside KMC_SPAN_X and KMC_SPAN_Y in a body's bits */
+#define KMC_BD_INTACT 0
+#define KMC_BD_GROWN 1
+#define KMC_BD_BROKEN 2
+#define KMC_BD_IS_PRISTINE 1
+#define KMC_BD_IS_VALID 2
+#define KMC_BD_IS_ROT 4
+typedef struct kmc_bd_config {
+  int32_t every, max_size;
+  double max_jump, max_disp;
+} kmc_bd_config;
+typedef struct kmc_bd_info {
+  int64_t n_updates; /* n of this update */
+  int64_t n_jumped;  /* proteins that this update flagged KMC_BD_JUMPED for the first time */
+  int64_t n_changed; /* the same for KMC_BD_CHANGED */
+} kmc_bd_info;
+typedef struct kmc_bd_cell {
+  int64_t n_bodies, sum_size, n_pristine, n_intact, n_grown, n_broken, n_valid, n_rot, n_rot_null, n_rot_skipped, c1, c2;
+  kmc_i128 m2, phi2;
+} kmc_bd_cell;
+typedef struct kmc_bd_out {
+  kmc_bd_config cfg; /* as in effect: max_jump and max_disp resolved */
+  int64_t J, F, BX, BY;
+  int64_t origin_step, last_step, n_updates;
+  int64_t n_bodies; /* bodies of the origin, single proteins included */
+} kmc_bd_out;
+typedef struct kmc_bd_body {
+  int32_t label, n_r, n_l;
+  int32_t bits;   /* KMC_SPAN_X | KMC_SPAN_Y | KMC_BD_WIDE */
+  int32_t status; /* KMC_BD_INTACT / GROWN / BROKEN */
+  int32_t is;     /* KMC_BD_IS_PRISTINE | KMC_BD_IS_VALID | KMC_BD_IS_ROT */
+  int32_t cur_label, cur_size;
+  int64_t su[2], C, S;
+} kmc_bd_body;
+typedef struct kmc_bd_view {
+  int64_t* prev;  /* [N][2] */
+  int64_t* U;     /* [N][2] */
+  int64_t* X0;    /* [N][2] */
+  int32_t* links; /* [3][N] */
+  uint8_t* flags; /* [N] */
+  int32_t* label; /* [N] 1-based */
+  int64_t* D0;    /* [N][2] */
+  uint8_t* bits;  /* [N] the bits of the protein's body */
+} kmc_bd_view;
+int kmc_bd_begin(kmc_sim* s, const kmc_bd_config* cfg);
+int kmc_bd_update(kmc_sim* s, kmc_bd_info* info);
+int kmc_bd_sample(kmc_sim* s, kmc_bd_out* out, kmc_bd_cell* table /* [2][max_size + 1] */);
+/* device milliseconds of the last kmc_bd_sample with a table: the current components, the reduction, the finish
+ * (the memset of the table counts with the first) */
+int kmc_bd_sample_ms(const kmc_sim* s, double ms[3]);
+int kmc_bd_bodies(kmc_sim* s, int32_t min_size, int64_t cap, kmc_bd_body* rows, int64_t* n);
+int kmc_bd_arrays(kmc_sim* s, int64_t* U, int64_t* X0, uint8_t* flags, int32_t* label, int64_t* D0);
+int kmc_bd_get(kmc_sim* s, const kmc_bd_view* view);
+int kmc_bd_put(kmc_sim* s, const kmc_bd_view* view, int64_t last_step);
+int kmc_bd_end(kmc_sim* s);
+int kmc_host_bd_begin(const kmc_params* p, const kmc_state_view* v, const kmc_bd_config* cfg, const kmc_bd_view* view,
+                      kmc_bd_out* acc);
+int kmc_host_bd_update(const kmc_params* p, const kmc_state_view* v, const kmc_bd_view* view, kmc_bd_out* acc,
+                       kmc_bd_info* info);
+int kmc_host_bd_sample(const kmc_params* p, const kmc_state_view* v, const kmc_bd_view* view, const kmc_bd_out* acc,
+                       kmc_bd_out* out, kmc_bd_cell* table);
+int kmc_host_bd_bodies(const kmc_params* p, const kmc_state_view* v, const kmc_bd_view* view, const kmc_bd_out* acc,
+                       int32_t min_size, int64_t cap, kmc_bd_body* rows, int64_t* n);
+
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */
 int kmc_format_bond_line(const kmc_params* p, const kmc_obs* o, char* buf, size_t n);   /* main.cpp:2251 */

@@ -12,12 +12,13 @@ fragmentation kernels K(a, b), F(a, b) and the growth modes from the cluster
 growth recorder (cf_sample), the hexagon fraction and ring densities of the
 ligand network from the ring counts (rings), the distinct van Hove function
 G_d(r, t) and the displacement correlation C_u(r, t) from the pair dynamics
-(pd_sample), and the replica sums of integer histograms,
+(pd_sample), the centre-of-mass MSD, diffusion coefficient, rotation and
+survival of clusters by size from the body dynamics (bd_sample), and the replica sums of integer histograms,
 float64 sums and geometry tables.
 
 The counts and sums themselves come from libkmc (kmc_analysis.hip,
 kmc_dynamics.hip, kmc_geometry.hip, kmc_structure.hip, kmc_bondorder.hip,
-kmc_kinetics.hip, kmc_coag.hip, kmc_rings.hip, kmc_pairdyn.hip);
+kmc_kinetics.hip, kmc_coag.hip, kmc_rings.hip, kmc_pairdyn.hip, kmc_bodydyn.hip);
 nothing here touches a trajectory.
 """
 from __future__ import annotations
@@ -589,3 +590,90 @@ def displacement_corr(sample):
             if n:
                 valid[kind, k] = int(sample.n_valid[kind, k]) / n
     return 0.5 * (edges[:-1] + edges[1:]), cu, valid
+
+
+def _bd_rows_ok(sample):
+    """[2, max_size + 1] bool: the rows that hold one size only — every row but the overflow row, and that one too
+    when all its bodies have max_size members."""
+    ok = np.ones((2, sample.max_size + 1), dtype=bool)
+    ok[:, 0] = False
+    for hl in range(2):
+        ok[hl, -1] = int(sample.sum_size[hl, -1]) == int(sample.n_bodies[hl, -1]) * sample.max_size
+    return ok
+
+
+def body_msd(sample):
+    """(msd[2, max_size + 1], n_valid[2, max_size + 1]) from a capi.BdSample: the mean squared displacement of the
+    centre of mass in A^2 by (holds a ligand, size) over the VALID bodies, m2 / n_valid / size^2 / 2^20; NaN where no
+    body is valid and in an overflow row that mixes sizes."""
+    ms = sample.max_size
+    msd = np.full((2, ms + 1), np.nan)
+    n_valid = np.zeros((2, ms + 1), dtype=np.int64)
+    ok = _bd_rows_ok(sample)
+    for hl in range(2):
+        for k in range(1, ms + 1):
+            nv = int(sample.n_valid[hl, k])
+            n_valid[hl, k] = nv
+            if nv and ok[hl, k]:
+                msd[hl, k] = int(sample.m2[hl, k]) / nv / (k * k) / 2.0 ** 20
+    return msd, n_valid
+
+
+def body_diffusion(samples_with_lags, time_step):
+    """D(s) from capi.BdSamples of one configuration at several lags: samples_with_lags is an iterable of (lag in
+    steps, sample), time_step the time of one step.  Per (holds a ligand, size) the least-squares line through the
+    origin MSD = 4 D t over the lags that have valid bodies, D in A^2 per time unit (NaN without any), and per hl the
+    exponent gamma of D ~ s^-gamma, the slope of log D against log s over the sizes with D > 0 (NaN below two of
+    them).  Returns dict(size, D[2, max_size + 1], n_lags, gamma[2])."""
+    pairs = [(float(lag) * float(time_step), body_msd(s)[0]) for lag, s in samples_with_lags]
+    if not pairs:
+        raise ValueError("body_diffusion: no sample")
+    shape = pairs[0][1].shape
+    num, den, cnt = np.zeros(shape), np.zeros(shape), np.zeros(shape, dtype=np.int64)
+    for t, msd in pairs:
+        if msd.shape != shape:
+            raise ValueError("body_diffusion: samples of different max_size")
+        have = np.isfinite(msd) & (t > 0)
+        num[have] += t * msd[have]
+        den[have] += t * t
+        cnt[have] += 1
+    D = np.divide(num, 4.0 * den, out=np.full(shape, np.nan), where=den > 0)
+    size = np.arange(shape[1])
+    gamma = np.full(2, np.nan)
+    for hl in range(2):
+        use = np.isfinite(D[hl]) & (D[hl] > 0) & (size >= 1)
+        if use.sum() >= 2:
+            gamma[hl] = -np.polyfit(np.log(size[use]), np.log(D[hl][use]), 1)[0]
+    return dict(size=size, D=D, n_lags=cnt, gamma=gamma)
+
+
+def body_rotation(sample):
+    """dict(c1, c2, phi2, n_rot)[2, max_size + 1] from a capi.BdSample: the rotational correlators C_1 = <cos phi>
+    and C_2 = <cos 2 phi> and the mean squared angle <phi^2> in rad^2 (phi wrapped to (-pi, pi]) over the bodies
+    with a rotation, by (holds a ligand, size); NaN where there is none and in an overflow row that mixes sizes."""
+    ms = sample.max_size
+    out = dict(c1=np.full((2, ms + 1), np.nan), c2=np.full((2, ms + 1), np.nan), phi2=np.full((2, ms + 1), np.nan),
+               n_rot=np.zeros((2, ms + 1), dtype=np.int64))
+    ok = _bd_rows_ok(sample)
+    for hl in range(2):
+        for k in range(1, ms + 1):
+            n = int(sample.n_rot[hl, k])
+            out["n_rot"][hl, k] = n
+            if n and ok[hl, k]:
+                out["c1"][hl, k] = int(sample.c1[hl, k]) / n / 2.0 ** 30
+                out["c2"][hl, k] = int(sample.c2[hl, k]) / n / 2.0 ** 30
+                out["phi2"][hl, k] = int(sample.phi2[hl, k]) / n / 2.0 ** 48
+    return out
+
+
+def body_survival(sample):
+    """dict(pristine, intact, grown, broken, n_bodies)[2, max_size + 1] from a capi.BdSample: the fractions of the
+    origin's bodies by (holds a ligand, size) that are untouched, that have the same members, that are together in a
+    larger cluster, and that have fallen apart; intact + grown + broken = 1; NaN where there is no body."""
+    ms = sample.max_size
+    n = np.array([[int(x) for x in row] for row in sample.n_bodies], dtype=np.float64)
+    out = dict(n_bodies=n.astype(np.int64))
+    for name in ("pristine", "intact", "grown", "broken"):
+        c = np.array([[int(x) for x in row] for row in getattr(sample, "n_" + name)], dtype=np.float64)
+        out[name] = np.divide(c, n, out=np.full((2, ms + 1), np.nan), where=n > 0)
+    return out

@@ -741,6 +741,134 @@ class PdArrays:
         return v
 
 
+BD_MAX_SIZE, BD_ROT_MAX = 255, 1023                 # KMC_BD_MAX_SIZE, KMC_BD_ROT_MAX
+BD_JUMPED, BD_CHANGED, BD_WIDE = 1, 2, 4            # KMC_BD_JUMPED, KMC_BD_CHANGED; KMC_BD_WIDE beside SPAN_X, SPAN_Y
+BD_INTACT, BD_GROWN, BD_BROKEN = 0, 1, 2            # a body's status
+BD_IS_PRISTINE, BD_IS_VALID, BD_IS_ROT = 1, 2, 4    # the bits of kmc_bd_body.is
+
+
+class BdConfig(C.Structure):
+    """kmc_bd_config — the body dynamics' configuration."""
+
+    _fields_ = [("every", C.c_int32), ("max_size", C.c_int32), ("max_jump", C.c_double), ("max_disp", C.c_double)]
+
+
+def bd_config(every: int, max_size: int, max_jump: float = 0.0, max_disp: float = 0.0) -> BdConfig:
+    return BdConfig(int(every), int(max_size), float(max_jump), float(max_disp))
+
+
+class BdInfo(C.Structure):
+    """kmc_bd_info — one update: its number n and the proteins it flagged jumped / changed for the first time."""
+
+    _fields_ = [(name, C.c_int64) for name in ("n_updates", "n_jumped", "n_changed")]
+
+
+class BdOut(C.Structure):
+    """kmc_bd_out — the configuration in effect, the integer bounds and box, the steps, the number of bodies."""
+
+    _fields_ = [("cfg", BdConfig)] + [(name, C.c_int64) for name in (
+        "J", "F", "BX", "BY", "origin_step", "last_step", "n_updates", "n_bodies")]
+
+
+class BdBody(C.Structure):
+    """kmc_bd_body — one body of the origin in a sample (bd_bodies)."""
+
+    _fields_ = [(name, C.c_int32) for name in ("label", "n_r", "n_l", "bits", "status", "is_", "cur_label",
+                                               "cur_size")] + [("su", C.c_int64 * 2), ("C", C.c_int64), ("S", C.c_int64)]
+
+    def as_tuple(self):
+        return (self.label, self.n_r, self.n_l, self.bits, self.status, self.is_, self.cur_label, self.cur_size,
+                self.su[0], self.su[1], self.C, self.S)
+
+
+assert C.sizeof(BdBody) == 64
+BD_BODY_DTYPE = np.dtype(BdBody)  # the rows of bd_bodies as a numpy record array: the same fields, su [2]
+
+
+class BdView(C.Structure):
+    """kmc_bd_view — caller-owned arrays of the recorder on the host."""
+
+    _fields_ = [("prev", C.POINTER(C.c_int64)), ("U", C.POINTER(C.c_int64)), ("X0", C.POINTER(C.c_int64)),
+                ("links", C.POINTER(C.c_int32)), ("flags", C.POINTER(C.c_uint8)), ("label", C.POINTER(C.c_int32)),
+                ("D0", C.POINTER(C.c_int64)), ("bits", C.POINTER(C.c_uint8))]
+
+
+BD_COUNTS = ("n_bodies", "sum_size", "n_pristine", "n_intact", "n_grown", "n_broken", "n_valid", "n_rot", "n_rot_null",
+             "n_rot_skipped", "c1", "c2")
+BD_SUMS = ("m2", "phi2")
+# kmc_bd_cell as a numpy record
+BD_CELL_DTYPE = np.dtype([(name, "<i8") for name in BD_COUNTS] + [(name, I128_DTYPE) for name in BD_SUMS])
+assert BD_CELL_DTYPE.itemsize == 128
+
+
+class BdSample:
+    """One kmc_bd_sample: the configuration and steps (as attributes and in .out) and, as [2, max_size + 1] arrays of
+    Python ints indexed by (holds a ligand, min(size, max_size)), the fields of kmc_bd_cell (the 128-bit sums whole).
+    lag_steps = last_step - origin_step.  counts() / from_counts(): the sample as one int64 vector that adds
+    (analysis.reduce_counts) — over replicas, and over recorders sampled at the same lag."""
+
+    def __init__(self, out: BdOut, table: np.ndarray):
+        self.out = out
+        self.every, self.max_size = out.cfg.every, out.cfg.max_size
+        self.max_jump, self.max_disp = out.cfg.max_jump, out.cfg.max_disp
+        for name in ("J", "F", "BX", "BY", "origin_step", "last_step", "n_updates"):
+            setattr(self, name, int(getattr(out, name)))
+        self.total_bodies = int(out.n_bodies)
+        self.lag_steps = self.last_step - self.origin_step
+        for name in BD_COUNTS:
+            setattr(self, name, table[name].astype(object))
+        for name in BD_SUMS:
+            setattr(self, name, _i128_ints(table[name]))
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name in BD_COUNTS + BD_SUMS}
+
+    def counts(self) -> np.ndarray:
+        """[2 * (max_size + 1) * (12 + 2 * 4)] int64: per cell the counts, then both sums' limbs."""
+        v = []
+        for idx in np.ndindex(2, self.max_size + 1):
+            v += [int(getattr(self, name)[idx]) for name in BD_COUNTS]
+            for name in BD_SUMS:
+                x = int(getattr(self, name)[idx])
+                v += [x >> 32 * m & 0xFFFFFFFF for m in range(LAG_LIMBS - 1)] + [x >> 32 * (LAG_LIMBS - 1)]
+        return np.array(v, dtype=np.int64)
+
+    def from_counts(self, counts) -> "BdSample":
+        """A sample of this one's configuration holding the (summed) counts() vector."""
+        import copy
+        s = copy.copy(self)
+        it = iter(int(x) for x in np.asarray(counts).ravel())
+        for name in BD_COUNTS + BD_SUMS:
+            setattr(s, name, np.zeros((2, self.max_size + 1), dtype=object))
+        for idx in np.ndindex(2, self.max_size + 1):
+            for name in BD_COUNTS:
+                getattr(s, name)[idx] = next(it)
+            for name in BD_SUMS:
+                getattr(s, name)[idx] = sum(next(it) << 32 * m for m in range(LAG_LIMBS))
+        return s
+
+
+class BdArrays:
+    """numpy-backed kmc_bd_view for n proteins: prev, U, X0, D0 [n, 2] int64, links [3, n] int32, flags, bits [n]
+    uint8 and label [n] int32 (1-based)."""
+
+    def __init__(self, n: int):
+        self.prev = np.zeros((n, 2), dtype=np.int64)
+        self.U = np.zeros((n, 2), dtype=np.int64)
+        self.X0 = np.zeros((n, 2), dtype=np.int64)
+        self.links = np.zeros((3, n), dtype=np.int32)
+        self.flags = np.zeros(n, dtype=np.uint8)
+        self.label = np.zeros(n, dtype=np.int32)
+        self.D0 = np.zeros((n, 2), dtype=np.int64)
+        self.bits = np.zeros(n, dtype=np.uint8)
+
+    def view(self) -> BdView:
+        v = BdView()
+        for name, ptr in BdView._fields_:
+            setattr(v, name, getattr(self, name).ctypes.data_as(ptr))
+        return v
+
+
 ROT_VECS, POSE_MAX_BINS, POSE_CLASSES = 2, 64, 4  # KMC_ROT_VECS, KMC_POSE_MAX_BINS, KMC_POSE_CLASSES
 ROT_BAD = 1 << 63                                  # KMC_ROT_BAD: the packed word of a bad protein's vector
 

@@ -27,6 +27,7 @@
 #include "kmc_lagcorr.hip"
 #include "kmc_orient.hip"
 #include "kmc_pairdyn.hip"
+#include "kmc_bodydyn.hip"
 
 using namespace kmcd;
 
@@ -165,8 +166,11 @@ struct __attribute__((visibility("hidden"))) kmc_sim {
   LagState lag;
   RotState rot;
   PdState pd;
+  BdState bd;
   PoseState pose;
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
+  hipEvent_t bd_ev[2] = {nullptr, nullptr};  // after the components and after the reduction of the last kmc_bd_sample
+  double bd_ms[3] = {0.0, 0.0, 0.0};         // its components, reduction and finish (kmc_bd_sample_ms)
   double an_ms = 0.0;
 };
 
@@ -529,6 +533,8 @@ int kmc_destroy(kmc_sim* s) {
   for (auto& g : s->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   if (s->side) (void)hipStreamSynchronize(s->side);
+  for (auto& e : s->bd_ev)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : s->an_ev)
     if (e) (void)hipEventDestroy(e);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
@@ -818,6 +824,7 @@ static int set_state_impl(kmc_sim* s, const kmc_state_view* v) {
   s->lag.rec.on = false;  // and the lag correlator's origins
   s->rot.rec.on = false;  // and the orientation recorder's
   s->pd.rec.on = false;   // and the pair dynamics' origin
+  s->bd.rec.on = false;   // and the body dynamics' bodies
   return KMC_OK;
 }
 

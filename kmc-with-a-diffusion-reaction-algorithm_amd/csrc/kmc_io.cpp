@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/kmc.h"
+#include "kmc_bodydyn.h"
 #include "kmc_bondorder.h"
 #include "kmc_coag.h"
 #include "kmc_host.h"
@@ -2303,6 +2304,249 @@ int kmc_host_pd_sample(const kmc_params* p, const kmc_pd_view* view, const kmc_p
             }
         }
       }
+  }
+  return KMC_OK;
+}
+
+// Body dynamics (include/kmc.h), sequential: the bodies are the components of
+// kmc_host_cluster_geometry at the begin, with its image shifts; the
+// per-protein step is the lag correlator's; the sample labels the current
+// components (kmc_host_census) and walks each body's members in index order.
+// C and S are summed as include/kmc.h defines them, member by member with D =
+// D0 + u - u_r — not through the device's rearrangement; the verdict's bounds
+// and the rotation terms are kmc_bodydyn.h's.
+extern "C++" {
+namespace {
+
+bool bd_view_ok(const kmc_bd_view* w) {
+  return w && w->prev && w->U && w->X0 && w->links && w->flags && w->label && w->D0 && w->bits;
+}
+
+// one row per body, in label order, from the view and the current state
+int bd_host_rows(const kmc_params* p, const kmc_state_view* v, const kmc_bd_view* w, const kmc_bd_out* acc,
+                 std::vector<kmc_bd_body>* rows) {
+  const int na = p->n_a, n = p->n_a + p->n_b;
+  std::vector<int32_t> cur((size_t)n), size((size_t)n + 1, 0);
+  kmc_census census;
+  const int rc = kmc_host_census(p, v, cur.data(), 0, 0, nullptr, &census);
+  if (rc != KMC_OK) return rc;
+  for (int i = 0; i < n; ++i) size[(size_t)cur[i]] += 1;
+  // the members of every body, in index order: a counting sort by label
+  std::vector<int32_t> start((size_t)n + 2, 0), order((size_t)n);
+  for (int i = 0; i < n; ++i) start[(size_t)w->label[i] + 1] += 1;
+  for (int r = 1; r <= n; ++r) start[(size_t)r + 1] += start[r];
+  std::vector<int32_t> at(start.begin(), start.end() - 1);
+  for (int i = 0; i < n; ++i) order[(size_t)at[(size_t)w->label[i]]++] = i;
+  rows->clear();
+  for (int r = 1; r <= n; ++r) {
+    const int m = start[(size_t)r + 1] - start[r];
+    if (!m) continue;
+    const int32_t* mem = &order[(size_t)start[r]];
+    kmc_bd_body b;
+    std::memset(&b, 0, sizeof b);
+    b.label = r;
+    b.bits = w->bits[r - 1];
+    int orbits = 0, lmin = n + 1, lmax = 0;
+    for (int t = 0; t < m; ++t) {
+      const size_t i = (size_t)mem[t];
+      ((int)i < na ? b.n_r : b.n_l) += 1;
+      orbits |= kmcb::member_bits(w->flags[i], w->U[2 * i] - w->X0[2 * i], w->U[2 * i + 1] - w->X0[2 * i + 1], acc->F);
+      lmin = std::min(lmin, (int)cur[i]);
+      lmax = std::max(lmax, (int)cur[i]);
+    }
+    b.cur_label = lmin;
+    b.cur_size = size[(size_t)lmin];
+    b.status = lmin != lmax ? KMC_BD_BROKEN : b.cur_size == m ? KMC_BD_INTACT : KMC_BD_GROWN;
+    if (!(orbits & (BD_JUMPED | BD_CHANGED))) b.is |= KMC_BD_IS_PRISTINE;
+    if (!orbits) {
+      b.is |= KMC_BD_IS_VALID;
+      const size_t q = (size_t)r - 1;
+      const int64_t ur[2] = {w->U[2 * q] - w->X0[2 * q], w->U[2 * q + 1] - w->X0[2 * q + 1]};
+      const bool rot = m >= 2 && m <= KMC_BD_ROT_MAX && !b.bits;
+      for (int t = 0; t < m; ++t) {
+        const size_t i = (size_t)mem[t];
+        const int64_t u[2] = {w->U[2 * i] - w->X0[2 * i], w->U[2 * i + 1] - w->X0[2 * i + 1]};
+        b.su[0] += u[0];
+        b.su[1] += u[1];
+        if (!rot) continue;
+        const int64_t d0[2] = {w->D0[2 * i], w->D0[2 * i + 1]};
+        const int64_t d[2] = {d0[0] + u[0] - ur[0], d0[1] + u[1] - ur[1]};
+        b.C += d0[0] * d[0] + d0[1] * d[1];
+        b.S += d0[0] * d[1] - d0[1] * d[0];
+      }
+      if (rot) b.is |= KMC_BD_IS_ROT;
+    }
+    rows->push_back(b);
+  }
+  return KMC_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int kmc_host_bd_begin(const kmc_params* p, const kmc_state_view* v, const kmc_bd_config* cfg, const kmc_bd_view* view,
+                      kmc_bd_out* acc) {
+  if (!p || !v || !v->ra || !v->rb || !v->a_int || !v->b_int || !cfg || !bd_view_ok(view) || !acc) {
+    g_host_err = "bd: params, state, the configuration, the view's eight arrays and acc are needed";
+    return KMC_ERR_ARG;
+  }
+  kmc_bd_config c = *cfg;
+  int64_t J, F, BX, BY;
+  const char* bad = kmcb::check(c.every, c.max_size, p->box_x, p->box_y, &c.max_jump, &c.max_disp, &J, &F, &BX, &BY);
+  if (bad) {
+    g_host_err = bad;
+    return KMC_ERR_ARG;
+  }
+  const size_t N = (size_t)p->n_a + (size_t)p->n_b;
+  std::vector<int32_t> shift(2 * N + 1);
+  kmc_geom geom;
+  const int rc = kmc_host_cluster_geometry(p, v, view->label, shift.data(), view->bits, 2, nullptr, &geom);
+  if (rc != KMC_OK) return rc;
+  int64_t n_bodies = 0;
+  for (size_t i = 0; i < N; ++i) {
+    int64_t X[2];
+    int32_t l[3];
+    lag_host_cur(p, v, (int)i, X, l);
+    for (int k = 0; k < 2; ++k) view->prev[2 * i + k] = view->U[2 * i + k] = view->X0[2 * i + k] = X[k];
+    for (int k = 0; k < 3; ++k) view->links[(size_t)k * N + i] = l[k];
+    view->flags[i] = 0;
+    n_bodies += view->label[i] == (int32_t)i + 1;
+  }
+  for (size_t i = 0; i < N; ++i) {
+    const size_t r = (size_t)view->label[i] - 1;
+    view->D0[2 * i] = view->X0[2 * i] + (int64_t)shift[i] * BX - view->X0[2 * r];
+    view->D0[2 * i + 1] = view->X0[2 * i + 1] + (int64_t)shift[N + i] * BY - view->X0[2 * r + 1];
+  }
+  // a body is WIDE by any of its members: the bit goes to all of them
+  std::vector<uint8_t> wide(N, 0);
+  for (size_t i = 0; i < N; ++i)
+    if (kmcb::wide(view->D0[2 * i], view->D0[2 * i + 1])) wide[(size_t)view->label[i] - 1] = 1;
+  for (size_t i = 0; i < N; ++i)
+    if (wide[(size_t)view->label[i] - 1]) view->bits[i] |= KMC_BD_WIDE;
+  std::memset(acc, 0, sizeof *acc);
+  acc->cfg = c;
+  acc->J = J;
+  acc->F = F;
+  acc->BX = BX;
+  acc->BY = BY;
+  acc->origin_step = acc->last_step = v->step;
+  acc->n_bodies = n_bodies;
+  return KMC_OK;
+}
+
+int kmc_host_bd_update(const kmc_params* p, const kmc_state_view* v, const kmc_bd_view* view, kmc_bd_out* acc,
+                       kmc_bd_info* info) {
+  if (!p || !v || !v->ra || !v->rb || !v->a_int || !v->b_int || !bd_view_ok(view) || !acc) {
+    g_host_err = "bd: params, state, the view's eight arrays and acc are needed";
+    return KMC_ERR_ARG;
+  }
+  if (v->step != acc->last_step + acc->cfg.every) {
+    g_host_err = "bd: an update is due " + std::to_string(acc->cfg.every) + " steps after the last one";
+    return KMC_ERR_ARG;
+  }
+  const size_t N = (size_t)p->n_a + (size_t)p->n_b;
+  const int64_t B[2] = {acc->BX, acc->BY};
+  int64_t n_jumped = 0, n_changed = 0;
+  for (size_t i = 0; i < N; ++i) {
+    int64_t X[2];
+    int32_t l[3];
+    lag_host_cur(p, v, (int)i, X, l);
+    int f = 0;
+    for (int k = 0; k < 2; ++k) {
+      const int64_t d = kmcl::min_image(X[k] - view->prev[2 * i + k], B[k]);
+      view->U[2 * i + k] += d;
+      view->prev[2 * i + k] = X[k];
+      if (std::llabs(d) >= acc->J) f |= BD_JUMPED;
+    }
+    for (int k = 0; k < 3; ++k) {
+      int32_t* q = &view->links[(size_t)k * N + i];
+      if (*q != l[k]) f |= BD_CHANGED;
+      *q = l[k];
+    }
+    const int fresh = f & ~view->flags[i];
+    n_jumped += (fresh & BD_JUMPED) != 0;
+    n_changed += (fresh & BD_CHANGED) != 0;
+    view->flags[i] |= (uint8_t)f;
+  }
+  acc->last_step = v->step;
+  acc->n_updates += 1;
+  if (info) {
+    info->n_updates = acc->n_updates;
+    info->n_jumped = n_jumped;
+    info->n_changed = n_changed;
+  }
+  return KMC_OK;
+}
+
+int kmc_host_bd_sample(const kmc_params* p, const kmc_state_view* v, const kmc_bd_view* view, const kmc_bd_out* acc,
+                       kmc_bd_out* out, kmc_bd_cell* table) {
+  if (!p || !v || !v->a_int || !v->b_int || !bd_view_ok(view) || !acc || !out) {
+    g_host_err = "bd sample: params, state, the view's eight arrays, acc and out are needed";
+    return KMC_ERR_ARG;
+  }
+  if (v->step != acc->last_step) {
+    g_host_err = "bd sample: the state has moved on since the last update (an update is due first)";
+    return KMC_ERR_ARG;
+  }
+  const kmc_bd_out a = *acc;  // (out may be acc itself)
+  *out = a;
+  if (!table) return KMC_OK;
+  std::vector<kmc_bd_body> rows;
+  const int rc = bd_host_rows(p, v, view, &a, &rows);
+  if (rc != KMC_OK) return rc;
+  const int ms = a.cfg.max_size;
+  std::memset(table, 0, sizeof(kmc_bd_cell) * 2 * ((size_t)ms + 1));
+  for (const kmc_bd_body& b : rows) {
+    const int n = b.n_r + b.n_l;
+    kmc_bd_cell* c = &table[(size_t)(b.n_l > 0) * (ms + 1) + std::min(n, ms)];
+    c->n_bodies += 1;
+    c->sum_size += n;
+    (b.status == KMC_BD_INTACT ? c->n_intact : b.status == KMC_BD_GROWN ? c->n_grown : c->n_broken) += 1;
+    if (b.is & KMC_BD_IS_PRISTINE) c->n_pristine += 1;
+    if (!(b.is & KMC_BD_IS_VALID)) continue;
+    c->n_valid += 1;
+    lag_add(&c->m2, (__int128)kmcb::trans_term(b.su[0], b.su[1]));
+    if (!(b.is & KMC_BD_IS_ROT)) {
+      if (n >= 2) c->n_rot_skipped += 1;
+      continue;
+    }
+    if (b.C == 0 && b.S == 0) {
+      c->n_rot_null += 1;
+      continue;
+    }
+    int64_t c1, c2, ph;
+    kmcb::rot_terms(b.C, b.S, &c1, &c2, &ph);
+    c->n_rot += 1;
+    c->c1 += c1;
+    c->c2 += c2;
+    lag_add(&c->phi2, (__int128)(ph * ph));
+  }
+  return KMC_OK;
+}
+
+int kmc_host_bd_bodies(const kmc_params* p, const kmc_state_view* v, const kmc_bd_view* view, const kmc_bd_out* acc,
+                       int32_t min_size, int64_t cap, kmc_bd_body* rows, int64_t* n) {
+  if (!p || !v || !v->a_int || !v->b_int || !bd_view_ok(view) || !acc || !n || min_size < 1 || cap < 0 ||
+      (cap > 0 && !rows)) {
+    g_host_err = "bd bodies: params, state, the view, acc and n are needed, min_size >= 1, cap >= 0, rows for cap > 0";
+    return KMC_ERR_ARG;
+  }
+  if (v->step != acc->last_step) {
+    g_host_err = "bd bodies: the state has moved on since the last update (an update is due first)";
+    return KMC_ERR_ARG;
+  }
+  std::vector<kmc_bd_body> all;
+  const int rc = bd_host_rows(p, v, view, acc, &all);
+  if (rc != KMC_OK) return rc;
+  *n = 0;
+  for (const kmc_bd_body& b : all)
+    if (b.n_r + b.n_l >= min_size) {
+      if (*n < cap) rows[*n] = b;
+      *n += 1;
+    }
+  if (*n > cap) {
+    g_host_err = "bd bodies: " + std::to_string(*n) + " bodies qualify, cap is " + std::to_string(cap);
+    return KMC_ERR_CAPACITY;
   }
   return KMC_OK;
 }

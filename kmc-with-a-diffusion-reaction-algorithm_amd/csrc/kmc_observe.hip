@@ -1,6 +1,6 @@
 // kmc_observe.hip — the host side of the read-only layers over the committed
-// state (DESIGN.md §10-§20): their C-ABI calls, one section a layer, over the
-// kernels and the state structs of kmc_analysis.hip ... kmc_pairdyn.hip.  Nothing
+// state (DESIGN.md §10-§21): their C-ABI calls, one section a layer, over the
+// kernels and the state structs of kmc_analysis.hip ... kmc_bodydyn.hip.  Nothing
 // here writes a buffer a step reads, so the trajectory, the step counter and
 // clusters_valid stay as they are.
 //
@@ -1722,6 +1722,336 @@ int kmc_pd_arrays(kmc_sim* s, int64_t* U, int64_t* X0, uint8_t* flags) {
 
 int kmc_pd_end(kmc_sim* s) {
   return s ? rec_end(s, s->pd) : KMC_ERR_ARG;
+}
+
+// ---------------------------------------------------------------- body dynamics
+// kmc_bodydyn.hip: a recorder with one origin, on the pair dynamics' life cycle
+// (begin allocates, end frees).  The begin runs the geometry layer's unwrap
+// once and sorts the members by body; the update advances the per-protein
+// state; the sample labels the current components and runs the segmented
+// reduction and the finish into a table it zeroed.
+
+static_assert(KMC_BD_MAX_SIZE == BD_MAX_SIZE && KMC_BD_ROT_MAX == BD_ROT_MAX && KMC_BD_JUMPED == BD_JUMPED &&
+                  KMC_BD_CHANGED == BD_CHANGED && KMC_BD_WIDE == BD_WIDE && KMC_BD_INTACT == BD_INTACT &&
+                  KMC_BD_GROWN == BD_GROWN && KMC_BD_BROKEN == BD_BROKEN &&
+                  KMC_BD_IS_PRISTINE == BD_IS_PRISTINE && KMC_BD_IS_VALID == BD_IS_VALID &&
+                  KMC_BD_IS_ROT == BD_IS_ROT,
+              "kmc.h and kmc_bodydyn.h agree");
+static_assert(sizeof(kmc_bd_cell) == sizeof(bd_u64) * BD_CELL_WORDS &&
+                  offsetof(kmc_bd_cell, n_intact) == 8 * BD_W_INTACT &&
+                  offsetof(kmc_bd_cell, n_broken) == 8 * BD_W_BROKEN && offsetof(kmc_bd_cell, c1) == 8 * BD_W_C1 &&
+                  offsetof(kmc_bd_cell, m2) == 8 * BD_W_M2 && offsetof(kmc_bd_cell, phi2) == 8 * BD_W_PHI2,
+              "kmc_bd_cell is the layout k_bd_finish adds into");
+static_assert(sizeof(kmc_bd_body) == 64, "kmc_bd_body layout");
+
+static const char* const BD_OFF = "bd: not begun (kmc_bd_begin; a new state drops the recorder)";
+
+int kmc_bd_begin(kmc_sim* s, const kmc_bd_config* cfg) {
+  if (!s) return KMC_ERR_ARG;
+  if (!cfg) return fail(s, KMC_ERR_ARG, "bd: the configuration is needed");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  kmc_bd_config c = *cfg;
+  int64_t J, F, BX, BY;
+  const char* bad = kmcb::check(c.every, c.max_size, s->K.box_x, s->K.box_y, &c.max_jump, &c.max_disp, &J, &F, &BX, &BY);
+  if (bad) return fail(s, KMC_ERR_ARG, bad);
+  // a recorder that was on ends here, whatever becomes of this call
+  rc = rec_end(s, s->bd);
+  if (rc != KMC_OK) return rc;
+  // debug: the segmented reduction takes shorter spans of the member list
+  s->bd.span = (int)int_getenv("KMC_DEBUG_BD_SPAN", BD_SPAN, 1, BD_SPAN);
+  const size_t N = (size_t)s->K.N;
+  Scratch& g = s->bd.scratch;
+  Bd& D = s->bd.dev;
+  rc = KMC_OK;
+  rc |= salloc(s, g, &D.prev, N);
+  rc |= salloc(s, g, &D.U, N);
+  rc |= salloc(s, g, &D.X0, N);
+  rc |= salloc(s, g, &D.D0, N);
+  rc |= salloc(s, g, &D.links, 3 * N);
+  rc |= salloc(s, g, &D.flags, N);
+  rc |= salloc(s, g, &D.label, N);
+  rc |= salloc(s, g, &D.list, N);
+  rc |= salloc(s, g, &D.rank, N);
+  rc |= salloc(s, g, &D.ccnt, N + 1);
+  rc |= salloc(s, g, &D.start, N + 1);
+  rc |= salloc(s, g, &D.part, (N + 1 + SCAN_TILE - 1) / SCAN_TILE);
+  rc |= salloc(s, g, &D.sd0, 2 * N);
+  rc |= salloc(s, g, &D.sd2, N);
+  rc |= salloc(s, g, &D.cnt, N);
+  rc |= salloc(s, g, &D.bits, N);
+  rc |= salloc(s, g, &D.acc, N * BD_ACC);
+  rc |= salloc(s, g, &D.table, (size_t)2 * (BD_MAX_SIZE + 1) * BD_CELL_WORDS);
+  rc |= salloc(s, g, &D.out, BD_OUT);
+  if (rc != KMC_OK) {
+    scratch_drop(s, s->bd);
+    return fail(s, KMC_ERR_HIP, "bd: allocation failed (189 bytes per protein)");
+  }
+  rc = an_begin(s);
+  if (rc == KMC_OK) rc = geo_run(s);
+  if (rc != KMC_OK) {
+    scratch_drop(s, s->bd);
+    return rc;
+  }
+  if (N > 0) {
+    const unsigned gr = (unsigned)((N + BD_T - 1) / BD_T);
+    // (ccnt, the bodies' sums and bits, acc and out are zero: salloc)
+    k_bd_begin<<<gr, BD_T, 0, s->stream>>>(s->K, s->d, D, s->geo.label, s->geo.off, s->geo.span, s->geo.cnt, BX, BY);
+    bins_scan(s, D.ccnt, D.start, (int)N + 1, D.part);
+    k_bd_scatter<<<gr, BD_T, 0, s->stream>>>((int)N, D);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  GeoOut o;
+  if (rc == KMC_OK) rc = geo_result(s, &o);
+  bd_u64 out[BD_OUT] = {0, 0, 0, 0};
+  if (rc == KMC_OK && hipMemcpy(out, D.out, sizeof out, hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(s, KMC_ERR_HIP, "bd: the begin's counts could not be read");
+  if (rc != KMC_OK) {
+    scratch_drop(s, s->bd);
+    return rc;
+  }
+  s->bd.cfg = c;
+  s->bd.J = J;
+  s->bd.F = F;
+  s->bd.BX = BX;
+  s->bd.BY = BY;
+  s->bd.n_bodies = (int64_t)out[3];
+  s->bd.rec = Recorder{true, s->step_done, s->step_done, 0};
+  return KMC_OK;
+}
+
+int kmc_bd_update(kmc_sim* s, kmc_bd_info* info) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = rec_check(s, s->bd.rec, BD_OFF);
+  if (rc != KMC_OK) return rc;
+  BdState& g = s->bd;
+  if (s->step_done != g.rec.last + g.cfg.every)
+    return fail(s, KMC_ERR_ARG, "bd: an update is due " + std::to_string(g.cfg.every) + " steps after the last one");
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  const int N = s->K.N, nblk = (N + BD_T - 1) / BD_T;
+  HIPCHK(s, hipMemsetAsync(g.dev.out, 0, sizeof(bd_u64) * 2, s->stream));
+  if (nblk > 0)
+    k_bd_update<<<(unsigned)std::min(nblk, AN_WG_MAX), BD_T, 0, s->stream>>>(s->K, s->d, g.dev, g.BX, g.BY, g.J, nblk);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) {
+    g.rec.on = false;  // the per-protein state may be half advanced
+    return rc;
+  }
+  g.rec.last = s->step_done;
+  g.rec.updates += 1;
+  if (info) {
+    bd_u64 n[2] = {0, 0};
+    HIPCHK(s, hipMemcpy(n, g.dev.out, sizeof n, hipMemcpyDeviceToHost));
+    info->n_updates = g.rec.updates;
+    info->n_jumped = (int64_t)n[0];
+    info->n_changed = (int64_t)n[1];
+  }
+  return KMC_OK;
+}
+
+// the current components and the segmented reduction over the member list,
+// left on the device for k_bd_finish or k_bd_rows; the stream is not waited
+// for.  timed: an event after either part (kmc_bd_sample_ms).
+static int bd_reduce(kmc_sim* s, bool timed) {
+  const int rc = an_components(s);
+  if (rc != KMC_OK) return rc;
+  if (timed) {
+    for (auto& e : s->bd_ev)
+      if (!e) HIPCHK(s, hipEventCreate(&e));
+    HIPCHK(s, hipEventRecord(s->bd_ev[0], s->stream));
+  }
+  const BdState& g = s->bd;
+  const int N = s->K.N, nspans = (N + g.span - 1) / g.span, nwg = (nspans + BD_T / 64 - 1) / (BD_T / 64);
+  if (nwg > 0)
+    k_bd_reduce<<<(unsigned)std::min(nwg, AN_WG_MAX), BD_T, 0, s->stream>>>(g.dev, s->an.label, N, g.span, g.F, nspans);
+  if (timed) HIPCHK(s, hipEventRecord(s->bd_ev[1], s->stream));
+  return KMC_OK;
+}
+
+static int bd_ready(kmc_sim* s, const char* what) {
+  const int rc = rec_check(s, s->bd.rec, BD_OFF);
+  if (rc != KMC_OK) return rc;
+  if (s->step_done != s->bd.rec.last)
+    return fail(s, KMC_ERR_ARG, std::string(what) + ": the state has moved on since the last update (an update is due first)");
+  return KMC_OK;
+}
+
+static int bd_components_ok(kmc_sim* s) {
+  AnOut o;
+  HIPCHK(s, hipMemcpy(&o, s->an.out, sizeof o, hipMemcpyDeviceToHost));
+  if (o.err) return fail(s, KMC_ERR_STATE, "analysis: a bond link leaves the state or the link chains do not end");
+  return KMC_OK;
+}
+
+int kmc_bd_sample(kmc_sim* s, kmc_bd_out* out, kmc_bd_cell* table) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "bd sample: out is needed");
+  int rc = bd_ready(s, "bd sample");
+  if (rc != KMC_OK) return rc;
+  BdState& g = s->bd;
+  const int N = s->K.N, ms = g.cfg.max_size;
+  const size_t nword = (size_t)2 * (ms + 1) * BD_CELL_WORDS;
+  if (table) {
+    rc = an_begin(s);
+    if (rc != KMC_OK) return rc;
+    HIPCHK(s, hipMemsetAsync(g.dev.table, 0, sizeof(bd_u64) * nword, s->stream));
+    if (N > 0) {
+      rc = bd_reduce(s, true);
+      if (rc != KMC_OK) return rc;
+      const int nblk = (N + BD_T - 1) / BD_T;
+      // (at most 2 x 256 cells of 128 bytes: the 64 KiB every launch may ask for)
+      k_bd_finish<<<(unsigned)std::min(nblk, AN_WG_MAX), BD_T, sizeof(bd_u64) * nword, s->stream>>>(g.dev, s->an.cnt, N, ms,
+                                                                                                   g.span);
+    }
+    HIPCHK(s, hipGetLastError());
+    rc = an_end(s);
+    if (rc == KMC_OK && N > 0) rc = bd_components_ok(s);
+    if (rc != KMC_OK) {
+      g.rec.on = false;  // the accumulators may be half served
+      return rc;
+    }
+    float ms[3] = {0.0f, 0.0f, 0.0f};
+    if (N > 0) {
+      HIPCHK(s, hipEventElapsedTime(&ms[0], s->an_ev[0], s->bd_ev[0]));
+      HIPCHK(s, hipEventElapsedTime(&ms[1], s->bd_ev[0], s->bd_ev[1]));
+      HIPCHK(s, hipEventElapsedTime(&ms[2], s->bd_ev[1], s->an_ev[1]));
+    }
+    for (int k = 0; k < 3; ++k) s->bd_ms[k] = ms[k];
+  }
+  std::memset(out, 0, sizeof *out);
+  out->cfg = g.cfg;
+  out->J = g.J;
+  out->F = g.F;
+  out->BX = g.BX;
+  out->BY = g.BY;
+  out->origin_step = g.rec.origin;
+  out->last_step = g.rec.last;
+  out->n_updates = g.rec.updates;
+  out->n_bodies = g.n_bodies;
+  if (table) HIPCHK(s, hipMemcpy(table, g.dev.table, sizeof(bd_u64) * nword, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_bd_sample_ms(const kmc_sim* s, double ms[3]) {
+  if (!s || !ms) return KMC_ERR_ARG;
+  for (int k = 0; k < 3; ++k) ms[k] = s->bd_ms[k];
+  return KMC_OK;
+}
+
+int kmc_bd_bodies(kmc_sim* s, int32_t min_size, int64_t cap, kmc_bd_body* rows, int64_t* n) {
+  if (!s) return KMC_ERR_ARG;
+  if (!n || min_size < 1 || cap < 0 || (cap > 0 && !rows))
+    return fail(s, KMC_ERR_ARG, "bd bodies: n is needed, min_size >= 1, cap >= 0, rows for cap > 0");
+  int rc = bd_ready(s, "bd bodies");
+  if (rc != KMC_OK) return rc;
+  BdState& g = s->bd;
+  const int N = s->K.N;
+  // no more than N / min_size bodies can qualify: a larger cap needs no larger buffer
+  const size_t dcap = (size_t)std::min<int64_t>(cap, N / min_size);
+  if (dcap > g.rows_cap) {
+    HIPCHK(s, hipStreamSynchronize(s->stream));
+    if (g.rows) {
+      g.scratch.ptrs.erase(std::find(g.scratch.ptrs.begin(), g.scratch.ptrs.end(), (void*)g.rows));
+      dfree(s, g.rows);
+    }
+    g.rows_cap = 0;
+    if (salloc(s, g.scratch, &g.rows, dcap) != KMC_OK) return fail(s, KMC_ERR_HIP, "bd bodies: scratch allocation failed");
+    g.rows_cap = dcap;
+  }
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemsetAsync(g.dev.out + 2, 0, sizeof(bd_u64), s->stream));
+  if (N > 0) {
+    rc = bd_reduce(s, false);
+    if (rc != KMC_OK) return rc;
+    k_bd_rows<<<(unsigned)((N + BD_T - 1) / BD_T), BD_T, 0, s->stream>>>(g.dev, s->an.cnt, N, g.span, min_size,
+                                                                         (long long)dcap, g.rows);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc == KMC_OK && N > 0) rc = bd_components_ok(s);
+  if (rc != KMC_OK) {
+    g.rec.on = false;
+    return rc;
+  }
+  bd_u64 cnt = 0;
+  HIPCHK(s, hipMemcpy(&cnt, g.dev.out + 2, sizeof cnt, hipMemcpyDeviceToHost));
+  *n = (int64_t)cnt;
+  if (*n > cap)
+    return fail(s, KMC_ERR_CAPACITY, "bd bodies: " + std::to_string(*n) + " bodies qualify, cap is " + std::to_string(cap));
+  if (*n) {
+    HIPCHK(s, hipMemcpy(rows, g.rows, sizeof(kmc_bd_body) * (size_t)*n, hipMemcpyDeviceToHost));
+    std::sort(rows, rows + *n, [](const kmc_bd_body& a, const kmc_bd_body& b) { return a.label < b.label; });
+  }
+  return KMC_OK;
+}
+
+int kmc_bd_arrays(kmc_sim* s, int64_t* U, int64_t* X0, uint8_t* flags, int32_t* label, int64_t* D0) {
+  if (!s) return KMC_ERR_ARG;
+  const int rc = rec_check(s, s->bd.rec, BD_OFF);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  const Bd& D = s->bd.dev;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  if (U && N) HIPCHK(s, hipMemcpy(U, D.U, sizeof(longlong2) * N, hipMemcpyDeviceToHost));
+  if (X0 && N) HIPCHK(s, hipMemcpy(X0, D.X0, sizeof(longlong2) * N, hipMemcpyDeviceToHost));
+  if (flags && N) HIPCHK(s, hipMemcpy(flags, D.flags, N, hipMemcpyDeviceToHost));
+  if (D0 && N) HIPCHK(s, hipMemcpy(D0, D.D0, sizeof(longlong2) * N, hipMemcpyDeviceToHost));
+  if (label && N) {
+    HIPCHK(s, hipMemcpy(label, D.label, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N; ++i) label[i] += 1;
+  }
+  return KMC_OK;
+}
+
+int kmc_bd_get(kmc_sim* s, const kmc_bd_view* v) {
+  if (!s) return KMC_ERR_ARG;
+  if (!v || !v->prev || !v->U || !v->links || !v->flags)
+    return fail(s, KMC_ERR_ARG, "bd get: the view with prev, U, links and flags is needed");
+  int rc = kmc_bd_arrays(s, v->U, v->X0, v->flags, v->label, v->D0);
+  if (rc != KMC_OK) return rc;
+  const size_t N = (size_t)s->K.N;
+  const Bd& D = s->bd.dev;
+  if (N) HIPCHK(s, hipMemcpy(v->prev, D.prev, sizeof(longlong2) * N, hipMemcpyDeviceToHost));
+  if (N) HIPCHK(s, hipMemcpy(v->links, D.links, sizeof(int32_t) * 3 * N, hipMemcpyDeviceToHost));
+  if (v->bits && N) {
+    std::vector<uint32_t> b(N);
+    std::vector<int32_t> lab(N);
+    HIPCHK(s, hipMemcpy(b.data(), D.bits, sizeof(uint32_t) * N, hipMemcpyDeviceToHost));
+    HIPCHK(s, hipMemcpy(lab.data(), D.label, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < N; ++i) v->bits[i] = (uint8_t)b[(size_t)lab[i]];
+  }
+  return KMC_OK;
+}
+
+int kmc_bd_put(kmc_sim* s, const kmc_bd_view* v, int64_t last_step) {
+  if (!s) return KMC_ERR_ARG;
+  if (!v || !v->prev || !v->U || !v->links || !v->flags)
+    return fail(s, KMC_ERR_ARG, "bd put: the view with prev, U, links and flags is needed");
+  const int rc = rec_check(s, s->bd.rec, BD_OFF);
+  if (rc != KMC_OK) return rc;
+  if (last_step > s->step_done) return fail(s, KMC_ERR_ARG, "bd put: last_step lies after the current step");
+  const size_t N = (size_t)s->K.N;
+  for (size_t i = 0; i < N; ++i)
+    if (v->flags[i] & ~(BD_JUMPED | BD_CHANGED))
+      return fail(s, KMC_ERR_ARG, "bd put: the flags of protein " + std::to_string(i + 1) + " hold an unknown bit");
+  const Bd& D = s->bd.dev;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  if (N) {
+    HIPCHK(s, hipMemcpy(D.prev, v->prev, sizeof(longlong2) * N, hipMemcpyHostToDevice));
+    HIPCHK(s, hipMemcpy(D.U, v->U, sizeof(longlong2) * N, hipMemcpyHostToDevice));
+    HIPCHK(s, hipMemcpy(D.links, v->links, sizeof(int32_t) * 3 * N, hipMemcpyHostToDevice));
+    HIPCHK(s, hipMemcpy(D.flags, v->flags, N, hipMemcpyHostToDevice));
+  }
+  s->bd.rec.last = last_step;
+  return KMC_OK;
+}
+
+int kmc_bd_end(kmc_sim* s) {
+  return s ? rec_end(s, s->bd) : KMC_ERR_ARG;
 }
 
 // ---------------------------------------------------------------- orientation

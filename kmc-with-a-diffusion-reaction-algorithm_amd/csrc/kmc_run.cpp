@@ -100,6 +100,15 @@
 //                              gd step origin kind k count             (kind = 2 species(i) + species(j))
 //                              gs step origin species k count
 //                              cu step origin kind k n_pairs n_valid dot sq   (kind: 0 AA, 1 AB, 2 BB)
+//           [--bd EVERY SAMPLE_EVERY MAX_SIZE FILE]  body dynamics (kmc_bd_*): the clusters of the state where the
+//                            process starts or resumes are the bodies (not checkpointed: a new origin, every
+//                            line carries it); updates every EVERY steps as --lag's, and after every
+//                            SAMPLE_EVERY-th update FILE gets
+//                              bd step origin n_updates every max_size J F BX BY n_bodies
+//                            and per non-empty cell (hl: holds a ligand; k = min(size, max_size); the 128-bit
+//                            sums in decimal)
+//                              body step origin hl k n_bodies sum_size n_pristine n_intact n_grown n_broken
+//                                   n_valid n_rot n_rot_null n_rot_skipped c1 c2 m2 phi2
 //           [--pose NZ NC FILE]  ligand pose census (kmc_ligand_pose) of every output step:
 //                              pose step nz nc n_bad chi_pos[0..3] chi_neg[0..3]
 //                              bin step k zbin tiltbin count          (non-zero bins)
@@ -160,6 +169,34 @@ int pd_append(kmc_sim* s, const char* path) {
   return KMC_OK;
 }
 
+// --bd: one sample's non-empty cells appended to path, every line with the current and the origin step
+int bd_append(kmc_sim* s, const char* path) {
+  kmc_bd_out k;
+  int rc = kmc_bd_sample(s, &k, nullptr);
+  if (rc) return rc;
+  const int ms = k.cfg.max_size;
+  std::vector<kmc_bd_cell> table((size_t)2 * (ms + 1));
+  rc = kmc_bd_sample(s, &k, table.data());
+  if (rc) return rc;
+  FILE* f = fopen(path, "ab");
+  if (!f) return KMC_ERR_IO;
+  const long long step = (long long)k.last_step, o = (long long)k.origin_step;
+  fprintf(f, "bd %lld %lld %lld %d %d %lld %lld %lld %lld %lld\n", step, o, (long long)k.n_updates, k.cfg.every, ms,
+          (long long)k.J, (long long)k.F, (long long)k.BX, (long long)k.BY, (long long)k.n_bodies);
+  for (int hl = 0; hl < 2; ++hl)
+    for (int b = 0; b <= ms; ++b) {
+      const kmc_bd_cell& w = table[(size_t)hl * (ms + 1) + b];
+      if (!w.n_bodies) continue;
+      fprintf(f, "body %lld %lld %d %d %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %s %s\n", step, o, hl,
+              b, (long long)w.n_bodies, (long long)w.sum_size, (long long)w.n_pristine, (long long)w.n_intact,
+              (long long)w.n_grown, (long long)w.n_broken, (long long)w.n_valid, (long long)w.n_rot,
+              (long long)w.n_rot_null, (long long)w.n_rot_skipped, (long long)w.c1, (long long)w.c2,
+              dec128(w.m2).c_str(), dec128(w.phi2).c_str());
+    }
+  fclose(f);
+  return KMC_OK;
+}
+
 bool set_field(kmc_params* p, const std::string& k, const std::string& v) {
   double d = strtod(v.c_str(), nullptr);
 #define F(name)            \
@@ -215,6 +252,9 @@ int main(int argc, char** argv) {
   std::string pd_path;
   kmc_pd_config pd_cfg = {0, 0, 0.0, 0.0, 0.0};
   int pd_sample_every = 0;
+  std::string bd_path;
+  kmc_bd_config bd_cfg = {0, 0, 0.0, 0.0};
+  int bd_sample_every = 0;
   int pose_nz = 0, pose_nc = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -337,6 +377,16 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--bd") {
+      bd_cfg.every = atoi(next().c_str());
+      bd_sample_every = atoi(next().c_str());
+      bd_cfg.max_size = atoi(next().c_str());
+      bd_path = next();
+      if (bd_cfg.every < 1 || bd_sample_every < 1 || bd_cfg.max_size < 2 || bd_cfg.max_size > KMC_BD_MAX_SIZE) {
+        fprintf(stderr, "kmc_run: bad --bd %d %d %d\n", bd_cfg.every, bd_sample_every, bd_cfg.max_size);
+        return 2;
+      }
+    }
     else if (a == "--rot") {
       rot_cfg.every = atoi(next().c_str());
       rot_cfg.levels = atoi(next().c_str());
@@ -402,6 +452,7 @@ int main(int argc, char** argv) {
     if (!lag_path.empty()) truncate(lag_path.c_str());
     if (!rot_path.empty()) truncate(rot_path.c_str());
     if (!pd_path.empty()) truncate(pd_path.c_str());
+    if (!bd_path.empty()) truncate(bd_path.c_str());
     if (!pose_path.empty()) truncate(pose_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
@@ -449,6 +500,11 @@ int main(int argc, char** argv) {
     rc = kmc_pd_begin(s, &pd_cfg);
     if (rc) return die(s, rc, "pd begin");
   }
+  int64_t bd_left = bd_cfg.every;
+  if (!bd_path.empty()) {
+    rc = kmc_bd_begin(s, &bd_cfg);
+    if (rc) return die(s, rc, "bd begin");
+  }
   int64_t step = kmc_current_step(s);
   while (step < p.simu_step) {
     int64_t next_out = (step / p.out_interval + 1) * p.out_interval;
@@ -456,7 +512,7 @@ int main(int argc, char** argv) {
     int64_t n = end - step;
     obs.resize((size_t)n);
     if (dyn_path.empty() && kin_path.empty() && cf_path.empty() && lag_path.empty() && rot_path.empty() &&
-        pd_path.empty()) {
+        pd_path.empty() && bd_path.empty()) {
       rc = kmc_step(s, n, obs.data());
       if (rc) return die(s, rc, "kmc_step");
     } else {
@@ -472,6 +528,7 @@ int main(int argc, char** argv) {
         if (!lag_path.empty() && lag_left < m) m = lag_left;
         if (!rot_path.empty() && rot_left < m) m = rot_left;
         if (!pd_path.empty() && pd_left < m) m = pd_left;
+        if (!bd_path.empty() && bd_left < m) m = bd_left;
         rc = kmc_step(s, m, obs.data() + done);
         if (rc) return die(s, rc, "kmc_step");
         done += m;
@@ -481,6 +538,7 @@ int main(int argc, char** argv) {
         lag_left -= m;
         rot_left -= m;
         pd_left -= m;
+        bd_left -= m;
         if (!dyn_path.empty() && (dyn_left == 0 || done == n)) {
           rc = kmc_track_update(s, nullptr);
           if (rc) return die(s, rc, "track update");
@@ -514,6 +572,16 @@ int main(int argc, char** argv) {
           if (info.n_updates % pd_sample_every == 0) {
             rc = pd_append(s, pd_path.c_str());
             if (rc) return die(s, rc, "pd sample");
+          }
+        }
+        if (!bd_path.empty() && bd_left == 0) {
+          kmc_bd_info info;
+          rc = kmc_bd_update(s, &info);
+          if (rc) return die(s, rc, "bd update");
+          bd_left = bd_cfg.every;
+          if (info.n_updates % bd_sample_every == 0) {
+            rc = bd_append(s, bd_path.c_str());
+            if (rc) return die(s, rc, "bd sample");
           }
         }
       }

@@ -163,6 +163,21 @@ def load_library(path: Optional[str] = None):
     L.kmc_host_pd_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.PdView), P(capi.PdOut), P(capi.PdInfo)]
     L.kmc_host_pd_sample.argtypes = [P(capi.Params), P(capi.PdView), P(capi.PdOut), P(capi.PdOut), C.c_void_p,
                                      C.c_void_p, C.c_void_p]
+    L.kmc_bd_begin.argtypes = [C.c_void_p, P(capi.BdConfig)]
+    L.kmc_bd_update.argtypes = [C.c_void_p, P(capi.BdInfo)]
+    L.kmc_bd_sample.argtypes = [C.c_void_p, P(capi.BdOut), C.c_void_p]
+    L.kmc_bd_sample_ms.argtypes = [C.c_void_p, C.c_void_p]
+    L.kmc_bd_bodies.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, P(C.c_int64)]
+    L.kmc_bd_arrays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kmc_bd_get.argtypes = [C.c_void_p, P(capi.BdView)]
+    L.kmc_bd_put.argtypes = [C.c_void_p, P(capi.BdView), C.c_int64]
+    L.kmc_bd_end.argtypes = [C.c_void_p]
+    L.kmc_host_bd_begin.argtypes = [P(capi.Params), P(capi.StateView), P(capi.BdConfig), P(capi.BdView), P(capi.BdOut)]
+    L.kmc_host_bd_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.BdView), P(capi.BdOut), P(capi.BdInfo)]
+    L.kmc_host_bd_sample.argtypes = [P(capi.Params), P(capi.StateView), P(capi.BdView), P(capi.BdOut), P(capi.BdOut),
+                                     C.c_void_p]
+    L.kmc_host_bd_bodies.argtypes = [P(capi.Params), P(capi.StateView), P(capi.BdView), P(capi.BdOut), C.c_int32,
+                                     C.c_int64, C.c_void_p, P(C.c_int64)]
     L.kmc_host_lag_begin.argtypes = [P(capi.Params), P(capi.StateView), P(capi.LagConfig), P(capi.LagView),
                                      P(capi.LagOut)]
     L.kmc_host_lag_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.LagView), P(capi.LagOut),
@@ -509,6 +524,54 @@ class HostPd:
         return capi.PdSample(out, gd, gs, cu)
 
 
+def _bd_table(max_size: int) -> np.ndarray:
+    return np.zeros((2, max(2, min(int(max_size), capi.BD_MAX_SIZE)) + 1), dtype=capi.BD_CELL_DTYPE)
+
+
+class HostBd:
+    """Body dynamics on host states, sequentially (kmc_host_bd_*): Simulation.bd_*'s counterpart without a device.
+    The recorder begins at hs (update 0); update(hs) advances it to the state `every` steps later; sample(hs) and
+    bodies(hs) take the state of the last update again, for its components.  arrays (capi.BdArrays) holds the
+    per-protein state and may be edited between the calls."""
+
+    def __init__(self, params: capi.Params, hs: capi.HostState, config: capi.BdConfig):
+        self.params = params
+        self.arrays = capi.BdArrays(params.n_a + params.n_b)
+        self.acc = capi.BdOut()
+        v = hs.view()
+        _host_check(load_library().kmc_host_bd_begin(C.byref(params), C.byref(v), C.byref(config),
+                                                     C.byref(self.arrays.view()), C.byref(self.acc)))
+
+    def update(self, hs: capi.HostState) -> capi.BdInfo:
+        """Advance the recorder to hs (kmc_host_bd_update)."""
+        v = hs.view()
+        info = capi.BdInfo()
+        _host_check(load_library().kmc_host_bd_update(C.byref(self.params), C.byref(v), C.byref(self.arrays.view()),
+                                                      C.byref(self.acc), C.byref(info)))
+        return info
+
+    def sample(self, hs: capi.HostState) -> capi.BdSample:
+        """The table of hs, the state of the last update — kmc_host_bd_sample."""
+        v = hs.view()
+        out = capi.BdOut()
+        table = _bd_table(self.acc.cfg.max_size)
+        _host_check(load_library().kmc_host_bd_sample(C.byref(self.params), C.byref(v), C.byref(self.arrays.view()),
+                                                      C.byref(self.acc), C.byref(out), table.ctypes.data))
+        return capi.BdSample(out, table)
+
+    def bodies(self, hs: capi.HostState, min_size: int = 1, cap: Optional[int] = None):
+        """The bodies of at least min_size members, by label, as a record array (capi.BD_BODY_DTYPE, the fields of
+        capi.BdBody) — kmc_host_bd_bodies."""
+        v = hs.view()
+        cap = self.params.n_a + self.params.n_b if cap is None else int(cap)
+        rows = np.zeros(max(cap, 1), dtype=capi.BD_BODY_DTYPE)
+        n = C.c_int64(0)
+        _host_check(load_library().kmc_host_bd_bodies(C.byref(self.params), C.byref(v), C.byref(self.arrays.view()),
+                                                      C.byref(self.acc), int(min_size), cap, rows.ctypes.data,
+                                                      C.byref(n)))
+        return rows[:n.value].copy()
+
+
 class HostRot:
     """The orientation recorder on host states, sequentially (kmc_host_rot_*): Simulation.rot_*'s counterpart without
     a device.  The recorder begins at hs (update 0); update(hs) advances it to the state `every` steps later.
@@ -815,7 +878,7 @@ class Simulation:
 
     @property
     def analysis_ms(self) -> float:
-        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / lag_* / rot_* / pd_* / ligand_pose / unwrap /
+        """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / lag_* / rot_* / pd_* / bd_* / ligand_pose / unwrap /
         cluster_* / structure_factor / bond_order / bond_order_corr / network / rings call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
@@ -1070,6 +1133,85 @@ class Simulation:
             done += every
             if self.pd_update().n_updates % sample_every == 0:
                 samples.append(self.pd_sample())
+        return recs, samples
+
+    # ---- body dynamics since a begin: D(s), rotation and survival of clusters by size (kmc_bodydyn.hip)
+    def bd_begin(self, config: capi.BdConfig) -> None:
+        """Start the body dynamics at the current state (update 0; capi.bd_config builds the configuration): the
+        clusters of this state are the bodies.  It allocates 189 bytes per protein, freed by bd_end."""
+        self._check(load_library().kmc_bd_begin(self._h, C.byref(config)))
+
+    def bd_update(self) -> capi.BdInfo:
+        """Advance the unwrapped positions and the flags; legal exactly `every` steps after the last update."""
+        info = capi.BdInfo()
+        self._check(load_library().kmc_bd_update(self._h, C.byref(info)))
+        return info
+
+    def bd_sample(self) -> capi.BdSample:
+        """The table of the current state, which must be that of the last update — kmc_bd_sample; analysis.body_msd,
+        body_rotation and body_survival read it."""
+        out = capi.BdOut()
+        self._check(load_library().kmc_bd_sample(self._h, C.byref(out), None))
+        table = _bd_table(out.cfg.max_size)
+        self._check(load_library().kmc_bd_sample(self._h, C.byref(out), table.ctypes.data))
+        return capi.BdSample(out, table)
+
+    def bd_sample_ms(self):
+        """(components, reduce, finish): device milliseconds of the parts of the last bd_sample (kmc_bd_sample_ms)."""
+        ms = (C.c_double * 3)()
+        self._check(load_library().kmc_bd_sample_ms(self._h, ms))
+        return tuple(ms)
+
+    def bd_bodies(self, min_size: int = 1, cap: Optional[int] = None):
+        """The bodies of at least min_size members, by label, as a record array (capi.BD_BODY_DTYPE, the fields of
+        capi.BdBody) — kmc_bd_bodies."""
+        cap = self.params.n_a + self.params.n_b if cap is None else int(cap)
+        rows = np.zeros(max(cap, 1), dtype=capi.BD_BODY_DTYPE)
+        n = C.c_int64(0)
+        self._check(load_library().kmc_bd_bodies(self._h, int(min_size), cap, rows.ctypes.data, C.byref(n)))
+        return rows[:n.value].copy()
+
+    def bd_arrays(self):
+        """(U[N, 2], X0[N, 2] int64, flags[N] uint8, label[N] int32 1-based, D0[N, 2] int64) by reference index."""
+        n = self.params.n_a + self.params.n_b
+        U, X0, D0 = (np.zeros((n, 2), dtype=np.int64) for _ in range(3))
+        flags = np.zeros(n, dtype=np.uint8)
+        label = np.zeros(n, dtype=np.int32)
+        self._check(load_library().kmc_bd_arrays(self._h, U.ctypes.data, X0.ctypes.data, flags.ctypes.data,
+                                                 label.ctypes.data, D0.ctypes.data))
+        return U, X0, flags, label, D0
+
+    def bd_get(self) -> capi.BdArrays:
+        """The recorder's per-protein state and its static arrays as a capi.BdArrays (kmc_bd_get)."""
+        a = capi.BdArrays(self.params.n_a + self.params.n_b)
+        self._check(load_library().kmc_bd_get(self._h, C.byref(a.view())))
+        return a
+
+    def bd_put(self, arrays: capi.BdArrays, last_step: Optional[int] = None) -> None:
+        """Load prev, U, links and flags of `arrays` into the recorder, which was begun on the current state, and set
+        the step of its last update (default: the current step) — kmc_bd_put."""
+        step = self.current_step if last_step is None else int(last_step)
+        self._check(load_library().kmc_bd_put(self._h, C.byref(arrays.view()), step))
+
+    def bd_end(self) -> None:
+        self._check(load_library().kmc_bd_end(self._h))
+
+    def run_bodies(self, nsteps: int, sample_every: int):
+        """Advance nsteps steps, `every` of the begun recorder's configuration at a time, with a bd_update after each
+        piece and a bd_sample after every sample_every-th update (nsteps must be a multiple of every).  Returns
+        (records[nsteps], the list of capi.BdSample)."""
+        out = capi.BdOut()
+        self._check(load_library().kmc_bd_sample(self._h, C.byref(out), None))
+        every = int(out.cfg.every)
+        if nsteps < 0 or nsteps % every or sample_every < 1:
+            raise ValueError("run_bodies: nsteps >= 0, a multiple of the recorder's every; sample_every >= 1")
+        recs = np.zeros(nsteps, dtype=capi.OBS_DTYPE)
+        done, samples = 0, []
+        while done < nsteps:
+            self.step(every, recs[done:done + every])
+            done += every
+            if self.bd_update().n_updates % sample_every == 0:
+                samples.append(self.bd_sample())
         return recs, samples
 
     # ---- orientation: the rotational lag correlator and the ligands' poses (kmc_orient.hip; DESIGN.md §19)
