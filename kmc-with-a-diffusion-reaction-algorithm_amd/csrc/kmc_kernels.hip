@@ -1651,7 +1651,9 @@ __device__ __forceinline__ void wave_sync() {
 //  * step 4 (1691-1732): each ligand-free cis partner is snapped onto its
 //    unique ligand-bound partner.
 // Every value is computed by the same expressions as the one-lane version
-// (complex_align), so the result is bit-identical.  Requires csize <= 64 (CXL).
+// (complex_align), so the result is bit-identical.  Requires csize <= CXL (one
+// member per lane, CxLds arrays of CXL entries): k_complex_heavy's staged
+// branch is its only caller, larger complexes take complex_align itself.
 
 // one random_shuffle pass over res[0 .. size-2] (libstdc++, main.cpp:1285)
 // on the row held one member per lane

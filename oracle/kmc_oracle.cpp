@@ -159,6 +159,10 @@ struct Oracle {
   enum { EV_FREE_A, EV_DIMER, EV_FREE_B, EV_COMPLEX, EV_LAYDOWN, EV_MULTI, EV_REPEAT, EV_REJECT,
          EV_RL, EV_MONO, EV_CIS, EV_RLD, EV_MD, EV_CD, EV_SNAP_BOND, EV_SNAP_CIS, EV_N };
   int64_t ev[EV_N] = {0};
+  // the complexes' collision tests by member count (clamped to CX_SIZES - 1): rejected, accepted — what ev[]
+  // cannot tell (its reject count includes the free units)
+  enum { CX_SIZES = 128 };
+  int64_t cx_rejected[CX_SIZES] = {0}, cx_accepted[CX_SIZES] = {0};
   // decomposed trajectory (oracle_dd_*; the engine's kmc_dd_* contract): the
   // window's global indices, the proteins this slab owns (1-based), the
   // counters' offsets of this slab's share, x at the window's set, and the
@@ -1010,6 +1014,8 @@ struct Oracle {
         coll = true;
         break;
       }
+    const size_t nres = res.size() < (size_t)CX_SIZES ? res.size() : (size_t)CX_SIZES - 1;
+    (coll ? cx_rejected : cx_accepted)[nres]++;
     if (coll) {
       ev[EV_REJECT]++;
       for (int m : res) revert(m);
@@ -1609,6 +1615,15 @@ int oracle_stats(oracle_t* h, int64_t* out, int n) {
   int m = n < (int)Oracle::EV_N ? n : (int)Oracle::EV_N;
   for (int i = 0; i < m; ++i) out[i] = h->o->ev[i];
   return (int)Oracle::EV_N;
+}
+// rejected[k], accepted[k]: complexes of k members (the last entry: that many or more) since the oracle was made
+int oracle_complex_outcomes(oracle_t* h, int64_t* rejected, int64_t* accepted, int n) {
+  int m = n < (int)Oracle::CX_SIZES ? n : (int)Oracle::CX_SIZES;
+  for (int i = 0; i < m; ++i) {
+    rejected[i] = h->o->cx_rejected[i];
+    accepted[i] = h->o->cx_accepted[i];
+  }
+  return (int)Oracle::CX_SIZES;
 }
 uint64_t oracle_draws(oracle_t* h) { return h->o->rng.ndraw; }
 int64_t oracle_current_step(oracle_t* h) { return h->o->step_done; }

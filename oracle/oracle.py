@@ -67,6 +67,7 @@ def lib():
         L.oracle_current_step.argtypes = [C.c_void_p]
         L.oracle_last_error.restype = C.c_char_p
         L.oracle_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.oracle_complex_outcomes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.oracle_get_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_set_stream.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
         L.oracle_stream_clock.restype = C.c_uint64
@@ -259,6 +260,12 @@ class Oracle:
         out = np.zeros(32, dtype=np.int64)
         n = lib().oracle_stats(self.h, out.ctypes.data_as(C.c_void_p), 32)
         return dict(zip(self.EVENTS, (int(x) for x in out[:n])))
+
+    def complex_outcomes(self):
+        """(rejected[128], accepted[128]): the complexes' collision tests by member count since the oracle was made."""
+        rej, acc = np.zeros(128, dtype=np.int64), np.zeros(128, dtype=np.int64)
+        lib().oracle_complex_outcomes(self.h, rej.ctypes.data, acc.ctypes.data, 128)
+        return rej, acc
 
     @property
     def draws(self) -> int:
