@@ -237,7 +237,7 @@ int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label
                     int64_t* hist, kmc_census* out);
 /* Device milliseconds of the last kmc_components / kmc_oligomer_census /
  * kmc_pair_counts / kmc_track_* / kmc_kin_* / kmc_cf_* / kmc_unwrap / kmc_cluster_* / kmc_structure_factor /
- * kmc_bond_order / kmc_bond_order_corr / kmc_network / kmc_rings call: HIP events on the handle's stream around
+ * kmc_bond_order / kmc_bond_order_corr / kmc_network / kmc_rings / kmc_reach_census / kmc_enc_* call: HIP events on the handle's stream around
  * its kernels and clears (the result copies to the host excluded); 0 before
  * the first. */
 double kmc_analysis_ms(const kmc_sim* s);
@@ -1471,6 +1471,156 @@ int kmc_host_bd_sample(const kmc_params* p, const kmc_state_view* v, const kmc_b
                        kmc_bd_out* out, kmc_bd_cell* table);
 int kmc_host_bd_bodies(const kmc_params* p, const kmc_state_view* v, const kmc_bd_view* view, const kmc_bd_out* acc,
                        int32_t min_size, int64_t cap, kmc_bd_body* rows, int64_t* n);
+
+/* Encounter statistics: what happens BEFORE the association
+ * draw.  A bond forms when two sites diffuse into reach, pass the orientation
+ * gates and win a draw (main.cpp:1877-2058); this layer evaluates the first two
+ * conditions exactly on the committed state — what kmc_get_state returns — and
+ * follows every R–L encounter from the update it opens to the one it ends in.
+ * Nothing runs inside kmc_step; every output is an integer count, and the
+ * device, kmc_host_reach_census / kmc_host_enc_* and the tests agree by
+ * equality.
+ *
+ * Definitions (no minimum image anywhere, as in the engine's gates):
+ *   in reach, R–L     the triple (receptor i, ligand b, site k in 2..4) with
+ *                     protein_status[i][2] == 0, protein_status[b][k] == 0 and
+ *                       d2 = dx*dx + dy*dy + dz*dz < T(bond_dist_cutoff),
+ *                     (dx, dy, dz) = R[b][k][2] - R[i][3][2], T(c) the smallest
+ *                     double with sqrt(T) >= c (sqrt(d2) < c <=> d2 < T), no
+ *                     fused multiply-add.
+ *   reactive, R–L     in reach, and |theta_pd| < bond_thetapd_cutoff and
+ *                     |theta_ot - 180| < bond_thetaot_cutoff, the two angles
+ *                     from the vectors of main.cpp:1889-1911 in gettheta's
+ *                     expression order (main.cpp:2329-2366; conv = 180/3.14159).
+ *   in reach, cis     the pair i < j of receptors with protein_status[.][3] == 0
+ *                     on both and d2 of their [3][3] beads < T(cis_dist_cutoff);
+ *                     its kind is MONO when protein_status[.][2] == 0 on both,
+ *                     else CX; reactive when |theta_ot - 180| < cis_thetaot_cutoff
+ *                     (main.cpp:1966-1981, the lower receptor first).
+ *
+ * kmc_reach_census (read-only, no recorder), channels KMC_REACH_RL / MONO / CX:
+ *   out            n_reach, n_reactive per channel; for R–L the receptors with
+ *                  protein_status[.][2] == 0 and the ligand sites with status 0,
+ *                  those of them with at least one partner in reach, and the
+ *                  largest number of partners of one receptor.
+ *   hist_d         [3][2][nd] (may be NULL) in-reach pairs by channel, reactive
+ *                  flag and distance bin k = #{m in 1..nd-1 : E2[m] <= d2},
+ *                  E2[m] = e*e, e = cutoff*m/nd in double (the channel's cutoff).
+ *   hist_a_rl      [na][na] (may be NULL) in-reach R–L triples over
+ *                  (|theta_pd|, |theta_ot - 180|); hist_a_cis [2][na] (may be
+ *                  NULL) the MONO and the CX pairs over |theta_ot - 180|.  An
+ *                  angle x falls into bin min((int)(x * (na / 180.0)), na - 1).
+ *   1 <= nd <= KMC_REACH_MAX_ND, 1 <= na <= KMC_REACH_MAX_NA, else KMC_ERR_ARG.
+ *
+ * The recorder, R–L channel.  Per receptor: the (lig, site) link seen at the
+ * last update (lig: the ligand's reference index n_a + b, 0: none) and
+ * KMC_ENC_SLOTS slots, each key = b << 2 | (k - 2) (b = 1..n_b; 0: empty),
+ * since (the step it opened), nreact (the looks, the opening one included, at
+ * which it was reactive) and flags (KMC_ENC_CENSORED: open at begin; GEMINATE;
+ * REACTIVE: at the last look; WAS_REACTIVE: at some look).  The slots are
+ * sorted by key, the empty ones last.  A receptor's current set is ALL its
+ * in-reach triples cut to the KMC_ENC_SLOTS smallest keys — the result does
+ * not depend on the order a scan meets the pairs in — and the cut entries add
+ * to n_overflow (at begin and at every update).
+ *   kmc_enc_begin   cfg->every >= 1.  The current sets become the slots, since
+ *                   = the current step, flagged CENSORED; the links are stored.
+ *                   A running recorder ends first.  The arrays are allocated
+ *                   here and freed by kmc_enc_end / kmc_destroy.
+ *   kmc_enc_update  due exactly `every` steps after the last one (KMC_ERR_ARG
+ *                   otherwise); a second update at the same step moves only
+ *                   n_updates.  At step t, D = t - last_step, per receptor:
+ *                   1. exp_reach += D * open slots, exp_reactive += D * slots
+ *                      with REACTIVE, exp_free_receptor += D * receptors whose
+ *                      link was 0, all as of the last update;
+ *                   2. R–L born (the link is non-zero and differs from the
+ *                      stored one): if (lig, site) is an open slot,
+ *                      on_from_encounter++ and t - since is filed in row BOUND,
+ *                      or GEM_REBOUND if the slot is GEMINATE; else on_direct++;
+ *                   3. every other open slot that is not in the current set has
+ *                      ended: LOST_RECEPTOR if the receptor is bound now, else
+ *                      LOST_SITE if protein_status[b][k] != 0 now, else
+ *                      SEPARATED; a CENSORED slot files t - since in row
+ *                      CENSORED_ENDED, a GEMINATE one in GEM_ESCAPED (separated)
+ *                      or GEM_LOST, the others in the row of their outcome;
+ *                      each slot that ended in 2. or 3. counts in n_ended and
+ *                      files nreact in react_hist[bound ? 0 : 1];
+ *                   4. every current triple that is not an open slot opens one
+ *                      (n_opened++), since = t, GEMINATE if the stored link is
+ *                      this very triple (the bond to it ended at this update);
+ *                   5. the slots that continue refresh REACTIVE, and nreact += 1
+ *                      when reactive;
+ *                   6. the link is stored; occ_reach, occ_reactive,
+ *                      occ_free_receptor are counted.
+ *                   Every duration and nreact is binned by the kinetics rule
+ *                   (KMC_KIN_BINS bins, §15).
+ *   kmc_enc_sample  read-only over the recorder as of the last update: out, hist
+ *                   (may be NULL) [KMC_ENC_HISTS][KMC_ENC_BINS] — rows 0-7 since
+ *                   begin, row 8 (ALIVE) the ages last_step - since of the open
+ *                   slots that are not CENSORED (those are counted in
+ *                   n_censored_alive) — and react_hist (may be NULL) [2][KMC_ENC_BINS].
+ *   kmc_enc_arrays  copies the per-receptor arrays out, by reference index
+ *                   (each pointer of the view may be NULL).
+ *   kmc_enc_end     drops the recorder and frees its arrays; idempotent.
+ *   kmc_enc_phase_ms  device milliseconds of the last census / begin / update:
+ *                   binning + the distance walk, the gates, the rest.
+ * A new state drops the recorder; a call that fails on the device drops it too;
+ * a decomposed window is refused (KMC_ERR_ARG); KMC_ERR_STATE when a slot or a
+ * receptor's link leaves its range.  kmc_host_*: the same, sequentially (brute
+ * force over all pairs), from host state views, no device: acc carries the
+ * counters between the calls, hist10 [10][KMC_ENC_BINS] rows 0-7 and react_hist's
+ * two.  KMC_DEBUG_ENC_SLOTS (1..4) lowers the slots kept, on both sides. */
+#define KMC_ENC_SLOTS 4
+#define KMC_ENC_BINS 256
+#define KMC_ENC_HISTS 9
+#define KMC_ENC_CENSORED 1
+#define KMC_ENC_GEMINATE 2
+#define KMC_ENC_REACTIVE 4
+#define KMC_ENC_WAS_REACTIVE 8
+#define KMC_REACH_RL 0
+#define KMC_REACH_MONO 1
+#define KMC_REACH_CX 2
+#define KMC_REACH_MAX_ND 64
+#define KMC_REACH_MAX_NA 36
+typedef struct kmc_reach_out {
+  int64_t n_reach[3], n_reactive[3]; /* per channel */
+  int64_t rl_free_receptors, rl_free_sites, rl_receptors_in_reach, rl_sites_in_reach, rl_max_partners;
+} kmc_reach_out;
+typedef struct kmc_enc_config {
+  int32_t every; /* steps between two updates */
+  int32_t reserved;
+} kmc_enc_config;
+typedef struct kmc_enc_out {
+  int64_t origin_step, last_step, n_updates;
+  int64_t on_from_encounter, on_direct, n_opened, n_ended; /* since begin */
+  int64_t exp_reach, exp_reactive, exp_free_receptor;      /* slot-steps, receptor-steps since begin */
+  int64_t n_overflow;                                      /* in-reach triples beyond the slots, summed over the looks */
+  int64_t occ_reach, occ_reactive, occ_free_receptor;      /* at the last look */
+  int64_t n_censored_alive;                                /* kmc_enc_sample only */
+  int64_t every, slots;                                    /* the configuration; the slots kept per receptor */
+} kmc_enc_out;
+typedef struct kmc_enc_view {
+  int32_t *lig, *site; /* [n_a] */
+  int32_t* key;        /* [n_a][KMC_ENC_SLOTS] */
+  int64_t* since;      /* [n_a][KMC_ENC_SLOTS] */
+  int32_t* nreact;     /* [n_a][KMC_ENC_SLOTS] */
+  uint8_t* flags;      /* [n_a][KMC_ENC_SLOTS] */
+} kmc_enc_view;
+int kmc_reach_census(kmc_sim* s, int32_t nd, int32_t na, kmc_reach_out* out, int64_t* hist_d, int64_t* hist_a_rl,
+                     int64_t* hist_a_cis);
+int kmc_enc_begin(kmc_sim* s, const kmc_enc_config* cfg);
+int kmc_enc_update(kmc_sim* s, kmc_enc_out* out);
+int kmc_enc_sample(kmc_sim* s, kmc_enc_out* out, int64_t* hist, int64_t* react_hist);
+int kmc_enc_arrays(kmc_sim* s, const kmc_enc_view* view);
+int kmc_enc_end(kmc_sim* s);
+int kmc_enc_phase_ms(const kmc_sim* s, double ms[3]);
+int kmc_host_reach_census(const kmc_params* p, const kmc_state_view* v, int32_t nd, int32_t na, kmc_reach_out* out,
+                          int64_t* hist_d, int64_t* hist_a_rl, int64_t* hist_a_cis);
+int kmc_host_enc_begin(const kmc_params* p, const kmc_state_view* v, const kmc_enc_config* cfg,
+                       const kmc_enc_view* view, kmc_enc_out* acc, int64_t* hist10);
+int kmc_host_enc_update(const kmc_params* p, const kmc_state_view* v, const kmc_enc_view* view, kmc_enc_out* acc,
+                        int64_t* hist10);
+int kmc_host_enc_sample(const kmc_params* p, const kmc_enc_view* view, const kmc_enc_out* acc, const int64_t* hist10,
+                        kmc_enc_out* out, int64_t* hist, int64_t* react_hist);
 
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */

@@ -367,6 +367,78 @@ def lifetime_survival(ended_row, alive_row):
     return edges, np.cumprod(factor)
 
 
+# ---------------------------------------------------------------- encounter statistics
+def _ratio(num, den) -> float:
+    return float(num) / float(den) if den else 0.0
+
+
+def reach_factors(out, hist_d, cutoffs) -> dict:
+    """From a reach_census (capi.ReachOut or its as_dict(), hist_d[3, 2, nd]) and cutoffs = (bond_dist_cutoff,
+    cis_dist_cutoff), per channel (RL, MONO, CX):
+      orientation_factor [3]   n_reactive / n_reach: the share of in-reach pairs whose orientation gates are open,
+      r [3, nd]                the centres of the distance bins (the channel's cutoff / nd wide),
+      profile [3, nd]          the in-reach pairs per distance bin (reactive or not),
+      reactive_share [3, nd]   the reactive share of each bin.
+    Zeros where a denominator is zero.  Sum the counts of replicas (reduce_counts) before this call."""
+    d = out.as_dict() if hasattr(out, "as_dict") else dict(out)
+    h = np.asarray(hist_d, dtype=np.float64)
+    nd = h.shape[2]
+    cut = np.array([cutoffs[0], cutoffs[1], cutoffs[1]], dtype=np.float64)
+    profile = h.sum(axis=1)
+    return {
+        "orientation_factor": np.array([_ratio(a, b) for a, b in zip(d["n_reactive"], d["n_reach"])]),
+        "r": (np.arange(nd, dtype=np.float64) + 0.5)[None, :] * (cut / nd)[:, None],
+        "profile": profile,
+        "reactive_share": np.divide(h[:, 1], profile, out=np.zeros_like(profile), where=profile > 0),
+    }
+
+
+def encounter_rates(out, time_step: float, ass_rate=None) -> dict:
+    """From an enc_sample / enc_update result (capi.EncOut, capi.EncSample or a dict), float64, zeros where a
+    denominator is zero:
+      encounter_rate         encounters opened per free receptor-step, n_opened / exp_free_receptor,
+      encounter_rate_per_ns  the same divided by time_step (ns),
+      mean_dwell             steps in reach per encounter, exp_reach / n_opened,
+      capture_probability    bonds per encounter, on_from_encounter / n_opened,
+      on_per_reactive_step   on_from_encounter / exp_reactive — beside model_probability = ass_rate * time_step
+                             (with ass_rate), the draw an open gate wins per step,
+      direct_share           on_direct / (on_from_encounter + on_direct): the bonds no look saw coming (the pair
+                             met and bound between two updates).
+    Whether the on-rate is limited by diffusion (few encounters, each captured) or by reaction (many encounters,
+    few captures) reads off encounter_rate and capture_probability."""
+    d = out.as_dict() if hasattr(out, "as_dict") else dict(out)
+    r = {
+        "encounter_rate": _ratio(d["n_opened"], d["exp_free_receptor"]),
+        "mean_dwell": _ratio(d["exp_reach"], d["n_opened"]),
+        "capture_probability": _ratio(d["on_from_encounter"], d["n_opened"]),
+        "on_per_reactive_step": _ratio(d["on_from_encounter"], d["exp_reactive"]),
+        "direct_share": _ratio(d["on_direct"], d["on_from_encounter"] + d["on_direct"]),
+    }
+    r["encounter_rate_per_ns"] = r["encounter_rate"] / float(time_step) if time_step else 0.0
+    if ass_rate is not None:
+        r["model_probability"] = float(ass_rate) * float(time_step)
+    return r
+
+
+def escape_probability(hist) -> dict:
+    """From an enc_sample's hist[ENC_HISTS, ENC_BINS]: of the geminate encounters (a bond ended and the pair was
+    still in reach) that have ended,
+      escape_probability     GEM_ESCAPED / (GEM_REBOUND + GEM_ESCAPED + GEM_LOST): the factor between the
+                             microscopic diss_rate and the observed off-rate,
+      rebinding_probability  GEM_REBOUND over the same,
+      edges, survival        the share of them still open after the durations of each bin (lower edges in steps)."""
+    h = np.asarray(hist)
+    reb, esc, lost = int(h[5].sum()), int(h[6].sum()), int(h[7].sum())
+    n = reb + esc + lost
+    ended = (h[5] + h[6] + h[7]).astype(np.float64)
+    return {
+        "escape_probability": _ratio(esc, n),
+        "rebinding_probability": _ratio(reb, n),
+        "edges": kin_bin_edges() if ended.size == capi.KIN_BINS else np.arange(ended.size, dtype=np.int64),
+        "survival": 1.0 - np.cumsum(ended) / n if n else np.ones_like(ended),
+    }
+
+
 # ---------------------------------------------------------------- cluster growth kinetics (DESIGN.md §16)
 def _cf_expo2(expo2) -> list:
     """expo2 as rows of Python ints: from capi.I128_DTYPE records (the two words), or ints already."""

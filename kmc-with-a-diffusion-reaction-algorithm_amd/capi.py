@@ -1062,6 +1062,118 @@ def default_params(**overrides) -> Params:
     return p
 
 
+ENC_SLOTS, ENC_BINS, ENC_HISTS = 4, 256, 9    # KMC_ENC_SLOTS / KMC_ENC_BINS / KMC_ENC_HISTS
+ENC_CENSORED, ENC_GEMINATE, ENC_REACTIVE, ENC_WAS_REACTIVE = 1, 2, 4, 8  # KMC_ENC_* (bits of a slot)
+REACH_RL, REACH_MONO, REACH_CX = 0, 1, 2      # KMC_REACH_* (channels of the reach census)
+REACH_MAX_ND, REACH_MAX_NA = 64, 36           # KMC_REACH_MAX_ND / KMC_REACH_MAX_NA
+REACH_CHANNELS = ("rl", "mono", "cx")
+# rows of the encounter histogram
+ENC_ROWS = ("bound", "separated", "lost_receptor", "lost_site", "censored_ended", "gem_rebound", "gem_escaped",
+            "gem_lost", "alive")
+
+
+class ReachOut(C.Structure):
+    """kmc_reach_out — the reach census' counts: n_reach, n_reactive per channel (RL, MONO, CX) and the R–L summary."""
+
+    _fields_ = [("n_reach", C.c_int64 * 3), ("n_reactive", C.c_int64 * 3)] + [(name, C.c_int64) for name in (
+        "rl_free_receptors", "rl_free_sites", "rl_receptors_in_reach", "rl_sites_in_reach", "rl_max_partners")]
+
+    def as_dict(self) -> dict:
+        d = {"n_reach": [int(x) for x in self.n_reach], "n_reactive": [int(x) for x in self.n_reactive]}
+        d.update({name: int(getattr(self, name)) for name, _ in self._fields_[2:]})
+        return d
+
+
+class EncConfig(C.Structure):
+    """kmc_enc_config — steps between two updates of the encounter recorder."""
+
+    _fields_ = [("every", C.c_int32), ("reserved", C.c_int32)]
+
+
+def enc_config(every: int = 1) -> EncConfig:
+    c = EncConfig()
+    c.every = int(every)
+    return c
+
+
+class EncOut(C.Structure):
+    """kmc_enc_out — steps, event counters, exposures and occupancy of the encounter recorder."""
+
+    _fields_ = [(name, C.c_int64) for name in (
+        "origin_step", "last_step", "n_updates",
+        "on_from_encounter", "on_direct", "n_opened", "n_ended",
+        "exp_reach", "exp_reactive", "exp_free_receptor",
+        "n_overflow",
+        "occ_reach", "occ_reactive", "occ_free_receptor",
+        "n_censored_alive",
+        "every", "slots")]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class EncView(C.Structure):
+    """kmc_enc_view — caller-owned per-receptor arrays of the encounter recorder."""
+
+    _fields_ = [
+        ("lig", C.POINTER(C.c_int32)),
+        ("site", C.POINTER(C.c_int32)),
+        ("key", C.POINTER(C.c_int32)),
+        ("since", C.POINTER(C.c_int64)),
+        ("nreact", C.POINTER(C.c_int32)),
+        ("flags", C.POINTER(C.c_uint8)),
+    ]
+
+
+class EncArrays:
+    """numpy-backed kmc_enc_view for n_a receptors: lig, site [n_a] and key, since, nreact, flags [n_a, ENC_SLOTS]."""
+
+    DTYPES = dict(lig=np.int32, site=np.int32, key=np.int32, since=np.int64, nreact=np.int32, flags=np.uint8)
+
+    def __init__(self, n_a: int):
+        for name, dt in self.DTYPES.items():
+            shape = (n_a,) if name in ("lig", "site") else (n_a, ENC_SLOTS)
+            setattr(self, name, np.zeros(shape, dtype=dt))
+
+    def view(self) -> EncView:
+        v = EncView()
+        for name, ptr in EncView._fields_:
+            setattr(v, name, getattr(self, name).ctypes.data_as(ptr))
+        return v
+
+
+class EncSample:
+    """One kmc_enc_sample: out (capi.EncOut), hist [ENC_HISTS, ENC_BINS] and react_hist [2, ENC_BINS] int64.
+    counts(): the sample as one int64 vector that adds over replicas (analysis.reduce_counts) — the counters
+    (steps and configuration excluded), then the two histograms."""
+
+    ADDITIVE = ("n_updates", "on_from_encounter", "on_direct", "n_opened", "n_ended", "exp_reach", "exp_reactive",
+                "exp_free_receptor", "n_overflow", "occ_reach", "occ_reactive", "occ_free_receptor",
+                "n_censored_alive")
+
+    def __init__(self, out: EncOut, hist: np.ndarray, react_hist: np.ndarray):
+        self.out, self.hist, self.react_hist = out, hist, react_hist
+
+    def as_dict(self) -> dict:
+        return self.out.as_dict()
+
+    def counts(self) -> np.ndarray:
+        d = self.out.as_dict()
+        return np.concatenate([np.array([d[k] for k in self.ADDITIVE], dtype=np.int64), self.hist.ravel(),
+                               self.react_hist.ravel()])
+
+    @classmethod
+    def from_counts(cls, counts) -> "EncSample":
+        v = np.asarray(counts, dtype=np.int64)
+        n = len(cls.ADDITIVE)
+        out = EncOut()
+        for k, x in zip(cls.ADDITIVE, v[:n]):
+            setattr(out, k, int(x))
+        h = v[n:n + ENC_HISTS * ENC_BINS].reshape(ENC_HISTS, ENC_BINS).copy()
+        r = v[n + ENC_HISTS * ENC_BINS:].reshape(2, ENC_BINS).copy()
+        return cls(out, h, r)
+
+
 class HostState:
     """numpy-backed kmc_state_view for n_a receptors and n_b ligands."""
 

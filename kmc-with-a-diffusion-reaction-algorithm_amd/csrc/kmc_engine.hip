@@ -28,6 +28,7 @@
 #include "kmc_orient.hip"
 #include "kmc_pairdyn.hip"
 #include "kmc_bodydyn.hip"
+#include "kmc_encounter.hip"
 
 using namespace kmcd;
 
@@ -168,6 +169,8 @@ struct __attribute__((visibility("hidden"))) kmc_sim {
   PdState pd;
   BdState bd;
   PoseState pose;
+  EncWalk ew;
+  EncState enc;
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   hipEvent_t bd_ev[2] = {nullptr, nullptr};  // after the components and after the reduction of the last kmc_bd_sample
   double bd_ms[3] = {0.0, 0.0, 0.0};         // its components, reduction and finish (kmc_bd_sample_ms)
@@ -537,6 +540,8 @@ int kmc_destroy(kmc_sim* s) {
     if (e) (void)hipEventDestroy(e);
   for (auto& e : s->an_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : s->ew.ev)
+    if (e) (void)hipEventDestroy(e);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
   if (s->ev_join) (void)hipEventDestroy(s->ev_join);
   if (s->side) (void)hipStreamDestroy(s->side);
@@ -825,6 +830,7 @@ static int set_state_impl(kmc_sim* s, const kmc_state_view* v) {
   s->rot.rec.on = false;  // and the orientation recorder's
   s->pd.rec.on = false;   // and the pair dynamics' origin
   s->bd.rec.on = false;   // and the body dynamics' bodies
+  s->enc.rec.on = false;  // and the encounter recorder's slots
   return KMC_OK;
 }
 

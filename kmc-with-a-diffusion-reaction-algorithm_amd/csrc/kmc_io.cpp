@@ -23,6 +23,7 @@
 #include "kmc_bodydyn.h"
 #include "kmc_bondorder.h"
 #include "kmc_coag.h"
+#include "kmc_encounter.h"
 #include "kmc_host.h"
 #include "kmc_kinetics.h"
 #include "kmc_lagcorr.h"
@@ -2547,6 +2548,284 @@ int kmc_host_bd_bodies(const kmc_params* p, const kmc_state_view* v, const kmc_b
   if (*n > cap) {
     g_host_err = "bd bodies: " + std::to_string(*n) + " bodies qualify, cap is " + std::to_string(cap);
     return KMC_ERR_CAPACITY;
+  }
+  return KMC_OK;
+}
+
+// Encounter statistics (include/kmc.h): kmc_reach_census' and
+// kmc_enc_*'s definitions on host state views by brute force over all pairs;
+// the gates, the bin rules and the slot transition are kmc_encounter.h's, the
+// ones the device evaluates.
+extern "C++" {
+namespace {
+
+struct EncHost {
+  const kmc_params* p;
+  const kmc_state_view* v;
+  int na, nb;
+  double T_bond, T_cis;
+  kmce::V3 a(int i, int j, int k) const {
+    const size_t o = (size_t)((j - 1) * 4 + (k - 1)) * 3;
+    return kmce::V3{v->ra[(o + 0) * na + i], v->ra[(o + 1) * na + i], v->ra[(o + 2) * na + i]};
+  }
+  kmce::V3 b(int q, int j, int k) const {
+    const size_t o = (size_t)((j - 1) * 2 + (k - 1)) * 3;
+    return kmce::V3{v->rb[(o + 0) * nb + q], v->rb[(o + 1) * nb + q], v->rb[(o + 2) * nb + q]};
+  }
+  int st2(int i) const { return v->a_int[0 * (size_t)na + i]; }
+  int st3(int i) const { return v->a_int[1 * (size_t)na + i]; }
+  int stb(int q, int k) const { return v->b_int[(size_t)(k - 1) * nb + q]; }
+};
+
+bool enc_host_open(const kmc_params* p, const kmc_state_view* v, EncHost* h) {
+  if (!p || !v || !v->ra || !v->rb || !v->a_int || !v->b_int || p->n_a < 0 || p->n_b < 0) return false;
+  h->p = p;
+  h->v = v;
+  h->na = p->n_a;
+  h->nb = p->n_b;
+  h->T_bond = kmce::sqrt_threshold(p->bond_dist_cutoff);
+  h->T_cis = kmce::sqrt_threshold(p->cis_dist_cutoff);
+  return true;
+}
+
+// the R–L triple (i, q, k), all 0-based but k: in reach (then *q2, *pd, *ot are set)
+bool enc_host_rl(const EncHost& h, int i, int q, int k, double* q2, double* pd, double* ot) {
+  const kmce::V3 s = h.a(i, 3, 2), t = h.b(q, k, 2);
+  *q2 = kmce::d2(t.x - s.x, t.y - s.y, t.z - s.z);
+  if (!(*q2 < h.T_bond)) return false;
+  kmce::rl_angles(h.a(i, 3, 1), s, h.a(i, 3, 4), h.b(q, k, 1), t, h.b(q, 1, 1), h.b(q, 1, 2), pd, ot);
+  return true;
+}
+
+bool enc_view_ok(const kmc_enc_view* w) { return w && w->lig && w->site && w->key && w->since && w->nreact && w->flags; }
+
+// receptor i's (0-based) current look, checked as the device checks it
+bool enc_host_cur(const EncHost& h, int i, int slots, kmce::Cur* c) {
+  kmck::Cur l;
+  bool ok = kin_host_cur(h.p, h.v, i, &l);
+  if (ok && l.lig != 0 && (l.site < 2 || l.site > 4)) ok = false;
+  kmce::cur_clear(*c, ok ? l.lig : 0, ok && l.lig != 0 ? l.site : 0);
+  if (!ok) return false;
+  if (h.st2(i) != 0) return true;
+  for (int q = 0; q < h.nb; ++q)
+    for (int k = 2; k <= 4; ++k) {
+      if (h.stb(q, k) != 0) continue;
+      double q2, pd, ot;
+      if (!enc_host_rl(h, i, q, k, &q2, &pd, &ot)) continue;
+      kmce::cur_add(*c, slots, kmce::key_of(q + 1, k), pd < h.p->bond_thetapd_cutoff && ot < h.p->bond_thetaot_cutoff);
+    }
+  return true;
+}
+
+kmce::Slots enc_load(const kmc_enc_view* w, int i) {
+  kmce::Slots r;
+  r.lig = w->lig[i];
+  r.site = w->site[i];
+  for (int s = 0; s < ENC_SLOTS; ++s) {
+    r.key[s] = w->key[(size_t)i * ENC_SLOTS + s];
+    r.since[s] = w->since[(size_t)i * ENC_SLOTS + s];
+    r.nreact[s] = w->nreact[(size_t)i * ENC_SLOTS + s];
+    r.flags[s] = w->flags[(size_t)i * ENC_SLOTS + s];
+  }
+  return r;
+}
+
+void enc_store(const kmc_enc_view* w, int i, const kmce::Slots& r) {
+  w->lig[i] = r.lig;
+  w->site[i] = r.site;
+  for (int s = 0; s < ENC_SLOTS; ++s) {
+    w->key[(size_t)i * ENC_SLOTS + s] = r.key[s];
+    w->since[(size_t)i * ENC_SLOTS + s] = r.since[s];
+    w->nreact[(size_t)i * ENC_SLOTS + s] = r.nreact[s];
+    w->flags[(size_t)i * ENC_SLOTS + s] = r.flags[s];
+  }
+}
+
+void enc_set_occ(kmc_enc_out* acc, const int64_t cnt[kmce::ENC_NCNT]) {
+  acc->occ_reach = cnt[kmce::C_OCC_REACH];
+  acc->occ_reactive = cnt[kmce::C_OCC_REACTIVE];
+  acc->occ_free_receptor = cnt[kmce::C_OCC_FREE];
+}
+
+}  // namespace
+}  // extern "C++"
+
+int kmc_host_reach_census(const kmc_params* p, const kmc_state_view* v, int32_t nd, int32_t na, kmc_reach_out* out,
+                          int64_t* hist_d, int64_t* hist_a_rl, int64_t* hist_a_cis) {
+  EncHost h;
+  if (!enc_host_open(p, v, &h) || !out) {
+    g_host_err = "reach census: params, the state's four arrays and out are needed";
+    return KMC_ERR_ARG;
+  }
+  if (nd < 1 || nd > ENC_MAX_ND || na < 1 || na > ENC_MAX_NA) {
+    g_host_err = "reach census: 1 <= nd <= 64 and 1 <= na <= 36";
+    return KMC_ERR_ARG;
+  }
+  double E2[ENC_CHANNELS][ENC_MAX_ND];
+  kmce::edges(p->bond_dist_cutoff, nd, E2[kmce::CH_RL]);
+  kmce::edges(p->cis_dist_cutoff, nd, E2[kmce::CH_MONO]);
+  kmce::edges(p->cis_dist_cutoff, nd, E2[kmce::CH_CX]);
+  std::memset(out, 0, sizeof *out);
+  if (hist_d) std::fill(hist_d, hist_d + (size_t)ENC_CHANNELS * 2 * nd, (int64_t)0);
+  if (hist_a_rl) std::fill(hist_a_rl, hist_a_rl + (size_t)na * na, (int64_t)0);
+  if (hist_a_cis) std::fill(hist_a_cis, hist_a_cis + (size_t)2 * na, (int64_t)0);
+  auto file = [&](int ch, bool react, double q2) {
+    out->n_reach[ch] += 1;
+    out->n_reactive[ch] += react ? 1 : 0;
+    if (hist_d) hist_d[(size_t)(ch * 2 + (react ? 1 : 0)) * nd + kmce::dist_bin(E2[ch], nd, q2)] += 1;
+  };
+  std::vector<uint8_t> site_hit((size_t)3 * h.nb, 0);
+  for (int q = 0; q < h.nb; ++q)
+    for (int k = 2; k <= 4; ++k) out->rl_free_sites += h.stb(q, k) == 0 ? 1 : 0;
+  for (int i = 0; i < h.na; ++i) {
+    if (h.st2(i) != 0) continue;
+    out->rl_free_receptors += 1;
+    int64_t partners = 0;
+    for (int q = 0; q < h.nb; ++q)
+      for (int k = 2; k <= 4; ++k) {
+        if (h.stb(q, k) != 0) continue;
+        double q2, pd, ot;
+        if (!enc_host_rl(h, i, q, k, &q2, &pd, &ot)) continue;
+        file(kmce::CH_RL, pd < p->bond_thetapd_cutoff && ot < p->bond_thetaot_cutoff, q2);
+        if (hist_a_rl) hist_a_rl[(size_t)kmce::ang_bin(pd, na) * na + kmce::ang_bin(ot, na)] += 1;
+        site_hit[(size_t)3 * q + (k - 2)] = 1;
+        partners += 1;
+      }
+    out->rl_receptors_in_reach += partners > 0 ? 1 : 0;
+    out->rl_max_partners = std::max(out->rl_max_partners, partners);
+  }
+  for (uint8_t f : site_hit) out->rl_sites_in_reach += f;
+  for (int i = 0; i < h.na; ++i) {
+    if (h.st3(i) != 0) continue;
+    for (int j = i + 1; j < h.na; ++j) {
+      if (h.st3(j) != 0) continue;
+      const kmce::V3 si = h.a(i, 3, 3), sj = h.a(j, 3, 3);
+      const double q2 = kmce::d2(sj.x - si.x, sj.y - si.y, sj.z - si.z);
+      if (!(q2 < h.T_cis)) continue;
+      const double ot = kmce::cis_angle(h.a(i, 3, 1), si, h.a(j, 3, 1), sj);
+      const int ch = h.st2(i) != 0 || h.st2(j) != 0 ? kmce::CH_CX : kmce::CH_MONO;
+      file(ch, ot < p->cis_thetaot_cutoff, q2);
+      if (hist_a_cis) hist_a_cis[(size_t)(ch - kmce::CH_MONO) * na + kmce::ang_bin(ot, na)] += 1;
+    }
+  }
+  return KMC_OK;
+}
+
+int kmc_host_enc_begin(const kmc_params* p, const kmc_state_view* v, const kmc_enc_config* cfg,
+                       const kmc_enc_view* view, kmc_enc_out* acc, int64_t* hist10) {
+  EncHost h;
+  if (!enc_host_open(p, v, &h) || !cfg || !enc_view_ok(view) || !acc || !hist10) {
+    g_host_err = "enc: params, state, the configuration, the view's six arrays, acc and hist are needed";
+    return KMC_ERR_ARG;
+  }
+  if (cfg->every < 1) {
+    g_host_err = "enc: every >= 1";
+    return KMC_ERR_ARG;
+  }
+  // debug: fewer slots are kept per receptor
+  const char* e = getenv("KMC_DEBUG_ENC_SLOTS");
+  const int slots = e && *e ? std::max(1, std::min(ENC_SLOTS, atoi(e))) : ENC_SLOTS;
+  int64_t cnt[kmce::ENC_NCNT] = {0};
+  std::vector<kmce::Slots> recs((size_t)h.na);
+  for (int i = 0; i < h.na; ++i) {
+    kmce::Cur c;
+    if (!enc_host_cur(h, i, slots, &c)) {
+      g_host_err = "enc: a receptor's bond link leaves its range";
+      return KMC_ERR_STATE;
+    }
+    int32_t m[kmce::ENC_NCNT] = {0};
+    kmce::begin(v->step, c, recs[(size_t)i], m);
+    for (int k = 0; k < kmce::ENC_NCNT; ++k) cnt[k] += m[k];
+  }
+  for (int i = 0; i < h.na; ++i) enc_store(view, i, recs[(size_t)i]);
+  std::memset(acc, 0, sizeof *acc);
+  std::fill(hist10, hist10 + (size_t)ENC_ACC_ROWS * ENC_BINS, (int64_t)0);
+  acc->origin_step = acc->last_step = v->step;
+  acc->n_overflow = cnt[kmce::C_OVERFLOW];
+  acc->every = cfg->every;
+  acc->slots = slots;
+  enc_set_occ(acc, cnt);
+  return KMC_OK;
+}
+
+int kmc_host_enc_update(const kmc_params* p, const kmc_state_view* v, const kmc_enc_view* view, kmc_enc_out* acc,
+                        int64_t* hist10) {
+  EncHost h;
+  if (!enc_host_open(p, v, &h) || !enc_view_ok(view) || !acc || !hist10) {
+    g_host_err = "enc: params, state, the view's six arrays, acc and hist are needed";
+    return KMC_ERR_ARG;
+  }
+  const int64_t t = v->step, dt = t - acc->last_step;
+  if (dt == 0) {  // a second update at the same step moves only the count
+    acc->n_updates += 1;
+    return KMC_OK;
+  }
+  if (dt != acc->every) {
+    g_host_err = "enc: an update is due " + std::to_string(acc->every) + " steps after the last one";
+    return KMC_ERR_ARG;
+  }
+  const int slots = (int)acc->slots;
+  std::vector<kmce::Cur> cur((size_t)h.na);
+  for (int i = 0; i < h.na; ++i)  // checked first: a failed call leaves the recorder as it was
+    if (!enc_host_cur(h, i, slots, &cur[(size_t)i])) {
+      g_host_err = "enc: a receptor's bond link leaves its range";
+      return KMC_ERR_STATE;
+    }
+  acc->exp_reach += dt * acc->occ_reach;
+  acc->exp_reactive += dt * acc->occ_reactive;
+  acc->exp_free_receptor += dt * acc->occ_free_receptor;
+  int64_t cnt[kmce::ENC_NCNT] = {0};
+  for (int i = 0; i < h.na; ++i) {
+    kmce::Slots r = enc_load(view, i);
+    bool occ[ENC_SLOTS];
+    for (int s = 0; s < ENC_SLOTS; ++s) {
+      const int32_t k = r.key[s];
+      const int q = (k >> 2) - 1;
+      occ[s] = k != 0 && q >= 0 && q < h.nb && h.stb(q, 2 + (k & 3)) != 0;
+    }
+    kmce::Events ev;
+    int32_t m[kmce::ENC_NCNT] = {0};
+    kmce::transition(t, h.na, cur[(size_t)i], occ, r, ev, m);
+    for (int k = 0; k < ev.n; ++k) {
+      hist10[(size_t)ev.row[k] * ENC_BINS + kmck::bin(ev.val[k])] += 1;
+      hist10[(size_t)(ENC_ROWS_UPD + ev.rrow[k]) * ENC_BINS + kmck::bin(ev.rval[k])] += 1;
+    }
+    enc_store(view, i, r);
+    for (int k = 0; k < kmce::ENC_NCNT; ++k) cnt[k] += m[k];
+  }
+  acc->on_from_encounter += cnt[kmce::C_FROM_ENCOUNTER];
+  acc->on_direct += cnt[kmce::C_DIRECT];
+  acc->n_opened += cnt[kmce::C_OPENED];
+  acc->n_ended += cnt[kmce::C_ENDED];
+  acc->n_overflow += cnt[kmce::C_OVERFLOW];
+  enc_set_occ(acc, cnt);
+  acc->last_step = t;
+  acc->n_updates += 1;
+  return KMC_OK;
+}
+
+int kmc_host_enc_sample(const kmc_params* p, const kmc_enc_view* view, const kmc_enc_out* acc, const int64_t* hist10,
+                        kmc_enc_out* out, int64_t* hist, int64_t* react_hist) {
+  if (!p || !enc_view_ok(view) || !acc || !hist10 || !out) {
+    g_host_err = "enc sample: params, the view's six arrays, acc, hist10 and out are needed";
+    return KMC_ERR_ARG;
+  }
+  const kmc_enc_out a = *acc;  // (out may be acc itself)
+  *out = a;
+  out->n_censored_alive = 0;
+  if (hist) {
+    std::copy(hist10, hist10 + (size_t)ENC_ROWS_UPD * ENC_BINS, hist);
+    std::fill(hist + (size_t)ENC_ROWS_UPD * ENC_BINS, hist + (size_t)ENC_HISTS * ENC_BINS, (int64_t)0);
+  }
+  if (react_hist)
+    std::copy(hist10 + (size_t)ENC_ROWS_UPD * ENC_BINS, hist10 + (size_t)ENC_ACC_ROWS * ENC_BINS, react_hist);
+  for (int i = 0; i < p->n_a; ++i) {
+    const kmce::Slots r = enc_load(view, i);
+    for (int s = 0; s < ENC_SLOTS; ++s) {
+      if (r.key[s] == 0) continue;
+      if (r.flags[s] & kmce::F_CENSORED) out->n_censored_alive += 1;
+      else if (hist) hist[(size_t)kmce::ROW_ALIVE * ENC_BINS + kmck::bin(a.last_step - r.since[s])] += 1;
+    }
   }
   return KMC_OK;
 }

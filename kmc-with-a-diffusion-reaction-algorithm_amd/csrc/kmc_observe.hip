@@ -2222,4 +2222,381 @@ int kmc_ligand_pose(kmc_sim* s, int32_t nz, int32_t nc, int64_t* hist, kmc_pose_
   return KMC_OK;
 }
 
+// ---------------------------------------------------------------- encounters
+// kmc_encounter.hip: a read-only census and a recorder on the kinetics
+// recorder's life cycle (begin allocates its arrays, end frees them).  Both run
+// the same walk: binning, phase A into the hit list (read back once: a list
+// that was too short is grown and the walk replayed), the per-receptor scan,
+// phase B.  The walk's scratch is the handle's, allocated at the first call.
+
+static_assert(KMC_ENC_SLOTS == ENC_SLOTS && KMC_ENC_BINS == ENC_BINS && KMC_ENC_HISTS == ENC_HISTS &&
+                  KMC_REACH_MAX_ND == ENC_MAX_ND && KMC_REACH_MAX_NA == ENC_MAX_NA &&
+                  KMC_ENC_CENSORED == kmce::F_CENSORED && KMC_ENC_GEMINATE == kmce::F_GEMINATE &&
+                  KMC_ENC_REACTIVE == kmce::F_REACTIVE && KMC_ENC_WAS_REACTIVE == kmce::F_WAS_REACTIVE,
+              "kmc.h and kmc_encounter.h agree");
+
+static const char* const ENC_OFF = "enc: not begun (kmc_enc_begin; a new state drops the recorder)";
+
+// the walk's scratch: 48 bytes per receptor, 123 per ligand, 16 per cell of the search grid, 28 per hit
+static int enc_reserve(kmc_sim* s) {
+  EncWalk& E = s->ew;
+  EncW& W = E.w;
+  if (W.acc) return KMC_OK;
+  const size_t NA = (size_t)s->K.NA, NS = 3 * (size_t)s->K.NB;
+  // cell side: the larger cutoff (and a margin for the division's rounding), but about 8 proteins a cell at least
+  const double cut = std::max(s->p.bond_dist_cutoff, s->p.cis_dist_cutoff) * (1.0 + 1.0 / 1024.0);
+  EncGrid G;
+  G.cs = std::max(cut, std::sqrt(8.0 * s->p.box_x * s->p.box_y / (double)std::max(1, s->K.N)));
+  G.x0 = -s->p.box_x / 2;
+  G.y0 = -s->p.box_y / 2;
+  G.ncx = (int)std::max(1.0, std::min(32768.0, std::ceil(s->p.box_x / G.cs)));
+  G.ncy = (int)std::max(1.0, std::min(32768.0, std::ceil(s->p.box_y / G.cs)));
+  const size_t ncnt = (size_t)G.ncx * G.ncy + 1;
+  // debug: the walk stages fewer points at a time
+  E.chunk = (int)int_getenv("KMC_DEBUG_ENC_CHUNK", ENC_CHUNK, 1, ENC_CHUNK);
+  // debug: a shorter first hit list (the growth and the replay at test size)
+  const int64_t hits0 = std::max<int64_t>(1024, s->K.N);
+  const unsigned int cap = (unsigned int)int_getenv("KMC_DEBUG_ENC_HITS", hits0, 1, hits0);
+  for (auto& e : E.ev)
+    if (!e) HIPCHK(s, hipEventCreate(&e));
+  int rc = KMC_OK;
+  rc |= dalloc(s, &W.probe, NA);
+  rc |= dalloc(s, &W.point, NS);
+  rc |= dalloc(s, &W.pcell, NA);
+  rc |= dalloc(s, &W.prank, NA);
+  rc |= dalloc(s, &W.tcell, NS);
+  rc |= dalloc(s, &W.trank, NS);
+  rc |= dalloc(s, &W.pcnt, ncnt);
+  rc |= dalloc(s, &W.pstart, ncnt);
+  rc |= dalloc(s, &W.tcnt, ncnt);
+  rc |= dalloc(s, &W.tstart, ncnt);
+  rc |= dalloc(s, &W.part, (ncnt + SCAN_TILE - 1) / SCAN_TILE);
+  rc |= dalloc(s, &W.rcnt, NA + 1);
+  rc |= dalloc(s, &W.rstart, NA + 1);
+  rc |= dalloc(s, &W.rpart, (NA + 1 + SCAN_TILE - 1) / SCAN_TILE);
+  rc |= dalloc(s, &W.hits, (size_t)cap);
+  rc |= dalloc(s, &W.rhit, (size_t)cap);
+  rc |= dalloc(s, &W.site_flag, NS);
+  rc |= dalloc(s, &W.E2, (size_t)ENC_CHANNELS * ENC_MAX_ND);
+  rc |= dalloc(s, &W.tab, (size_t)ENC_TAB_WORDS);
+  if (rc == KMC_OK) rc = dalloc(s, &W.acc, 1);  // (the last: set when all the others are)
+  if (rc != KMC_OK) {
+    dfree(s, W.probe), dfree(s, W.point), dfree(s, W.pcell), dfree(s, W.prank), dfree(s, W.tcell), dfree(s, W.trank);
+    dfree(s, W.pcnt), dfree(s, W.pstart), dfree(s, W.tcnt), dfree(s, W.tstart), dfree(s, W.part), dfree(s, W.rcnt);
+    dfree(s, W.rstart), dfree(s, W.rpart), dfree(s, W.hits), dfree(s, W.rhit), dfree(s, W.site_flag), dfree(s, W.E2);
+    dfree(s, W.tab);
+    return fail(s, KMC_ERR_HIP, "enc: scratch allocation failed");
+  }
+  W.hit_cap = cap;
+  W.G = G;
+  return KMC_OK;
+}
+
+// one walk (walk 0 or 1 of the call: its two events) on the handle's stream; the stream is waited for once,
+// after phase A
+static int enc_walk(kmc_sim* s, bool cis, int walk, int nd, int na, int hist) {
+  EncWalk& E = s->ew;
+  EncW& W = E.w;
+  hipStream_t st = s->stream;
+  const int NA = s->K.NA, NS = 3 * s->K.NB, ncell = W.G.ncx * W.G.ncy;
+  const int nthr = std::max(NA, cis ? 0 : NS);
+  unsigned int nhits = 0;
+  HIPCHK(s, hipMemsetAsync(W.pcnt, 0, sizeof(int32_t) * (size_t)(ncell + 1), st));
+  if (!cis) {
+    HIPCHK(s, hipMemsetAsync(W.tcnt, 0, sizeof(int32_t) * (size_t)(ncell + 1), st));
+    HIPCHK(s, hipMemsetAsync(W.site_flag, 0, (size_t)std::max(NS, 1), st));
+  }
+  HIPCHK(s, hipMemsetAsync(W.rcnt, 0, sizeof(int32_t) * (size_t)(NA + 1), st));
+  HIPCHK(s, hipMemsetAsync(&W.acc->nhits, 0, sizeof(unsigned int), st));
+  if (NA > 0) {
+    const unsigned gr = (unsigned)((nthr + ENC_T - 1) / ENC_T);
+    const unsigned gw = (unsigned)std::min((ncell + ENC_WAVES - 1) / ENC_WAVES, AN_WG_MAX);
+    const size_t lds = sizeof(EncPt) * 2 * ENC_WAVES * (size_t)E.chunk;
+    const double T2 = cis ? s->K.T_cis : s->K.T_bond;
+    if (cis) k_enc_count<true><<<gr, ENC_T, 0, st>>>(s->K, s->d, W);
+    else k_enc_count<false><<<gr, ENC_T, 0, st>>>(s->K, s->d, W);
+    bins_scan(s, W.pcnt, W.pstart, ncell + 1, W.part);
+    if (!cis) bins_scan(s, W.tcnt, W.tstart, ncell + 1, W.part);
+    if (cis) k_enc_scatter<true><<<gr, ENC_T, 0, st>>>(s->K, s->d, W);
+    else k_enc_scatter<false><<<gr, ENC_T, 0, st>>>(s->K, s->d, W);
+    for (int attempt = 0;; ++attempt) {
+      if (cis) k_enc_walk<true><<<gw, ENC_T, lds, st>>>(W, T2, E.chunk);
+      else k_enc_walk<false><<<gw, ENC_T, lds, st>>>(W, T2, E.chunk);
+      HIPCHK(s, hipGetLastError());
+      HIPCHK(s, hipMemcpyAsync(&nhits, &W.acc->nhits, sizeof nhits, hipMemcpyDeviceToHost, st));
+      HIPCHK(s, hipStreamSynchronize(st));
+      if (nhits <= W.hit_cap) break;
+      if (attempt > 0) return fail(s, KMC_ERR_CAPACITY, "enc: the hit list overflowed after it was grown");
+      // the list was too short: grown to what the walk counted, and the walk replayed
+      dfree(s, W.hits);
+      dfree(s, W.rhit);
+      W.hit_cap = 0;
+      int rc = dalloc(s, &W.hits, (size_t)nhits);
+      if (rc == KMC_OK) rc = dalloc(s, &W.rhit, (size_t)nhits);
+      if (rc != KMC_OK) return fail(s, KMC_ERR_HIP, "enc: the hit list could not be grown");
+      W.hit_cap = nhits;
+      HIPCHK(s, hipMemsetAsync(W.rcnt, 0, sizeof(int32_t) * (size_t)(NA + 1), st));
+      HIPCHK(s, hipMemsetAsync(&W.acc->nhits, 0, sizeof(unsigned int), st));
+    }
+  }
+  HIPCHK(s, hipEventRecord(E.ev[2 * walk], st));
+  if (NA > 0) {
+    if (!cis) bins_scan(s, W.rcnt, W.rstart, NA + 1, W.rpart);
+    const unsigned gb = (unsigned)std::min<size_t>(std::max<size_t>(((size_t)nhits + ENC_T - 1) / ENC_T, 1), AN_WG_MAX);
+    if (cis) k_enc_gates<true><<<gb, ENC_T, 0, st>>>(s->K, s->d, W, nd, na, hist);
+    else k_enc_gates<false><<<gb, ENC_T, 0, st>>>(s->K, s->d, W, nd, na, hist);
+  }
+  HIPCHK(s, hipEventRecord(E.ev[2 * walk + 1], st));
+  HIPCHK(s, hipGetLastError());
+  return KMC_OK;
+}
+
+// the phases' times of a call of `walks` walks, after an_end
+static int enc_times(kmc_sim* s, int walks) {
+  EncWalk& E = s->ew;
+  float a = 0, b = 0, c = 0, t = 0;
+  HIPCHK(s, hipEventElapsedTime(&a, s->an_ev[0], E.ev[0]));
+  HIPCHK(s, hipEventElapsedTime(&b, E.ev[0], E.ev[1]));
+  if (walks == 2) {
+    HIPCHK(s, hipEventElapsedTime(&t, E.ev[1], E.ev[2]));
+    a += t;
+    HIPCHK(s, hipEventElapsedTime(&t, E.ev[2], E.ev[3]));
+    b += t;
+  }
+  HIPCHK(s, hipEventElapsedTime(&c, E.ev[2 * walks - 1], s->an_ev[1]));
+  E.ms[0] = a;
+  E.ms[1] = b;
+  E.ms[2] = c;
+  return KMC_OK;
+}
+
+int kmc_enc_phase_ms(const kmc_sim* s, double ms[3]) {
+  if (!s || !ms) return KMC_ERR_ARG;
+  for (int k = 0; k < 3; ++k) ms[k] = s->ew.ms[k];
+  return KMC_OK;
+}
+
+int kmc_reach_census(kmc_sim* s, int32_t nd, int32_t na, kmc_reach_out* out, int64_t* hist_d, int64_t* hist_a_rl,
+                     int64_t* hist_a_cis) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "reach census: out is needed");
+  if (nd < 1 || nd > ENC_MAX_ND || na < 1 || na > ENC_MAX_NA)
+    return fail(s, KMC_ERR_ARG, "reach census: 1 <= nd <= 64 and 1 <= na <= 36");
+  int rc = an_check(s);
+  if (rc == KMC_OK) rc = enc_reserve(s);
+  if (rc != KMC_OK) return rc;
+  EncW& W = s->ew.w;
+  double E2[ENC_CHANNELS * ENC_MAX_ND] = {0.0};
+  kmce::edges(s->p.bond_dist_cutoff, nd, E2 + kmce::CH_RL * ENC_MAX_ND);
+  kmce::edges(s->p.cis_dist_cutoff, nd, E2 + kmce::CH_MONO * ENC_MAX_ND);
+  kmce::edges(s->p.cis_dist_cutoff, nd, E2 + kmce::CH_CX * ENC_MAX_ND);
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  hipStream_t st = s->stream;
+  HIPCHK(s, hipMemcpyAsync(W.E2, E2, sizeof E2, hipMemcpyHostToDevice, st));  // (waited for in the first walk)
+  HIPCHK(s, hipMemsetAsync(W.acc, 0, sizeof(EncAcc), st));
+  HIPCHK(s, hipMemsetAsync(W.tab, 0, sizeof(enc_u64) * ENC_TAB_WORDS, st));
+  rc = enc_walk(s, false, 0, nd, na, 1);
+  if (rc != KMC_OK) return rc;
+  const int nthr = std::max(s->K.NA, 3 * s->K.NB);
+  if (s->K.NA > 0) k_enc_census_fin<<<(unsigned)((nthr + ENC_T - 1) / ENC_T), ENC_T, 0, st>>>(s->K, W);
+  rc = enc_walk(s, true, 1, nd, na, 1);
+  if (rc == KMC_OK) rc = an_end(s);
+  if (rc == KMC_OK) rc = enc_times(s, 2);
+  if (rc != KMC_OK) return rc;
+  EncAcc a;
+  std::vector<enc_u64> tab(ENC_TAB_WORDS);
+  HIPCHK(s, hipMemcpy(&a, W.acc, sizeof a, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(tab.data(), W.tab, sizeof(enc_u64) * ENC_TAB_WORDS, hipMemcpyDeviceToHost));
+  if (a.err) return fail(s, KMC_ERR_STATE, "reach census: a slot leaves its range");
+  std::memset(out, 0, sizeof *out);
+  for (int c = 0; c < ENC_CHANNELS; ++c) {
+    out->n_reach[c] = (int64_t)tab[ENC_TAB_N + c];
+    out->n_reactive[c] = (int64_t)tab[ENC_TAB_N + 3 + c];
+  }
+  out->rl_free_receptors = (int64_t)tab[ENC_TAB_RL + 0];
+  out->rl_free_sites = (int64_t)tab[ENC_TAB_RL + 1];
+  out->rl_receptors_in_reach = (int64_t)tab[ENC_TAB_RL + 2];
+  out->rl_sites_in_reach = (int64_t)tab[ENC_TAB_RL + 3];
+  out->rl_max_partners = (int64_t)a.max_partners;
+  auto put = [](int64_t* to, const enc_u64* from, size_t n) {
+    if (to)
+      for (size_t k = 0; k < n; ++k) to[k] = (int64_t)from[k];
+  };
+  put(hist_d, tab.data() + ENC_TAB_D, (size_t)ENC_CHANNELS * 2 * nd);
+  put(hist_a_rl, tab.data() + ENC_TAB_ARL, (size_t)na * na);
+  put(hist_a_cis, tab.data() + ENC_TAB_ACIS, (size_t)2 * na);
+  return KMC_OK;
+}
+
+static void enc_fill(const kmc_sim* s, int64_t alive, kmc_enc_out* out) {
+  const EncState& g = s->enc;
+  std::memset(out, 0, sizeof *out);
+  out->origin_step = g.rec.origin;
+  out->last_step = g.rec.last;
+  out->n_updates = g.rec.updates;
+  out->on_from_encounter = g.ev[kmce::C_FROM_ENCOUNTER];
+  out->on_direct = g.ev[kmce::C_DIRECT];
+  out->n_opened = g.ev[kmce::C_OPENED];
+  out->n_ended = g.ev[kmce::C_ENDED];
+  out->n_overflow = g.ev[kmce::C_OVERFLOW];
+  out->exp_reach = g.exp[0];
+  out->exp_reactive = g.exp[1];
+  out->exp_free_receptor = g.exp[2];
+  out->occ_reach = g.occ[0];
+  out->occ_reactive = g.occ[1];
+  out->occ_free_receptor = g.occ[2];
+  out->n_censored_alive = alive;
+  out->every = g.every;
+  out->slots = g.slots;
+}
+
+// the device work of a begin (t: its step) or an update: the R–L walk, then the slot kernel; the counters come back
+static int enc_look(kmc_sim* s, bool begin, EncAcc* a) {
+  EncState& g = s->enc;
+  EncW& W = s->ew.w;
+  hipStream_t st = s->stream;
+  int rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemsetAsync(W.acc, 0, sizeof(EncAcc), st));
+  rc = enc_walk(s, false, 0, 0, 0, 0);
+  if (rc != KMC_OK) return rc;
+  const int NA = s->K.NA;
+  if (NA > 0) {
+    const unsigned gr = (unsigned)((NA + ENC_T - 1) / ENC_T);
+    if (begin) k_enc_slots<true><<<gr, ENC_T, 0, st>>>(s->K, s->d, W, g.dev, g.slots, (long long)s->step_done, g.hist);
+    else k_enc_slots<false><<<gr, ENC_T, 0, st>>>(s->K, s->d, W, g.dev, g.slots, (long long)s->step_done, g.hist);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc == KMC_OK) rc = enc_times(s, 1);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpy(a, W.acc, sizeof *a, hipMemcpyDeviceToHost));
+  if (a->err) return fail(s, KMC_ERR_STATE, "enc: a slot or a receptor's bond link leaves its range");
+  return KMC_OK;
+}
+
+int kmc_enc_begin(kmc_sim* s, const kmc_enc_config* cfg) {
+  if (!s) return KMC_ERR_ARG;
+  if (!cfg) return fail(s, KMC_ERR_ARG, "enc: the configuration is needed");
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  if (cfg->every < 1) return fail(s, KMC_ERR_ARG, "enc: every >= 1");
+  // a recorder that was on ends here, whatever becomes of this call
+  rc = rec_end(s, s->enc);
+  if (rc == KMC_OK) rc = enc_reserve(s);
+  if (rc != KMC_OK) return rc;
+  EncState& g = s->enc;
+  const size_t NA = (size_t)s->K.NA;
+  rc = KMC_OK;
+  rc |= salloc(s, g.scratch, &g.dev.lig, NA);
+  rc |= salloc(s, g.scratch, &g.dev.site, NA);
+  rc |= salloc(s, g.scratch, &g.dev.key, NA);
+  rc |= salloc(s, g.scratch, &g.dev.since, NA);
+  rc |= salloc(s, g.scratch, &g.dev.nreact, NA);
+  rc |= salloc(s, g.scratch, &g.dev.flags, NA);
+  rc |= salloc(s, g.scratch, &g.hist, (size_t)(ENC_ACC_ROWS + 1) * ENC_BINS);  // (zero: salloc)
+  if (rc != KMC_OK) {
+    scratch_drop(s, s->enc);
+    return fail(s, KMC_ERR_HIP, "enc: allocation failed (76 bytes per receptor)");
+  }
+  g.every = cfg->every;
+  // debug: fewer slots are kept per receptor
+  g.slots = (int)int_getenv("KMC_DEBUG_ENC_SLOTS", ENC_SLOTS, 1, ENC_SLOTS);
+  EncAcc a;
+  rc = enc_look(s, true, &a);
+  if (rc != KMC_OK) {
+    scratch_drop(s, s->enc);
+    return rc;
+  }
+  g.ev[kmce::C_OVERFLOW] = (int64_t)a.cnt[kmce::C_OVERFLOW];
+  for (int k = 0; k < 3; ++k) g.occ[k] = (int64_t)a.cnt[kmce::C_OCC_REACH + k];
+  g.rec = Recorder{true, s->step_done, s->step_done, 0};
+  return KMC_OK;
+}
+
+int kmc_enc_update(kmc_sim* s, kmc_enc_out* out) {
+  if (!s) return KMC_ERR_ARG;
+  int rc = rec_check(s, s->enc.rec, ENC_OFF);
+  if (rc != KMC_OK) return rc;
+  EncState& g = s->enc;
+  if (s->step_done == g.rec.last) {  // a second update at the same step moves only the count
+    g.rec.updates += 1;
+    if (out) enc_fill(s, 0, out);
+    return KMC_OK;
+  }
+  if (s->step_done != g.rec.last + g.every)
+    return fail(s, KMC_ERR_ARG, "enc: an update is due " + std::to_string(g.every) + " steps after the last one");
+  EncAcc a;
+  rc = enc_look(s, false, &a);
+  if (rc != KMC_OK) {
+    g.rec.on = false;  // the slots may be half advanced
+    return rc;
+  }
+  const int64_t dt = s->step_done - g.rec.last;
+  for (int k = 0; k < 3; ++k) {
+    g.exp[k] += dt * g.occ[k];
+    g.occ[k] = (int64_t)a.cnt[kmce::C_OCC_REACH + k];
+  }
+  for (int k = 0; k < ENC_NEV; ++k) g.ev[k] += (int64_t)a.cnt[k];
+  g.rec.last = s->step_done;
+  g.rec.updates += 1;
+  if (out) enc_fill(s, 0, out);
+  return KMC_OK;
+}
+
+int kmc_enc_sample(kmc_sim* s, kmc_enc_out* out, int64_t* hist, int64_t* react_hist) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out) return fail(s, KMC_ERR_ARG, "enc sample: out is needed");
+  int rc = rec_check(s, s->enc.rec, ENC_OFF);
+  if (rc == KMC_OK) rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  EncState& g = s->enc;
+  EncW& W = s->ew.w;
+  enc_u64* row = g.hist + (size_t)ENC_ACC_ROWS * ENC_BINS;
+  HIPCHK(s, hipMemsetAsync(row, 0, sizeof(enc_u64) * ENC_BINS, s->stream));
+  HIPCHK(s, hipMemsetAsync(&W.acc->alive, 0, sizeof(enc_u64), s->stream));
+  const int NA = s->K.NA, nblk = (NA + ENC_T - 1) / ENC_T;
+  if (nblk > 0)
+    k_enc_sample<<<(unsigned)std::min(nblk, AN_WG_MAX), ENC_T, 0, s->stream>>>(NA, g.dev, (long long)g.rec.last, nblk,
+                                                                             row, W.acc);
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);
+  if (rc != KMC_OK) return rc;
+  enc_u64 alive = 0;
+  HIPCHK(s, hipMemcpy(&alive, &W.acc->alive, sizeof alive, hipMemcpyDeviceToHost));
+  enc_fill(s, (int64_t)alive, out);
+  static_assert(sizeof(enc_u64) == sizeof(int64_t), "the bins are copied out as they are");
+  if (hist) {
+    HIPCHK(s, hipMemcpy(hist, g.hist, sizeof(enc_u64) * ENC_ROWS_UPD * ENC_BINS, hipMemcpyDeviceToHost));
+    HIPCHK(s, hipMemcpy(hist + (size_t)ENC_ROWS_UPD * ENC_BINS, row, sizeof(enc_u64) * ENC_BINS, hipMemcpyDeviceToHost));
+  }
+  if (react_hist)
+    HIPCHK(s, hipMemcpy(react_hist, g.hist + (size_t)ENC_ROWS_UPD * ENC_BINS, sizeof(enc_u64) * ENC_REACT * ENC_BINS,
+                        hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_enc_arrays(kmc_sim* s, const kmc_enc_view* v) {
+  if (!s) return KMC_ERR_ARG;
+  if (!v) return fail(s, KMC_ERR_ARG, "enc arrays: the view is needed (each of its arrays may be NULL)");
+  const int rc = rec_check(s, s->enc.rec, ENC_OFF);
+  if (rc != KMC_OK) return rc;
+  const size_t NA = (size_t)s->K.NA;
+  const Enc& D = s->enc.dev;
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  if (NA == 0) return KMC_OK;
+  if (v->lig) HIPCHK(s, hipMemcpy(v->lig, D.lig, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  if (v->site) HIPCHK(s, hipMemcpy(v->site, D.site, sizeof(int32_t) * NA, hipMemcpyDeviceToHost));
+  if (v->key) HIPCHK(s, hipMemcpy(v->key, D.key, sizeof(int4) * NA, hipMemcpyDeviceToHost));
+  if (v->since) HIPCHK(s, hipMemcpy(v->since, D.since, sizeof(longlong4) * NA, hipMemcpyDeviceToHost));
+  if (v->nreact) HIPCHK(s, hipMemcpy(v->nreact, D.nreact, sizeof(int4) * NA, hipMemcpyDeviceToHost));
+  if (v->flags) HIPCHK(s, hipMemcpy(v->flags, D.flags, sizeof(uchar4) * NA, hipMemcpyDeviceToHost));
+  return KMC_OK;
+}
+
+int kmc_enc_end(kmc_sim* s) {
+  return s ? rec_end(s, s->enc) : KMC_ERR_ARG;
+}
+
 }  // extern "C"

@@ -66,6 +66,26 @@
 //                                  occ_free_site n_rl_censored_alive n_cis_censored_alive
 //                            and per non-empty bin of the histogram since that origin
 //                              life step row bin count
+//           [--reach FILE]   reach census (kmc_reach_census, 16 distance and 18 angle bins): every
+//                            out_interval FILE gets per channel (0 R-L, 1 mono cis, 2 complex cis)
+//                              reach step channel n_reach n_reactive
+//                            then
+//                              reachrl step free_receptors free_sites receptors_in_reach sites_in_reach
+//                                      max_partners
+//                            and per non-empty bin
+//                              rd step channel reactive k count     (distance bins)
+//                              ra step i j count                    (R-L: |theta_pd| bin, |theta_ot - 180| bin)
+//                              rc step kind k count                 (cis, kind 0 mono 1 complex: |theta_ot - 180| bin)
+//           [--enc EVERY FILE]  R-L encounter recorder (kmc_enc_*): it begins at the state the process starts
+//                            or resumes from (not checkpointed: a resume starts a new origin, every enc line
+//                            carries it); kmc_step runs in pieces that end where an update is due, EVERY steps
+//                            after the last one, on across the intervals; every out_interval FILE gets one line
+//                              enc step origin last_step n_updates on_from_encounter on_direct n_opened n_ended
+//                                  exp_reach exp_reactive exp_free_receptor n_overflow occ_reach occ_reactive
+//                                  occ_free_receptor n_censored_alive every slots
+//                            and per non-empty bin of the histograms since that origin
+//                              dwell step row bin count
+//                              react step row bin count             (row 0: ended in the bond, 1: otherwise)
 //           [--cf EVERY SMAX FILE]  cluster growth kinetics (kmc_cf_*, sizes clamped at SMAX): the
 //                            recorder begins where the process starts or resumes (a new origin,
 //                            as --kin's); an update after every piece of at most EVERY steps;
@@ -244,6 +264,8 @@ int main(int argc, char** argv) {
   int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0, geom_max = 0, sq_hmax = 0, sq_kmax = 0;
   double rdf_rmax = 0.0, dyn_rmax = 0.0;
   int64_t dyn_every = 0, kin_every = 0, cf_every = 0;
+  std::string reach_path, enc_path;
+  kmc_enc_config enc_cfg = {0, 0};
   int cf_smax = 0;
   kmc_lag_config lag_cfg;
   std::memset(&lag_cfg, 0, sizeof lag_cfg);
@@ -334,6 +356,17 @@ int main(int argc, char** argv) {
       dyn_path = next();
       if (dyn_every < 1 || !(dyn_rmax > 0.0) || dyn_nbins < 1 || dyn_nbins > KMC_TRACK_MAX_BINS) {
         fprintf(stderr, "kmc_run: bad --dyn %lld %g %d\n", (long long)dyn_every, dyn_rmax, dyn_nbins);
+        return 2;
+      }
+    }
+    else if (a == "--reach") {
+      reach_path = next();
+    }
+    else if (a == "--enc") {
+      enc_cfg.every = atoi(next().c_str());
+      enc_path = next();
+      if (enc_cfg.every < 1) {
+        fprintf(stderr, "kmc_run: bad --enc %d\n", enc_cfg.every);
         return 2;
       }
     }
@@ -454,6 +487,8 @@ int main(int argc, char** argv) {
     if (!pd_path.empty()) truncate(pd_path.c_str());
     if (!bd_path.empty()) truncate(bd_path.c_str());
     if (!pose_path.empty()) truncate(pose_path.c_str());
+    if (!reach_path.empty()) truncate(reach_path.c_str());
+    if (!enc_path.empty()) truncate(enc_path.c_str());
     rc = kmc_init_random(s);
     if (rc) return die(s, rc, "random placement");
   }
@@ -505,6 +540,11 @@ int main(int argc, char** argv) {
     rc = kmc_bd_begin(s, &bd_cfg);
     if (rc) return die(s, rc, "bd begin");
   }
+  int64_t enc_left = enc_cfg.every;
+  if (!enc_path.empty()) {
+    rc = kmc_enc_begin(s, &enc_cfg);
+    if (rc) return die(s, rc, "enc begin");
+  }
   int64_t step = kmc_current_step(s);
   while (step < p.simu_step) {
     int64_t next_out = (step / p.out_interval + 1) * p.out_interval;
@@ -512,7 +552,7 @@ int main(int argc, char** argv) {
     int64_t n = end - step;
     obs.resize((size_t)n);
     if (dyn_path.empty() && kin_path.empty() && cf_path.empty() && lag_path.empty() && rot_path.empty() &&
-        pd_path.empty() && bd_path.empty()) {
+        pd_path.empty() && bd_path.empty() && enc_path.empty()) {
       rc = kmc_step(s, n, obs.data());
       if (rc) return die(s, rc, "kmc_step");
     } else {
@@ -529,6 +569,7 @@ int main(int argc, char** argv) {
         if (!rot_path.empty() && rot_left < m) m = rot_left;
         if (!pd_path.empty() && pd_left < m) m = pd_left;
         if (!bd_path.empty() && bd_left < m) m = bd_left;
+        if (!enc_path.empty() && enc_left < m) m = enc_left;
         rc = kmc_step(s, m, obs.data() + done);
         if (rc) return die(s, rc, "kmc_step");
         done += m;
@@ -539,6 +580,12 @@ int main(int argc, char** argv) {
         rot_left -= m;
         pd_left -= m;
         bd_left -= m;
+        enc_left -= m;
+        if (!enc_path.empty() && enc_left == 0) {
+          rc = kmc_enc_update(s, nullptr);
+          if (rc) return die(s, rc, "enc update");
+          enc_left = enc_cfg.every;
+        }
         if (!dyn_path.empty() && (dyn_left == 0 || done == n)) {
           rc = kmc_track_update(s, nullptr);
           if (rc) return die(s, rc, "track update");
@@ -703,6 +750,58 @@ int main(int argc, char** argv) {
           for (int k = 0; k < dyn_nbins; ++k)
             if (vh[(size_t)c * dyn_nbins + k])
               fprintf(f, "vh %lld %d %d %lld\n", (long long)step, c, k, (long long)vh[(size_t)c * dyn_nbins + k]);
+        fclose(f);
+      }
+      if (!reach_path.empty()) {
+        const int nd = 16, na = 18;
+        kmc_reach_out r;
+        std::vector<int64_t> hd((size_t)3 * 2 * nd), harl((size_t)na * na), hacis((size_t)2 * na);
+        rc = kmc_reach_census(s, nd, na, &r, hd.data(), harl.data(), hacis.data());
+        if (rc) return die(s, rc, "reach census");
+        f = fopen(reach_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, reach_path.c_str());
+        for (int c = 0; c < 3; ++c)
+          fprintf(f, "reach %lld %d %lld %lld\n", (long long)step, c, (long long)r.n_reach[c], (long long)r.n_reactive[c]);
+        fprintf(f, "reachrl %lld %lld %lld %lld %lld %lld\n", (long long)step, (long long)r.rl_free_receptors,
+                (long long)r.rl_free_sites, (long long)r.rl_receptors_in_reach, (long long)r.rl_sites_in_reach,
+                (long long)r.rl_max_partners);
+        for (int c = 0; c < 3; ++c)
+          for (int x = 0; x < 2; ++x)
+            for (int k = 0; k < nd; ++k)
+              if (hd[(size_t)(c * 2 + x) * nd + k])
+                fprintf(f, "rd %lld %d %d %d %lld\n", (long long)step, c, x, k, (long long)hd[(size_t)(c * 2 + x) * nd + k]);
+        for (int i = 0; i < na; ++i)
+          for (int j = 0; j < na; ++j)
+            if (harl[(size_t)i * na + j])
+              fprintf(f, "ra %lld %d %d %lld\n", (long long)step, i, j, (long long)harl[(size_t)i * na + j]);
+        for (int c = 0; c < 2; ++c)
+          for (int k = 0; k < na; ++k)
+            if (hacis[(size_t)c * na + k])
+              fprintf(f, "rc %lld %d %d %lld\n", (long long)step, c, k, (long long)hacis[(size_t)c * na + k]);
+        fclose(f);
+      }
+      if (!enc_path.empty()) {
+        kmc_enc_out k;
+        std::vector<int64_t> dwell((size_t)KMC_ENC_HISTS * KMC_ENC_BINS), react((size_t)2 * KMC_ENC_BINS);
+        rc = kmc_enc_sample(s, &k, dwell.data(), react.data());
+        if (rc) return die(s, rc, "enc sample");
+        f = fopen(enc_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, enc_path.c_str());
+        const int64_t fields[] = {k.origin_step, k.last_step, k.n_updates, k.on_from_encounter, k.on_direct, k.n_opened,
+                                  k.n_ended, k.exp_reach, k.exp_reactive, k.exp_free_receptor, k.n_overflow,
+                                  k.occ_reach, k.occ_reactive, k.occ_free_receptor, k.n_censored_alive, k.every,
+                                  k.slots};
+        fprintf(f, "enc %lld", (long long)step);
+        for (int64_t x : fields) fprintf(f, " %lld", (long long)x);
+        fputc('\n', f);
+        for (int r = 0; r < KMC_ENC_HISTS; ++r)
+          for (int b = 0; b < KMC_ENC_BINS; ++b)
+            if (dwell[(size_t)r * KMC_ENC_BINS + b])
+              fprintf(f, "dwell %lld %d %d %lld\n", (long long)step, r, b, (long long)dwell[(size_t)r * KMC_ENC_BINS + b]);
+        for (int r = 0; r < 2; ++r)
+          for (int b = 0; b < KMC_ENC_BINS; ++b)
+            if (react[(size_t)r * KMC_ENC_BINS + b])
+              fprintf(f, "react %lld %d %d %lld\n", (long long)step, r, b, (long long)react[(size_t)r * KMC_ENC_BINS + b]);
         fclose(f);
       }
       if (!kin_path.empty()) {

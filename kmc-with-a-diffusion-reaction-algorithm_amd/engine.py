@@ -198,6 +198,21 @@ def load_library(path: Optional[str] = None):
                                       C.c_void_p]
     L.kmc_host_ligand_pose.argtypes = [P(capi.Params), P(capi.StateView), C.c_int32, C.c_int32, C.c_void_p,
                                        P(capi.PoseOut)]
+    L.kmc_reach_census.argtypes = [C.c_void_p, C.c_int32, C.c_int32, P(capi.ReachOut), C.c_void_p, C.c_void_p,
+                                   C.c_void_p]
+    L.kmc_enc_begin.argtypes = [C.c_void_p, P(capi.EncConfig)]
+    L.kmc_enc_update.argtypes = [C.c_void_p, P(capi.EncOut)]
+    L.kmc_enc_sample.argtypes = [C.c_void_p, P(capi.EncOut), C.c_void_p, C.c_void_p]
+    L.kmc_enc_arrays.argtypes = [C.c_void_p, P(capi.EncView)]
+    L.kmc_enc_end.argtypes = [C.c_void_p]
+    L.kmc_enc_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
+    L.kmc_host_reach_census.argtypes = [P(capi.Params), P(capi.StateView), C.c_int32, C.c_int32, P(capi.ReachOut),
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
+    L.kmc_host_enc_begin.argtypes = [P(capi.Params), P(capi.StateView), P(capi.EncConfig), P(capi.EncView),
+                                     P(capi.EncOut), C.c_void_p]
+    L.kmc_host_enc_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.EncView), P(capi.EncOut), C.c_void_p]
+    L.kmc_host_enc_sample.argtypes = [P(capi.Params), P(capi.EncView), P(capi.EncOut), C.c_void_p, P(capi.EncOut),
+                                      C.c_void_p, C.c_void_p]
     for f in ("kmc_host_math", "kmc_device_math"):
         getattr(L, f).argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
@@ -385,6 +400,62 @@ def host_rings(params: capi.Params, hs: capi.HostState, max_len: int = 8, member
     rc, res = _rings_call(load_library().kmc_host_rings, (C.byref(params), C.byref(v)), params.n_b, max_len, members)
     _host_check(rc)
     return res
+
+
+def _reach_call(f, head, nd, na):
+    """One kmc_reach_census / kmc_host_reach_census call: rc and (capi.ReachOut, hist_d[3, 2, nd], hist_a_rl[na, na],
+    hist_a_cis[2, na], int64)."""
+    ok = 1 <= nd <= capi.REACH_MAX_ND and 1 <= na <= capi.REACH_MAX_NA
+    out = capi.ReachOut()
+    hist_d = np.zeros((3, 2, nd) if ok else (1,), dtype=np.int64)
+    hist_a_rl = np.zeros((na, na) if ok else (1,), dtype=np.int64)
+    hist_a_cis = np.zeros((2, na) if ok else (1,), dtype=np.int64)
+    rc = f(*head, int(nd), int(na), C.byref(out), hist_d.ctypes.data, hist_a_rl.ctypes.data, hist_a_cis.ctypes.data)
+    return rc, (out, hist_d, hist_a_rl, hist_a_cis)
+
+
+def host_reach_census(params: capi.Params, hs: capi.HostState, nd: int = 16, na: int = 18):
+    """The reach census of a host state, sequentially (kmc_host_reach_census): as Simulation.reach_census."""
+    v = hs.view()
+    rc, res = _reach_call(load_library().kmc_host_reach_census, (C.byref(params), C.byref(v)), nd, na)
+    _host_check(rc)
+    return res
+
+
+class HostEnc:
+    """The encounter recorder on host states, sequentially (kmc_host_enc_*): Simulation.enc_*'s counterpart
+    without a device.  The recorder begins at hs; update(hs) advances it to a later state of the trajectory."""
+
+    def __init__(self, params: capi.Params, hs: capi.HostState, cfg: capi.EncConfig = None):
+        self.params = params
+        self.arrays = capi.EncArrays(params.n_a)
+        self.acc = capi.EncOut()
+        self.hist = np.zeros((capi.ENC_HISTS - 1 + 2, capi.ENC_BINS), dtype=np.int64)
+        cfg = cfg if cfg is not None else capi.enc_config(1)
+        v = hs.view()
+        _host_check(load_library().kmc_host_enc_begin(C.byref(params), C.byref(v), C.byref(cfg),
+                                                      C.byref(self.arrays.view()), C.byref(self.acc),
+                                                      self.hist.ctypes.data))
+
+    def update(self, hs: capi.HostState) -> capi.EncOut:
+        """Advance the recorder to hs (kmc_host_enc_update); returns the counters as of this update."""
+        v = hs.view()
+        _host_check(load_library().kmc_host_enc_update(C.byref(self.params), C.byref(v),
+                                                       C.byref(self.arrays.view()), C.byref(self.acc),
+                                                       self.hist.ctypes.data))
+        out = capi.EncOut()
+        C.memmove(C.byref(out), C.byref(self.acc), C.sizeof(out))
+        return out
+
+    def sample(self) -> capi.EncSample:
+        """capi.EncSample as of the last update — kmc_host_enc_sample."""
+        out = capi.EncOut()
+        hist = np.zeros((capi.ENC_HISTS, capi.ENC_BINS), dtype=np.int64)
+        react = np.zeros((2, capi.ENC_BINS), dtype=np.int64)
+        _host_check(load_library().kmc_host_enc_sample(C.byref(self.params), C.byref(self.arrays.view()),
+                                                       C.byref(self.acc), self.hist.ctypes.data, C.byref(out),
+                                                       hist.ctypes.data, react.ctypes.data))
+        return capi.EncSample(out, hist, react)
 
 
 class HostKinetics:
@@ -1274,6 +1345,67 @@ class Simulation:
         out = capi.PoseOut()
         self._check(load_library().kmc_ligand_pose(self._h, int(nz), int(nc), hist.ctypes.data, C.byref(out)))
         return hist, out
+
+    # ---- encounter statistics (kmc_encounter.hip)
+    def reach_census(self, nd: int = 16, na: int = 18):
+        """(capi.ReachOut, hist_d[3, 2, nd], hist_a_rl[na, na], hist_a_cis[2, na]) of the current state: the R–L
+        triples and cis pairs within the engine's reaction distance, by channel (RL, MONO, CX), reactive flag and
+        distance bin, and over the gate angles (kmc_reach_census); analysis.reach_factors post-processes them."""
+        rc, res = _reach_call(load_library().kmc_reach_census, (self._h,), nd, na)
+        self._check(rc)
+        return res
+
+    def enc_begin(self, cfg: capi.EncConfig = None) -> None:
+        """Start the R–L encounter recorder at the current state: the encounters that are open are left-censored."""
+        cfg = cfg if cfg is not None else capi.enc_config(1)
+        self._check(load_library().kmc_enc_begin(self._h, C.byref(cfg)))
+
+    def enc_update(self) -> capi.EncOut:
+        """Record the encounters that opened, continued or ended since the last update; due exactly cfg.every steps
+        after it."""
+        out = capi.EncOut()
+        self._check(load_library().kmc_enc_update(self._h, C.byref(out)))
+        return out
+
+    def enc_sample(self) -> capi.EncSample:
+        """capi.EncSample of the recorder as of the last update — kmc_enc_sample; analysis.encounter_rates and
+        analysis.escape_probability post-process it."""
+        out = capi.EncOut()
+        hist = np.zeros((capi.ENC_HISTS, capi.ENC_BINS), dtype=np.int64)
+        react = np.zeros((2, capi.ENC_BINS), dtype=np.int64)
+        self._check(load_library().kmc_enc_sample(self._h, C.byref(out), hist.ctypes.data, react.ctypes.data))
+        return capi.EncSample(out, hist, react)
+
+    def enc_arrays(self) -> capi.EncArrays:
+        """The recorder's per-receptor arrays by reference index (kmc_enc_arrays): diagnostics and tests."""
+        a = capi.EncArrays(self.params.n_a)
+        self._check(load_library().kmc_enc_arrays(self._h, C.byref(a.view())))
+        return a
+
+    def enc_end(self) -> None:
+        self._check(load_library().kmc_enc_end(self._h))
+
+    @property
+    def enc_phase_ms(self):
+        """Device milliseconds of the last reach_census / enc_begin / enc_update: (binning and the distance walk,
+        the gates, the rest)."""
+        ms = (C.c_double * 3)()
+        load_library().kmc_enc_phase_ms(self._h, ms)
+        return tuple(float(x) for x in ms)
+
+    def run_encounters(self, nsteps: int, every: int = 1):
+        """Advance nsteps steps (a multiple of every) in pieces of `every` steps with an enc_update after each.
+        The recorder must have been begun with that `every`.  Returns (records[nsteps], the last update's
+        capi.EncOut or None)."""
+        if nsteps < 0 or every < 1 or nsteps % every:
+            raise ValueError("run_encounters: nsteps >= 0 a multiple of every >= 1")
+        recs = np.zeros(nsteps, dtype=capi.OBS_DTYPE)
+        done, out = 0, None
+        while done < nsteps:
+            self.step(every, recs[done:done + every])
+            done += every
+            out = self.enc_update()
+        return recs, out
 
     @property
     def current_step(self) -> int:
