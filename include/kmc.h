@@ -237,7 +237,7 @@ int kmc_host_census(const kmc_params* p, const kmc_state_view* v, int32_t* label
                     int64_t* hist, kmc_census* out);
 /* Device milliseconds of the last kmc_components / kmc_oligomer_census /
  * kmc_pair_counts / kmc_track_* / kmc_kin_* / kmc_cf_* / kmc_unwrap / kmc_cluster_* / kmc_structure_factor /
- * kmc_bond_order / kmc_bond_order_corr / kmc_network / kmc_rings / kmc_reach_census / kmc_enc_* call: HIP events on the handle's stream around
+ * kmc_bond_order / kmc_bond_order_corr / kmc_network / kmc_rings / kmc_reach_census / kmc_enc_* / kmc_prox_clusters call: HIP events on the handle's stream around
  * its kernels and clears (the result copies to the host excluded); 0 before
  * the first. */
 double kmc_analysis_ms(const kmc_sim* s);
@@ -1621,6 +1621,113 @@ int kmc_host_enc_update(const kmc_params* p, const kmc_state_view* v, const kmc_
                         int64_t* hist10);
 int kmc_host_enc_sample(const kmc_params* p, const kmc_enc_view* view, const kmc_enc_out* acc, const int64_t* hist10,
                         kmc_enc_out* out, int64_t* hist, int64_t* react_hist);
+
+/* Proximity clusters: what localisation microscopy measures —
+ * DBSCAN / friends-of-friends clusters at a search radius eps, local neighbour
+ * counts and nearest-neighbour distances of the CURRENT state — and how well
+ * those clusters recover the bonded oligomers, as exact integers.  Like the
+ * other analyses the call reads the current state on the device (valid
+ * straight after kmc_set_state / kmc_load_*), launches nothing inside kmc_step,
+ * reads no step-internal table, leaves the state, the step counter, the
+ * recorders, kmc_get_clusters' validity and the other analyses' scratch
+ * untouched and is timed by kmc_analysis_ms; its scratch is its own (allocated
+ * by the first call, freed by kmc_destroy).
+ *
+ * Definitions — the device, kmc_host_prox_clusters and the tests share them bit
+ * for bit (doubles, no fused multiply-add; round = half away from zero):
+ *   position        (x, y) of bead [1][1], as in kmc_pair_counts.
+ *   integer coords  X = (int64) round(x * 1024.0), BX = (int64) round(box_x *
+ *                   1024.0); the same in y (§12's 2^-10 A).  KMC_ERR_ARG
+ *                   unless 1 <= BX, BY < 2^31.
+ *   displacement    i -> j: DX = (X_j - X_i) mod BX in [0, BX) (the floor
+ *                   modulus); if (2 DX >= BX) DX -= BX; the same in y;
+ *                   D2 = DX*DX + DY*DY in int64.
+ *   set             which = KMC_PX_A (receptors), KMC_PX_B (ligands) or
+ *                   KMC_PX_AB (both species as one point set); select =
+ *                   KMC_SK_ALL, or KMC_SK_BOUND: a receptor with nei2 != 0 or
+ *                   nei3 != 0, a ligand with any of nei2..4 != 0; mask: NULL
+ *                   keeps all, else n_a + n_b bytes by reference index (a
+ *                   ligand b at n_a + b), non-zero keeps the protein — the
+ *                   labelling efficiency.  The set is the intersection of the
+ *                   three; centres and neighbours both come from it.
+ *   neighbours      EPS = (int64) round(eps * 1024.0); every j != i of the set
+ *                   with D2 <= EPS^2 — an integer test, inclusive and
+ *                   symmetric.  Coincident points (D2 = 0) ARE neighbours here,
+ *                   unlike §14.  Needs eps > 0, EPS >= 1, floor(BX / EPS) >= 3
+ *                   and floor(BY / EPS) >= 3 (integer division), else
+ *                   KMC_ERR_ARG.  N_i = the number of neighbours, int32.
+ *   core            point i is a core iff N_i + 1 >= min_pts, 1 <= min_pts <=
+ *                   2^30.  min_pts = 1 makes every point a core: friends of
+ *                   friends.
+ *   cluster         a connected component of the cores under "is a neighbour".
+ *                   Its label is the smallest reference index among its cores,
+ *                   1-based and global (ligand b is n_a + b).
+ *   border          a non-core point with at least one core neighbour.  It
+ *                   joins the cluster of its nearest core: smallest D2, ties to
+ *                   the smaller reference index.  Textbook DBSCAN gives a border
+ *                   point to whichever cluster visits it first, so its result
+ *                   depends on the visiting order; this rule fixes the choice,
+ *                   is local to the point and independent of any order.
+ *   noise           any other selected point: label 0.
+ *   kind            kind[i] = 0 not in the set, 1 noise, 2 border, 3 core.
+ *   size histogram  size_hist[max_size + 1], 1 <= max_size <= 65535: clusters
+ *                   by member count (cores plus borders), counts above max_size
+ *                   clamped into the last bin; the bins sum to n_clusters.
+ *   neighbour hist  nn_hist[KMC_PX_NN_ROWS]: the selected points by min(N_i, 63).
+ *   nearest neighb. for every point with N_i > 0, M_i = min D2 over its
+ *                   neighbours.  nnd_hist[nbins], 1 <= nbins <= 4096: dr = eps
+ *                   / nbins, E_m = (int64) round(((double) m * dr) * 1024.0),
+ *                   bin k = #{m in 1..nbins-1 : E_m^2 <= M_i}.  The points with
+ *                   N_i = 0 are counted in n_alone instead.
+ *   summary         kmc_prox_out: n_sel, n_core, n_border, n_noise, n_alone,
+ *                   n_clusters; n_multi = clusters with >= 2 members; sum_nn =
+ *                   sum N_i (twice the pairs within eps); n_core_edges = the
+ *                   unordered core - core pairs within eps; max_size and
+ *                   max_label of the largest cluster, ties to the smallest
+ *                   label (0, 0 without a cluster).
+ *   purity          against the bond graph: c(i) = kmc_components' label of
+ *                   protein i over the WHOLE bond graph (ligands included even
+ *                   when the set is receptors only).  n_pure = clusters with
+ *                   >= 2 members whose members all have one c; n_whole = the
+ *                   pure clusters whose size equals the number of selected
+ *                   proteins carrying that c (the oligomers recovered exactly);
+ *                   n_bond_multi = bond components with >= 2 selected members;
+ *                   n_bond_kept = those whose selected members all carry the
+ *                   same non-zero proximity label.
+ *   per protein out label[N] (int32), nn[N] (int32), kind[N] (uint8) by
+ *                   reference index, N = n_a + n_b, zero for unselected
+ *                   proteins; a NULL pointer skips that copy, and each
+ *                   histogram may be NULL too.
+ * kmc_host_prox_clusters: the same from a host state view, sequentially on a
+ * cell grid of its own, no device.  kmc_prox_phase_ms: device milliseconds of
+ * the last call's four phases — select and bin; the count walk; the union walk
+ * and the flatten; the border walk, the bond components and the reduces.
+ * KMC_ERR_ARG for a null handle or out, an out-of-range argument, a handle
+ * without state and a decomposed window; KMC_ERR_STATE from the component
+ * labelling for a bond link that leaves the state.  Every device loop is
+ * bounded, and the number of launches is fixed whatever the clusters look
+ * like. */
+#define KMC_PX_A 0
+#define KMC_PX_B 1
+#define KMC_PX_AB 2
+#define KMC_PX_NN_ROWS 64
+#define KMC_PX_MAX_SIZE 65535
+#define KMC_PX_NND_BINS 4096
+typedef struct kmc_prox_out {
+  int64_t n_sel, n_core, n_border, n_noise, n_alone, n_clusters;
+  int64_t n_multi, sum_nn, n_core_edges;
+  int64_t n_pure, n_whole, n_bond_multi, n_bond_kept;
+  int32_t max_size, max_label;
+} kmc_prox_out;
+int kmc_prox_clusters(kmc_sim* s, int32_t which, int32_t select, const uint8_t* mask, double eps, int32_t min_pts,
+                      int32_t max_size, int32_t nbins, kmc_prox_out* out, int64_t* size_hist /* [max_size + 1] */,
+                      int64_t* nn_hist /* [KMC_PX_NN_ROWS] */, int64_t* nnd_hist /* [nbins] */, int32_t* label,
+                      int32_t* nn, uint8_t* kind);
+int kmc_host_prox_clusters(const kmc_params* p, const kmc_state_view* v, int32_t which, int32_t select,
+                           const uint8_t* mask, double eps, int32_t min_pts, int32_t max_size, int32_t nbins,
+                           kmc_prox_out* out, int64_t* size_hist, int64_t* nn_hist, int64_t* nnd_hist, int32_t* label,
+                           int32_t* nn, uint8_t* kind);
+int kmc_prox_phase_ms(const kmc_sim* s, double ms[4]);
 
 /* Formatting helpers shared by every host driver.  Each returns the number of
  * characters written (excluding NUL) or < 0. */

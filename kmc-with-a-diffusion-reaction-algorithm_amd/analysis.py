@@ -749,3 +749,64 @@ def body_survival(sample):
         c = np.array([[int(x) for x in row] for row in getattr(sample, "n_" + name)], dtype=np.float64)
         out[name] = np.divide(c, n, out=np.full((2, ms + 1), np.nan), where=n > 0)
     return out
+
+
+def prox_summary(out, size_hist) -> dict:
+    """The ratios of one prox_clusters result (a capi.ProxOut or its as_dict(), size_hist[max_size + 1]):
+    clustered = (cores + borders) / selected; mean_size (number-weighted) and mean_size_w (member-weighted:
+    sum s^2 n_s / sum s n_s) over the bins below the clamp bin, which mixes sizes; recovery = n_whole /
+    n_bond_multi, the bonded oligomers recovered exactly; over_merge = 1 - n_pure / n_multi, the clusters that mix
+    oligomers; over_split = 1 - n_bond_kept / n_bond_multi, the oligomers not kept in one cluster.  A zero
+    denominator gives nan."""
+    d = out if isinstance(out, dict) else out.as_dict()
+    h = np.asarray(size_hist, dtype=np.float64)
+    s = np.arange(h.size - 1, dtype=np.float64)
+    body = h[:-1]
+
+    def ratio(a, b):
+        return float(a) / float(b) if b else float("nan")
+
+    return dict(clustered=ratio(d["n_core"] + d["n_border"], d["n_sel"]),
+                mean_size=ratio(np.dot(s, body), body.sum()),
+                mean_size_w=ratio(np.dot(s * s, body), np.dot(s, body)),
+                recovery=ratio(d["n_whole"], d["n_bond_multi"]),
+                over_merge=1.0 - ratio(d["n_pure"], d["n_multi"]),
+                over_split=1.0 - ratio(d["n_bond_kept"], d["n_bond_multi"]))
+
+
+def nn_distance(nnd_hist, eps: float, out):
+    """(r, pdf, cdf, alone) from prox_clusters' nnd_hist[nbins]: r the bin centres (bin k covers [k dr, (k + 1) dr),
+    dr = eps / nbins, the last bin closed at eps), pdf the density of the nearest-neighbour distance among the
+    points that have a neighbour within eps (it integrates to 1; zeros when there is none), cdf its integral at the
+    upper bin edges, alone = n_alone / n_sel, the points without one (nan for an empty set)."""
+    h = np.asarray(nnd_hist, dtype=np.float64)
+    d = out if isinstance(out, dict) else out.as_dict()
+    if h.ndim != 1 or h.size < 1 or not eps > 0:
+        raise ValueError("nn_distance: nnd_hist is [nbins], eps > 0")
+    dr = eps / h.size
+    r = (np.arange(h.size, dtype=np.float64) + 0.5) * dr
+    tot = h.sum()
+    pdf = h / (tot * dr) if tot > 0 else np.zeros_like(h)
+    cdf = np.cumsum(h) / tot if tot > 0 else np.zeros_like(h)
+    alone = d["n_alone"] / d["n_sel"] if d["n_sel"] else float("nan")
+    return r, pdf, cdf, alone
+
+
+def ripley(counts, which, p, r_max: float):
+    """(r, K, L, H) from kmc_pair_counts' histogram: Ripley's K(r) = area / pairs * #{ordered pairs closer than r} at
+    the upper bin edges r, with area = box_x * box_y, the unordered AA / BB counts doubled over pairs = n (n - 1),
+    the AB counts over n_a n_b; L = sqrt(K / pi) and H = L - r (0 for an ideal gas, > 0 where points cluster).
+    Pure post-processing of the integers; nan without a pair."""
+    c = np.asarray(counts, dtype=np.float64)
+    which = capi.PAIRS[which] if isinstance(which, str) else int(which)
+    if c.ndim != 1 or c.size < 1 or not r_max > 0:
+        raise ValueError("ripley: counts is [nbins], r_max > 0")
+    if which == capi.PAIR_AB:
+        ordered, pairs = np.cumsum(c), float(p.n_a) * float(p.n_b)
+    else:
+        n = p.n_a if which == capi.PAIR_AA else p.n_b
+        ordered, pairs = 2.0 * np.cumsum(c), float(n) * float(n - 1)
+    r = np.arange(1, c.size + 1, dtype=np.float64) * (r_max / c.size)
+    K = p.box_x * p.box_y * ordered / pairs if pairs > 0 else np.full_like(c, np.nan)
+    L = np.sqrt(K / np.pi)
+    return r, K, L, L - r

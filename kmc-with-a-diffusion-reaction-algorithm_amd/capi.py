@@ -1174,6 +1174,37 @@ class EncSample:
         return cls(out, h, r)
 
 
+PX_A, PX_B, PX_AB = 0, 1, 2           # KMC_PX_A / KMC_PX_B / KMC_PX_AB (the point set of kmc_prox_clusters)
+PX_NN_ROWS = 64                       # KMC_PX_NN_ROWS: neighbour counts clamp into the last bin
+PX_MAX_SIZE, PX_NND_BINS = 65535, 4096  # KMC_PX_MAX_SIZE / KMC_PX_NND_BINS
+PX_WHICH = {"A": PX_A, "B": PX_B, "AB": PX_AB}
+
+
+def px_which(which) -> int:
+    """'A' / 'B' / 'AB' or the KMC_PX_* number itself."""
+    return PX_WHICH[which] if isinstance(which, str) else int(which)
+
+
+class ProxOut(C.Structure):
+    """kmc_prox_out — the counts of kmc_prox_clusters: the points by kind, the clusters, the pairs, the purity
+    against the bond graph and the largest cluster."""
+
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_sel", "n_core", "n_border", "n_noise", "n_alone", "n_clusters",
+        "n_multi", "sum_nn", "n_core_edges",
+        "n_pure", "n_whole", "n_bond_multi", "n_bond_kept")] + [("max_size", C.c_int32), ("max_label", C.c_int32)]
+
+    # the fields that add over replicas and successive calls (the largest cluster does not)
+    ADDITIVE = tuple(name for name, _ in _fields_[:13])
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+    def counts(self) -> np.ndarray:
+        """The additive fields as one int64 vector (analysis.reduce_counts)."""
+        return np.array([int(getattr(self, k)) for k in self.ADDITIVE], dtype=np.int64)
+
+
 class HostState:
     """numpy-backed kmc_state_view for n_a receptors and n_b ligands."""
 

@@ -29,6 +29,7 @@
 #include "kmc_pairdyn.hip"
 #include "kmc_bodydyn.hip"
 #include "kmc_encounter.hip"
+#include "kmc_proximity.hip"
 
 using namespace kmcd;
 
@@ -171,6 +172,7 @@ struct __attribute__((visibility("hidden"))) kmc_sim {
   PoseState pose;
   EncWalk ew;
   EncState enc;
+  PxState px;
   hipEvent_t an_ev[2] = {nullptr, nullptr};  // around the last analysis call's device work (kmc_analysis_ms)
   hipEvent_t bd_ev[2] = {nullptr, nullptr};  // after the components and after the reduction of the last kmc_bd_sample
   double bd_ms[3] = {0.0, 0.0, 0.0};         // its components, reduction and finish (kmc_bd_sample_ms)
@@ -541,6 +543,8 @@ int kmc_destroy(kmc_sim* s) {
   for (auto& e : s->an_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : s->ew.ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : s->px.ev)
     if (e) (void)hipEventDestroy(e);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
   if (s->ev_join) (void)hipEventDestroy(s->ev_join);

@@ -32,6 +32,7 @@
 #include "kmc_pairdyn.h"
 #include "kmc_params_check.h"
 #include "kmc_philox.h"
+#include "kmc_proximity.h"
 #include "kmc_rings.h"
 #include "kmc_state_hash.h"
 #include "kmc_structure.h"
@@ -1150,6 +1151,176 @@ int kmc_host_bond_order_corr(const kmc_params* p, const kmc_state_view* v, int32
       corr[k] += pc[i] * pc[j] + ps[i] * ps[j];
       corr[(size_t)nbins + k] += 1;
     });
+  return KMC_OK;
+}
+
+// Proximity clusters (include/kmc.h), sequential on the bond
+// order's cell grid (BoHost holds all n_a + n_b proteins by reference index):
+// the neighbour counts, a union-find over the core pairs in index order, the
+// border rule from each non-core's side, then the counts; c(i) is
+// kmc_host_census' label.  The expressions are kmc_proximity.h's.
+int kmc_host_prox_clusters(const kmc_params* p, const kmc_state_view* v, int32_t which, int32_t select,
+                           const uint8_t* mask, double eps, int32_t min_pts, int32_t max_size, int32_t nbins,
+                           kmc_prox_out* out, int64_t* size_hist, int64_t* nn_hist, int64_t* nnd_hist, int32_t* label,
+                           int32_t* nn, uint8_t* kind) {
+  if (!p || !v || !out || !v->a_int || !v->b_int || !v->ra || !v->rb || p->n_a < 0 || p->n_b < 0 || which < KMC_PX_A ||
+      which > KMC_PX_AB || (select != KMC_SK_ALL && select != KMC_SK_BOUND) || min_pts < 1 ||
+      min_pts > PX_MIN_PTS_MAX || max_size < 1 || max_size > PX_MAX_SIZE || nbins < 1 || nbins > PX_NND_BINS) {
+    g_host_err = "prox: params, state and out are needed, which 0..2, select 0 or 1, 1 <= min_pts <= 2^30, 1 <= max_size <= 65535, 1 <= nbins <= 4096";
+    return KMC_ERR_ARG;
+  }
+  const int na = p->n_a, nb = p->n_b, n = na + nb;
+  const double bx = kmcm::round_(p->box_x * 1024.0), by = kmcm::round_(p->box_y * 1024.0);
+  if (!(bx >= 1.0) || !(by >= 1.0) || !(bx < (double)BO_BOX_MAX) || !(by < (double)BO_BOX_MAX)) {
+    g_host_err = "prox: the box is below 2^-10 A or not below 2^21 A";
+    return KMC_ERR_ARG;
+  }
+  BoHost h;
+  h.n = n;
+  h.B[0] = (int64_t)bx;
+  h.B[1] = (int64_t)by;
+  const int64_t EPS = eps > 0.0 && eps * 1024.0 < (double)BO_BOX_MAX ? (int64_t)kmcm::round_(eps * 1024.0) : 0;
+  if (EPS < 1 || h.B[0] / EPS < 3 || h.B[1] / EPS < 3) {
+    g_host_err = "prox: eps must be at least 2^-10 A and at most a third of the box (3 cells along an axis)";
+    return KMC_ERR_ARG;
+  }
+  std::vector<int32_t> c((size_t)n, 0);
+  kmc_census census;
+  const int rc = kmc_host_census(p, v, c.data(), 0, 0, nullptr, &census);
+  if (rc != KMC_OK) return rc;
+  h.sel.assign((size_t)n, 0);
+  h.X.resize((size_t)n);
+  h.Y.resize((size_t)n);
+  std::vector<int32_t> who;
+  for (int i = 0; i < n; ++i) {
+    bool sel;
+    if (i < na) {
+      h.X[i] = (int64_t)kmcm::round_(v->ra[RA(na, 1, 1, 0, i)] * 1024.0);
+      h.Y[i] = (int64_t)kmcm::round_(v->ra[RA(na, 1, 1, 1, i)] * 1024.0);
+      sel = which != KMC_PX_B &&
+            (select == KMC_SK_ALL || v->a_int[2 * (size_t)na + i] != 0 || v->a_int[4 * (size_t)na + i] != 0);
+    } else {
+      const int b = i - na;
+      h.X[i] = (int64_t)kmcm::round_(v->rb[RB(nb, 1, 1, 0, b)] * 1024.0);
+      h.Y[i] = (int64_t)kmcm::round_(v->rb[RB(nb, 1, 1, 1, b)] * 1024.0);
+      bool bound = false;
+      for (int j = 2; j <= 4; ++j) bound = bound || v->b_int[(size_t)(4 + j - 1) * nb + b] != 0;
+      sel = which != KMC_PX_A && (select == KMC_SK_ALL || bound);
+    }
+    if (sel && mask) sel = mask[i] != 0;
+    h.sel[i] = sel;
+    if (sel) who.push_back(i);
+  }
+  BoCells g;
+  g.build(h, who, (int)std::min<int64_t>(h.B[0] / EPS, BO_NC_MAX), (int)std::min<int64_t>(h.B[1] / EPS, BO_NC_MAX));
+  const int64_t EPS2 = EPS * EPS;
+  auto dist2 = [&](int i, int j) {
+    const int64_t DX = kmcb::fold(h.X[j] - h.X[i], h.B[0]), DY = kmcb::fold(h.Y[j] - h.Y[i], h.B[1]);
+    return DX * DX + DY * DY;
+  };
+  std::vector<int32_t> N((size_t)n, 0), lab((size_t)n, 0), parent((size_t)n);
+  std::vector<int64_t> M((size_t)n, 0);
+  std::vector<uint8_t> kd((size_t)n, 0);
+  for (int i : who) {
+    int64_t best = INT64_MAX;
+    g.around(h, i, [&](int j) {
+      if (j == i) return;
+      const int64_t D2 = dist2(i, j);
+      if (D2 > EPS2) return;
+      N[i] += 1;
+      best = std::min(best, D2);
+    });
+    M[i] = N[i] ? best : 0;
+    kd[i] = kmcx::is_core(N[i], min_pts) ? 3 : 1;
+  }
+  for (int i = 0; i < n; ++i) parent[i] = i;
+  auto find = [&](int x) {
+    while (parent[x] != x) x = parent[x] = parent[parent[x]];
+    return x;
+  };
+  std::memset(out, 0, sizeof *out);
+  for (int i : who) {
+    if (kd[i] != 3) continue;
+    g.around(h, i, [&](int j) {
+      if (j >= i || kd[j] != 3 || dist2(i, j) > EPS2) return;
+      out->n_core_edges += 1;
+      const int a = find(i), b = find(j);
+      if (a != b) parent[std::max(a, b)] = std::min(a, b);
+    });
+  }
+  for (int i : who)
+    if (kd[i] == 3) lab[i] = find(i) + 1;
+  for (int i : who) {
+    if (kd[i] == 3 || N[i] == 0) continue;
+    int64_t bestD = 0;
+    int32_t bestR = -1;
+    g.around(h, i, [&](int j) {
+      if (j == i || kd[j] != 3) return;
+      const int64_t D2 = dist2(i, j);
+      if (D2 > EPS2 || !kmcx::nearer(D2, j, bestD, bestR)) return;
+      bestD = D2;
+      bestR = j;
+    });
+    if (bestR >= 0) {
+      kd[i] = 2;
+      lab[i] = lab[bestR];
+    }
+  }
+  const double dr = eps / nbins;
+  std::vector<int64_t> E2((size_t)nbins);
+  for (int m = 0; m < nbins; ++m) {
+    const int64_t e = kmcb::corr_edge(m, dr);
+    E2[m] = e * e;
+  }
+  const double inv = 1.0 / (dr * 1024.0);
+  if (size_hist) std::fill(size_hist, size_hist + (size_t)max_size + 1, (int64_t)0);
+  if (nn_hist) std::fill(nn_hist, nn_hist + KMC_PX_NN_ROWS, (int64_t)0);
+  if (nnd_hist) std::fill(nnd_hist, nnd_hist + nbins, (int64_t)0);
+  // by root (a cluster's label - 1, a component's c - 1): members and the ranges purity is read from
+  std::vector<int32_t> cnt((size_t)n, 0), cmin((size_t)n, INT32_MAX), cmax((size_t)n, -1), pmin((size_t)n, INT32_MAX),
+      pmax((size_t)n, -1), bsel((size_t)n, 0);
+  for (int i : who) {
+    out->n_sel += 1;
+    (kd[i] == 3 ? out->n_core : kd[i] == 2 ? out->n_border : out->n_noise) += 1;
+    out->sum_nn += N[i];
+    if (nn_hist) nn_hist[std::min<int32_t>(N[i], KMC_PX_NN_ROWS - 1)] += 1;
+    if (N[i] == 0) out->n_alone += 1;
+    else if (nnd_hist) nnd_hist[kmcx::nnd_bin(E2.data(), nbins, M[i], (int)(std::sqrt((double)M[i]) * inv))] += 1;
+    const int ci = c[i] - 1, L = lab[i];
+    bsel[ci] += 1;
+    pmin[ci] = std::min(pmin[ci], L);
+    pmax[ci] = std::max(pmax[ci], L);
+    if (L > 0) {
+      cnt[L - 1] += 1;
+      cmin[L - 1] = std::min(cmin[L - 1], ci);
+      cmax[L - 1] = std::max(cmax[L - 1], ci);
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    if (kd[i] == 3 && lab[i] == i + 1) {
+      const int size = cnt[i];
+      if (size_hist) size_hist[std::min(size, (int)max_size)] += 1;
+      out->n_clusters += 1;
+      if (size > out->max_size) {  // (roots come in label order: the first of a size keeps the tie)
+        out->max_size = size;
+        out->max_label = i + 1;
+      }
+      if (size >= 2) {
+        out->n_multi += 1;
+        if (cmin[i] == cmax[i]) {
+          out->n_pure += 1;
+          if (bsel[cmin[i]] == size) out->n_whole += 1;
+        }
+      }
+    }
+    if (bsel[i] >= 2) {
+      out->n_bond_multi += 1;
+      if (pmin[i] == pmax[i] && pmin[i] > 0) out->n_bond_kept += 1;
+    }
+  }
+  if (label) std::copy(lab.begin(), lab.end(), label);
+  if (nn) std::copy(N.begin(), N.end(), nn);
+  if (kind) std::copy(kd.begin(), kd.end(), kind);
   return KMC_OK;
 }
 

@@ -1,6 +1,6 @@
 // kmc_observe.hip — the host side of the read-only layers over the committed
-// state (DESIGN.md §10-§21): their C-ABI calls, one section a layer, over the
-// kernels and the state structs of kmc_analysis.hip ... kmc_bodydyn.hip.  Nothing
+// state (DESIGN.md §10-§23): their C-ABI calls, one section a layer, over the
+// kernels and the state structs of kmc_analysis.hip ... kmc_proximity.hip.  Nothing
 // here writes a buffer a step reads, so the trajectory, the step counter and
 // clusters_valid stay as they are.
 //
@@ -2597,6 +2597,206 @@ int kmc_enc_arrays(kmc_sim* s, const kmc_enc_view* v) {
 
 int kmc_enc_end(kmc_sim* s) {
   return s ? rec_end(s, s->enc) : KMC_ERR_ARG;
+}
+
+// ---------------------------------------------------------------- proximity clusters
+// kmc_proximity.hip: read-only like the bond order above, on scratch of its own.
+// A fixed sequence of launches whatever the clusters look like: init, the bond
+// components, the binning, the count walk, the union walk, the flatten, the
+// border walk, the two reduces; the stream is waited for once, at the end.
+
+static_assert(KMC_PX_NN_ROWS == PX_NN_ROWS && KMC_PX_MAX_SIZE == PX_MAX_SIZE && KMC_PX_NND_BINS == PX_NND_BINS,
+              "kmc.h and kmc_proximity.h agree");
+static_assert(sizeof(kmc_prox_out) == 13 * sizeof(int64_t) + 2 * sizeof(int32_t), "kmc_prox_out layout");
+
+// the scratch of the first call: 91 bytes per protein, 12 per cell of the grid in use, 0.5 MiB of bins
+static int px_reserve(kmc_sim* s) {
+  PxState& X = s->px;
+  if (X.out) return KMC_OK;
+  const size_t N = (size_t)s->K.N;
+  // debug: the union walk flushes its queue at fewer pairs
+  X.q = (int)int_getenv("KMC_DEBUG_PX_QUEUE", 64, 1, 64);
+  for (auto& e : X.ev)
+    if (!e) HIPCHK(s, hipEventCreate(&e));
+  int rc = KMC_OK;
+  rc |= dalloc(s, &X.cell, N);
+  rc |= dalloc(s, &X.rank, N);
+  rc |= dalloc(s, &X.pts, N);
+  rc |= dalloc(s, &X.ref, N);
+  rc |= dalloc(s, &X.clist, N);
+  rc |= dalloc(s, &X.blist, N);
+  rc |= dalloc(s, &X.core_s, N);
+  rc |= dalloc(s, &X.kind, N);
+  rc |= dalloc(s, &X.mask, N);
+  rc |= dalloc(s, &X.nn, N);
+  rc |= dalloc(s, &X.parent, N);
+  rc |= dalloc(s, &X.label, N);
+  rc |= dalloc(s, &X.cnt, N);
+  rc |= dalloc(s, &X.M, N);
+  rc |= dalloc(s, &X.cparent, N);
+  rc |= dalloc(s, &X.clab, N);
+  rc |= dalloc(s, &X.cmin, N);
+  rc |= dalloc(s, &X.cmax, N);
+  rc |= dalloc(s, &X.pmin, N);
+  rc |= dalloc(s, &X.pmax, N);
+  rc |= dalloc(s, &X.bsel, N);
+  rc |= dalloc(s, &X.size_hist, (size_t)PX_MAX_SIZE + 1);
+  rc |= dalloc(s, &X.nn_hist, (size_t)PX_NN_ROWS);
+  rc |= dalloc(s, &X.nnd_hist, (size_t)PX_NND_BINS);
+  rc |= dalloc(s, &X.E2, (size_t)PX_NND_BINS);
+  rc |= dalloc(s, &X.an_out, 1);
+  if (rc == KMC_OK) rc = dalloc(s, &X.out, 1);  // (the last: set when all the others are)
+  if (rc != KMC_OK) {
+    dfree(s, X.cell), dfree(s, X.rank), dfree(s, X.pts), dfree(s, X.ref), dfree(s, X.clist), dfree(s, X.blist);
+    dfree(s, X.core_s), dfree(s, X.kind), dfree(s, X.mask), dfree(s, X.nn), dfree(s, X.parent), dfree(s, X.label);
+    dfree(s, X.cnt), dfree(s, X.M), dfree(s, X.cparent), dfree(s, X.clab), dfree(s, X.cmin), dfree(s, X.cmax);
+    dfree(s, X.pmin), dfree(s, X.pmax), dfree(s, X.bsel), dfree(s, X.size_hist), dfree(s, X.nn_hist);
+    dfree(s, X.nnd_hist), dfree(s, X.E2), dfree(s, X.an_out);
+    return fail(s, KMC_ERR_HIP, "prox: scratch allocation failed");
+  }
+  return KMC_OK;
+}
+
+int kmc_prox_phase_ms(const kmc_sim* s, double ms[4]) {
+  if (!s || !ms) return KMC_ERR_ARG;
+  for (int k = 0; k < 4; ++k) ms[k] = s->px.ms[k];
+  return KMC_OK;
+}
+
+int kmc_prox_clusters(kmc_sim* s, int32_t which, int32_t select, const uint8_t* mask, double eps, int32_t min_pts,
+                      int32_t max_size, int32_t nbins, kmc_prox_out* out, int64_t* size_hist, int64_t* nn_hist,
+                      int64_t* nnd_hist, int32_t* label, int32_t* nn, uint8_t* kind) {
+  if (!s) return KMC_ERR_ARG;
+  if (!out || which < KMC_PX_A || which > KMC_PX_AB || (select != KMC_SK_ALL && select != KMC_SK_BOUND) ||
+      min_pts < 1 || min_pts > PX_MIN_PTS_MAX || max_size < 1 || max_size > PX_MAX_SIZE || nbins < 1 ||
+      nbins > PX_NND_BINS)
+    return fail(s, KMC_ERR_ARG, "prox: out is needed, which 0..2, select 0 or 1, 1 <= min_pts <= 2^30, 1 <= max_size <= " +
+                                    std::to_string(PX_MAX_SIZE) + ", 1 <= nbins <= " + std::to_string(PX_NND_BINS));
+  int rc = an_check(s);
+  if (rc != KMC_OK) return rc;
+  const KParams& K = s->K;
+  const double bx = kmcm::round_(K.box_x * 1024.0), by = kmcm::round_(K.box_y * 1024.0);
+  if (!(bx >= 1.0) || !(by >= 1.0) || !(bx < (double)BO_BOX_MAX) || !(by < (double)BO_BOX_MAX))
+    return fail(s, KMC_ERR_ARG, "prox: the box is below 2^-10 A or not below 2^21 A");
+  BoArgs a;
+  a.which = which;
+  a.mode = a.fold = 0;
+  a.select = select;
+  a.base = which == KMC_PX_B ? K.NA : 0;
+  a.n = which == KMC_PX_A ? K.NA : which == KMC_PX_B ? K.NB : K.N;
+  a.BX = (long long)bx;
+  a.BY = (long long)by;
+  const long long EPS = eps > 0.0 && eps * 1024.0 < (double)BO_BOX_MAX ? (long long)kmcm::round_(eps * 1024.0) : 0;
+  if (EPS < 1 || a.BX / EPS < 3 || a.BY / EPS < 3)
+    return fail(s, KMC_ERR_ARG, "prox: eps must be at least 2^-10 A and at most a third of the box (3 cells along an axis)");
+  a.RC2 = EPS * EPS;
+  a.ncx = (int)std::min<long long>(a.BX / EPS, BO_NC_MAX);
+  a.ncy = (int)std::min<long long>(a.BY / EPS, BO_NC_MAX);
+  rc = px_reserve(s);
+  if (rc != KMC_OK) return rc;
+  PxState& X = s->px;
+  const size_t ncnt = (size_t)a.ncx * a.ncy + 1;  // the scan's last entry is the number of binned points
+  rc = bins_reserve(s, X.bins, ncnt, "prox");
+  if (rc != KMC_OK) return rc;
+  const int N = K.N;
+  const double dr = eps / nbins;
+  PxArgs x;
+  x.min_pts = min_pts;
+  x.max_size = max_size;
+  x.nbins = nbins;
+  x.N = N;
+  x.inv_dr = (float)(1.0 / (dr * 1024.0));
+  std::vector<int64_t> E2((size_t)nbins);
+  for (int m = 0; m < nbins; ++m) {
+    const int64_t e = kmcb::corr_edge(m, dr);
+    E2[m] = e * e;
+  }
+  hipStream_t st = s->stream;
+  rc = an_begin(s);
+  if (rc != KMC_OK) return rc;
+  HIPCHK(s, hipMemcpyAsync(X.E2, E2.data(), sizeof(int64_t) * E2.size(), hipMemcpyHostToDevice, st));
+  if (mask && N) HIPCHK(s, hipMemcpyAsync(X.mask, mask, (size_t)N, hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemsetAsync(X.out, 0, sizeof(PxOut), st));
+  HIPCHK(s, hipMemsetAsync(X.an_out, 0, sizeof(AnOut), st));
+  HIPCHK(s, hipMemsetAsync(X.size_hist, 0, sizeof(unsigned long long) * ((size_t)max_size + 1), st));
+  HIPCHK(s, hipMemsetAsync(X.nn_hist, 0, sizeof(unsigned long long) * PX_NN_ROWS, st));
+  HIPCHK(s, hipMemsetAsync(X.nnd_hist, 0, sizeof(unsigned long long) * (size_t)nbins, st));
+  HIPCHK(s, hipMemsetAsync(X.bins.ccnt, 0, sizeof(int32_t) * ncnt, st));
+  const unsigned gN = (unsigned)((N + PX_T - 1) / PX_T), gn = (unsigned)((a.n + PX_T - 1) / PX_T);
+  const unsigned gw = (unsigned)std::min<int64_t>(4 * PX_WG_MAX, ((int64_t)a.n + PX_T - 1) / PX_T);
+  const unsigned gr = (unsigned)std::min<int64_t>(PX_WG_MAX, ((int64_t)N + PX_T - 1) / PX_T);
+  // bin
+  if (gN) k_px_init<<<gN, PX_T, 0, st>>>(N, X.parent, X.cparent, X.nn, X.kind, X.label, X.cnt, X.cmin, X.cmax, X.pmin,
+                                         X.pmax, X.bsel);
+  if (gn) k_px_cell_count<<<gn, PX_T, 0, st>>>(s->K, s->d, a, mask ? X.mask : nullptr, X.bins.ccnt, X.cell, X.rank, X.out);
+  bins_scan(s, X.bins.ccnt, X.bins.cstart, (int)ncnt, X.bins.part);
+  if (gn) k_px_cell_scatter<<<gn, PX_T, 0, st>>>(s->K, s->d, a, X.bins.cstart, X.cell, X.rank, X.pts, X.ref);
+  HIPCHK(s, hipEventRecord(X.ev[0], st));
+  // count walk
+  if (gn)
+    k_px_count<<<gw, PX_T, 0, st>>>(a, x, X.bins.cstart, X.pts, X.ref, X.nn, X.M, X.kind, X.core_s, X.clist, X.blist,
+                                    X.out);
+  HIPCHK(s, hipEventRecord(X.ev[1], st));
+  // union + flatten
+  if (gn) {
+    k_px_union<<<gw, PX_T, 0, st>>>(a, x, X.q, X.bins.cstart, X.pts, X.ref, X.core_s, X.clist, X.parent, X.out);
+    k_px_flatten<<<gN, PX_T, 0, st>>>(N, X.kind, X.parent, X.label, X.out);
+  }
+  HIPCHK(s, hipEventRecord(X.ev[2], st));
+  // border + reduce (the bond components feed the reduce alone)
+  if (gN) {
+    k_an_hook<<<gN, AN_T, 0, st>>>(s->K, s->d, X.cparent, X.an_out);
+    k_an_flatten<<<gN, AN_T, 0, st>>>(X.cparent, X.clab, N, X.an_out);
+  }
+  if (gn) {
+    k_px_border<<<gw, PX_T, 0, st>>>(a, X.bins.cstart, X.pts, X.ref, X.core_s, X.blist, X.kind, X.label, X.out);
+    const size_t lds = sizeof(unsigned long long) * (size_t)(PX_NSUM + PX_NN_ROWS + nbins);
+    k_px_points<<<gr, PX_T, lds, st>>>(x, X.kind, X.nn, X.M, X.label, X.clab, X.E2, X.cnt, X.cmin, X.cmax, X.pmin, X.pmax,
+                                       X.bsel, X.nn_hist, X.nnd_hist, X.out);
+    k_px_roots<<<gr, PX_T, 0, st>>>(x, X.kind, X.label, X.cnt, X.cmin, X.cmax, X.pmin, X.pmax, X.bsel, X.size_hist, X.out);
+  }
+  HIPCHK(s, hipGetLastError());
+  rc = an_end(s);  // (waits: E2 and the mask are read by the copies until here)
+  if (rc != KMC_OK) return rc;
+  float t[4] = {0, 0, 0, 0};
+  HIPCHK(s, hipEventElapsedTime(&t[0], s->an_ev[0], X.ev[0]));
+  HIPCHK(s, hipEventElapsedTime(&t[1], X.ev[0], X.ev[1]));
+  HIPCHK(s, hipEventElapsedTime(&t[2], X.ev[1], X.ev[2]));
+  HIPCHK(s, hipEventElapsedTime(&t[3], X.ev[2], s->an_ev[1]));
+  for (int k = 0; k < 4; ++k) X.ms[k] = t[k];
+  PxOut o;
+  AnOut ao;
+  HIPCHK(s, hipMemcpy(&o, X.out, sizeof o, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipMemcpy(&ao, X.an_out, sizeof ao, hipMemcpyDeviceToHost));
+  if (ao.err) return fail(s, KMC_ERR_STATE, "prox: a bond link leaves the state or the link chains do not end");
+  if (o.err) return fail(s, KMC_ERR_STATE, "prox: a reference index or a union-find chain left its range");
+  std::memset(out, 0, sizeof *out);
+  out->n_sel = (int64_t)o.sum[PX_N_SEL];
+  out->n_core = (int64_t)o.sum[PX_N_CORE];
+  out->n_border = (int64_t)o.sum[PX_N_BORDER];
+  out->n_noise = (int64_t)o.sum[PX_N_NOISE];
+  out->n_alone = (int64_t)o.sum[PX_N_ALONE];
+  out->n_clusters = (int64_t)o.sum[PX_N_CLUSTERS];
+  out->n_multi = (int64_t)o.sum[PX_N_MULTI];
+  out->sum_nn = (int64_t)o.sum[PX_SUM_NN];
+  out->n_core_edges = (int64_t)o.sum[PX_N_EDGES];
+  out->n_pure = (int64_t)o.sum[PX_N_PURE];
+  out->n_whole = (int64_t)o.sum[PX_N_WHOLE];
+  out->n_bond_multi = (int64_t)o.sum[PX_N_BMULTI];
+  out->n_bond_kept = (int64_t)o.sum[PX_N_BKEPT];
+  if (o.best) {
+    out->max_size = (int32_t)(o.best >> 32);
+    out->max_label = (int32_t)(0xffffffffu - (uint32_t)o.best) + 1;
+  }
+  const size_t n = (size_t)N;
+  if (size_hist)
+    HIPCHK(s, hipMemcpy(size_hist, X.size_hist, sizeof(int64_t) * ((size_t)max_size + 1), hipMemcpyDeviceToHost));
+  if (nn_hist) HIPCHK(s, hipMemcpy(nn_hist, X.nn_hist, sizeof(int64_t) * PX_NN_ROWS, hipMemcpyDeviceToHost));
+  if (nnd_hist) HIPCHK(s, hipMemcpy(nnd_hist, X.nnd_hist, sizeof(int64_t) * (size_t)nbins, hipMemcpyDeviceToHost));
+  if (label && n) HIPCHK(s, hipMemcpy(label, X.label, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  if (nn && n) HIPCHK(s, hipMemcpy(nn, X.nn, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  if (kind && n) HIPCHK(s, hipMemcpy(kind, X.kind, n, hipMemcpyDeviceToHost));
+  return KMC_OK;
 }
 
 }  // extern "C"

@@ -40,6 +40,14 @@
 //                              step row bin count      (row = min(neighbours, 15), bin of |psi|)
 //                            and one line
 //                              step sum n_sel n_with sum_nn sum_pc sum_ps sum_m
+//           [--prox WHICH EPS MINPTS MAXSIZE FILE]  every out_interval, the proximity clusters of the
+//                            point set WHICH (A, B or AB) at the search radius EPS (kmc_prox_clusters,
+//                            KMC_SK_ALL, no mask; MINPTS >= 1, 1 <= MAXSIZE <= 65535), appended like the
+//                            census: per non-empty bin of the size histogram
+//                              step size count
+//                            and one line with kmc_prox_out's fields in their order
+//                              step sum n_sel n_core n_border n_noise n_alone n_clusters n_multi sum_nn
+//                                       n_core_edges n_pure n_whole n_bond_multi n_bond_kept max_size max_label
 //           [--rings MAXLEN FILE]  every out_interval, the rings of the ligand network of up to
 //                            MAXLEN bridges (kmc_rings; 1 <= MAXLEN <= 12), appended like the
 //                            census: one line
@@ -260,6 +268,9 @@ int main(int argc, char** argv) {
   std::string state_path, census_path, rdf_path, dyn_path, geom_path, sq_path, psi_path, kin_path, cf_path, rings_path, lag_path;
   int rings_max = 0;
   int psi_which = -1, psi_fold = 0, psi_nbins = 0;
+  std::string prox_path;
+  int prox_which = -1, prox_min_pts = 0, prox_max_size = 0;
+  double prox_eps = 0.0;
   double psi_rcut = 0.0;
   int rdf_which = -1, rdf_nbins = 0, dyn_nbins = 0, geom_max = 0, sq_hmax = 0, sq_kmax = 0;
   double rdf_rmax = 0.0, dyn_rmax = 0.0;
@@ -356,6 +367,19 @@ int main(int argc, char** argv) {
       dyn_path = next();
       if (dyn_every < 1 || !(dyn_rmax > 0.0) || dyn_nbins < 1 || dyn_nbins > KMC_TRACK_MAX_BINS) {
         fprintf(stderr, "kmc_run: bad --dyn %lld %g %d\n", (long long)dyn_every, dyn_rmax, dyn_nbins);
+        return 2;
+      }
+    }
+    else if (a == "--prox") {
+      const std::string w = next();
+      prox_which = w == "A" ? KMC_PX_A : w == "B" ? KMC_PX_B : w == "AB" ? KMC_PX_AB : -1;
+      prox_eps = atof(next().c_str());
+      prox_min_pts = atoi(next().c_str());
+      prox_max_size = atoi(next().c_str());
+      prox_path = next();
+      if (prox_which < 0 || !(prox_eps > 0.0) || prox_min_pts < 1 || prox_max_size < 1 ||
+          prox_max_size > KMC_PX_MAX_SIZE) {
+        fprintf(stderr, "kmc_run: bad --prox %s %g %d %d\n", w.c_str(), prox_eps, prox_min_pts, prox_max_size);
         return 2;
       }
     }
@@ -479,6 +503,7 @@ int main(int argc, char** argv) {
     if (!geom_path.empty()) truncate(geom_path.c_str());
     if (!sq_path.empty()) truncate(sq_path.c_str());
     if (!psi_path.empty()) truncate(psi_path.c_str());
+    if (!prox_path.empty()) truncate(prox_path.c_str());
     if (!rings_path.empty()) truncate(rings_path.c_str());
     if (!kin_path.empty()) truncate(kin_path.c_str());
     if (!cf_path.empty()) truncate(cf_path.c_str());
@@ -750,6 +775,24 @@ int main(int argc, char** argv) {
           for (int k = 0; k < dyn_nbins; ++k)
             if (vh[(size_t)c * dyn_nbins + k])
               fprintf(f, "vh %lld %d %d %lld\n", (long long)step, c, k, (long long)vh[(size_t)c * dyn_nbins + k]);
+        fclose(f);
+      }
+      if (!prox_path.empty()) {
+        kmc_prox_out px;
+        std::vector<int64_t> sizes((size_t)prox_max_size + 1);
+        rc = kmc_prox_clusters(s, prox_which, KMC_SK_ALL, nullptr, prox_eps, prox_min_pts, prox_max_size, 1, &px,
+                               sizes.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (rc) return die(s, rc, "prox clusters");
+        f = fopen(prox_path.c_str(), "ab");
+        if (!f) return die(s, KMC_ERR_IO, prox_path.c_str());
+        for (int k = 0; k <= prox_max_size; ++k)
+          if (sizes[(size_t)k]) fprintf(f, "%lld %d %lld\n", (long long)step, k, (long long)sizes[(size_t)k]);
+        const int64_t fields[] = {px.n_sel, px.n_core, px.n_border, px.n_noise, px.n_alone, px.n_clusters, px.n_multi,
+                                  px.sum_nn, px.n_core_edges, px.n_pure, px.n_whole, px.n_bond_multi, px.n_bond_kept,
+                                  px.max_size, px.max_label};
+        fprintf(f, "%lld sum", (long long)step);
+        for (int64_t x : fields) fprintf(f, " %lld", (long long)x);
+        fputc('\n', f);
         fclose(f);
       }
       if (!reach_path.empty()) {

@@ -213,6 +213,11 @@ def load_library(path: Optional[str] = None):
     L.kmc_host_enc_update.argtypes = [P(capi.Params), P(capi.StateView), P(capi.EncView), P(capi.EncOut), C.c_void_p]
     L.kmc_host_enc_sample.argtypes = [P(capi.Params), P(capi.EncView), P(capi.EncOut), C.c_void_p, P(capi.EncOut),
                                       C.c_void_p, C.c_void_p]
+    px = [C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32, P(capi.ProxOut)] + \
+        [C.c_void_p] * 6
+    L.kmc_prox_clusters.argtypes = [C.c_void_p] + px
+    L.kmc_host_prox_clusters.argtypes = [P(capi.Params), P(capi.StateView)] + px
+    L.kmc_prox_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
     for f in ("kmc_host_math", "kmc_device_math"):
         getattr(L, f).argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     _lib = L
@@ -418,6 +423,39 @@ def host_reach_census(params: capi.Params, hs: capi.HostState, nd: int = 16, na:
     """The reach census of a host state, sequentially (kmc_host_reach_census): as Simulation.reach_census."""
     v = hs.view()
     rc, res = _reach_call(load_library().kmc_host_reach_census, (C.byref(params), C.byref(v)), nd, na)
+    _host_check(rc)
+    return res
+
+
+def _prox_call(f, head, n, which, eps, min_pts, select, mask, max_size, nbins, per_protein):
+    """One kmc_prox_clusters / kmc_host_prox_clusters call: rc and (size_hist[max_size + 1], nn_hist[64],
+    nnd_hist[nbins] int64, capi.ProxOut) and, with per_protein, (label[n], nn[n] int32, kind[n] uint8) by reference
+    index; a size out of range gets the smallest buffer (the library refuses the call before it writes)."""
+    ok = 1 <= int(max_size) <= capi.PX_MAX_SIZE and 1 <= int(nbins) <= capi.PX_NND_BINS
+    size_hist = np.zeros(int(max_size) + 1 if ok else 1, dtype=np.int64)
+    nn_hist = np.zeros(capi.PX_NN_ROWS, dtype=np.int64)
+    nnd_hist = np.zeros(int(nbins) if ok else 1, dtype=np.int64)
+    out = capi.ProxOut()
+    label, nn, kind = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.shape != (n,):
+            raise ValueError("prox_clusters: mask has n_a + n_b entries, by reference index")
+    ptr = (lambda a: a.ctypes.data if per_protein and n else None)
+    rc = f(*head, capi.px_which(which), capi.sk_select(select), m.ctypes.data if m is not None and n else None,
+           float(eps), int(min_pts), int(max_size), int(nbins), C.byref(out), size_hist.ctypes.data,
+           nn_hist.ctypes.data, nnd_hist.ctypes.data, ptr(label), ptr(nn), ptr(kind))
+    res = (size_hist, nn_hist, nnd_hist, out)
+    return rc, (res + (label, nn, kind) if per_protein else res)
+
+
+def host_prox_clusters(params: capi.Params, hs: capi.HostState, which, eps: float, min_pts: int = 1, select="all",
+                       mask=None, max_size: int = 256, nbins: int = 64, per_protein: bool = False):
+    """Proximity clusters of a host state, sequentially (kmc_host_prox_clusters): as Simulation.prox_clusters."""
+    v = hs.view()
+    rc, res = _prox_call(load_library().kmc_host_prox_clusters, (C.byref(params), C.byref(v)),
+                         params.n_a + params.n_b, which, eps, min_pts, select, mask, max_size, nbins, per_protein)
     _host_check(rc)
     return res
 
@@ -950,7 +988,7 @@ class Simulation:
     @property
     def analysis_ms(self) -> float:
         """Device milliseconds (HIP events) of the last components / census / pair_counts / track_* / kin_* / cf_* / lag_* / rot_* / pd_* / bd_* / ligand_pose / unwrap /
-        cluster_* / structure_factor / bond_order / bond_order_corr / network / rings call."""
+        cluster_* / structure_factor / bond_order / bond_order_corr / network / rings / prox_clusters call."""
         return float(load_library().kmc_analysis_ms(self._h))
 
     # ---- displacement tracking since a time origin (kmc_dynamics.hip; DESIGN.md §11)
@@ -1391,6 +1429,29 @@ class Simulation:
         the gates, the rest)."""
         ms = (C.c_double * 3)()
         load_library().kmc_enc_phase_ms(self._h, ms)
+        return tuple(float(x) for x in ms)
+
+    # ---- proximity clusters (kmc_proximity.hip; DESIGN.md §23)
+    def prox_clusters(self, which, eps: float, min_pts: int = 1, select="all", mask=None, max_size: int = 256,
+                      nbins: int = 64, per_protein: bool = False):
+        """DBSCAN / friends-of-friends clusters of the current state at the search radius eps — kmc_prox_clusters:
+        (size_hist[max_size + 1], nn_hist[64], nnd_hist[nbins] int64, capi.ProxOut) and, with per_protein,
+        (label[N], nn[N] int32, kind[N] uint8) by reference index, N = n_a + n_b.  which 'A', 'B' or 'AB' (both
+        species as one point set); select 'all' or 'bound'; mask: None or N entries by reference index, non-zero
+        keeps the protein (labelling efficiency); min_pts = 1 is friends-of-friends.  The histograms and
+        out.counts() add over replicas (analysis.reduce_counts); analysis.prox_summary and analysis.nn_distance
+        post-process them."""
+        rc, res = _prox_call(load_library().kmc_prox_clusters, (self._h,), self.params.n_a + self.params.n_b, which,
+                             eps, min_pts, select, mask, max_size, nbins, per_protein)
+        self._check(rc)
+        return res
+
+    @property
+    def prox_phase_ms(self):
+        """Device milliseconds of the last prox_clusters: (select and bin, the count walk, the union walk and the
+        flatten, the border walk with the bond components and the reduces)."""
+        ms = (C.c_double * 4)()
+        load_library().kmc_prox_phase_ms(self._h, ms)
         return tuple(float(x) for x in ms)
 
     def run_encounters(self, nsteps: int, every: int = 1):
