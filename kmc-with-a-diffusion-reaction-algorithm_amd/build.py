@@ -20,8 +20,10 @@ RUN = os.path.join(LIB_DIR, "kmc_run")
 STAMP = os.path.join(LIB_DIR, ".build_stamp")  # content hash of the inputs of the current build
 # kmc_engine.hip is the device translation unit: it includes kmc_kernels.hip, the fourteen layers' kernels (kmc_analysis.hip,
 # kmc_geometry.hip, kmc_structure.hip, kmc_bondorder.hip, kmc_dynamics.hip, kmc_kinetics.hip, kmc_coag.hip, kmc_rings.hip,
-# kmc_lagcorr.hip, kmc_orient.hip, kmc_pairdyn.hip, kmc_bodydyn.hip, kmc_encounter.hip, kmc_proximity.hip) and their host side, kmc_observe.hip (every file of csrc/ enters the build's hash, _inputs)
-SOURCES = ["kmc_engine.hip", "kmc_io.cpp"]
+# kmc_lagcorr.hip, kmc_orient.hip, kmc_pairdyn.hip, kmc_bodydyn.hip, kmc_encounter.hip, kmc_proximity.hip) and their host side, kmc_observe.hip.
+# The two host translation units: kmc_io.cpp (formats, placement, checkpoint, validate) and kmc_host_observe.cpp (the layers'
+# sequential counterparts, kmc_host_*).  Every file of csrc/ enters the build's hash (_inputs).
+SOURCES = ["kmc_engine.hip", "kmc_io.cpp", "kmc_host_observe.cpp"]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 

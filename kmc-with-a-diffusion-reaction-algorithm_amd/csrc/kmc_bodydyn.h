@@ -1,6 +1,6 @@
 // kmc_bodydyn.h — the expressions of the body-dynamics layer that the device
 // kernels (kmc_bodydyn.hip) and the sequential host counterpart
-// (kmc_host_bd_*, kmc_io.cpp) must evaluate alike (include/kmc.h, DESIGN.md
+// (kmc_host_bd_*, kmc_host_observe.cpp) must evaluate alike (include/kmc.h, DESIGN.md
 // §21): the per-member terms of a body's sums, the root correction that turns
 // them into C and S, the verdict on a body and the three rotation terms.
 // Integers throughout; the only doubles are atan2 and cos of the rotation

@@ -28,7 +28,7 @@
 //
 // Included by kmc_engine.hip after kmc_pairdyn.hip (one translation unit, the
 // library's flags); the expressions are kmc_bodydyn.h's, shared with
-// kmc_host_bd_* (kmc_io.cpp); the host side of the calls is kmc_observe.hip
+// kmc_host_bd_* (kmc_host_observe.cpp); the host side of the calls is kmc_observe.hip
 // §body dynamics.
 #include "kmc_bodydyn.h"
 #include "kmc_device.h"

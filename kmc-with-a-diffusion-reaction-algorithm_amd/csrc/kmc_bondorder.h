@@ -1,6 +1,6 @@
 // kmc_bondorder.h — the expressions of the bond-orientational order that the
 // device kernels (kmc_bondorder.hip) and the sequential host counterparts
-// (kmc_host_bond_order / kmc_host_bond_order_corr, kmc_io.cpp) must evaluate
+// (kmc_host_bond_order / kmc_host_bond_order_corr, kmc_host_observe.cpp) must evaluate
 // bit for bit alike (include/kmc.h): the periodic displacement,
 // the cell of the integer grid, the term, the normalisation and the two bin
 // rules.  Doubles, no fused multiply-add (-ffp-contract=off), round_ / atan2 /

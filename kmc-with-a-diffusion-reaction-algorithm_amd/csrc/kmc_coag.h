@@ -1,6 +1,6 @@
 // kmc_coag.h — the expressions of the cluster growth recorder that the device
 // kernels (kmc_coag.hip) and the sequential host counterparts (kmc_host_cf_*,
-// kmc_io.cpp) must evaluate alike (include/kmc.h): the size
+// kmc_host_observe.cpp) must evaluate alike (include/kmc.h): the size
 // clamp, the ordered index of a size pair, the kind of a piece from its packed
 // (receptors, ligands) counts, the pieces clamp, and the two filing rules of a
 // core.  Integers only.

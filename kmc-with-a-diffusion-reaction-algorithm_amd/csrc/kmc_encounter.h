@@ -1,6 +1,6 @@
 // kmc_encounter.h — the expressions of the encounter layer that the device
 // kernels (kmc_encounter.hip) and the sequential host counterparts
-// (kmc_host_reach_census, kmc_host_enc_*, kmc_io.cpp) must evaluate alike
+// (kmc_host_reach_census, kmc_host_enc_*, kmc_host_observe.cpp) must evaluate alike
 // (include/kmc.h): the engine's reaction gates restated on the
 // committed state — the squared site distance, the two angles in gettheta's
 // expression order (main.cpp:2329-2366) over kmcm::sqrt_ / kmcm::acos — the bin

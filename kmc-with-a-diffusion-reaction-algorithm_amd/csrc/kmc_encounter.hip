@@ -31,7 +31,7 @@
 //
 // Included by kmc_engine.hip after kmc_bodydyn.hip (one translation unit, the
 // library's flags); the expressions are kmc_encounter.h's, shared with
-// kmc_host_reach_census / kmc_host_enc_* (kmc_io.cpp); the host side of the
+// kmc_host_reach_census / kmc_host_enc_* (kmc_host_observe.cpp); the host side of the
 // calls is kmc_observe.hip §encounters.
 #include "kmc_device.h"
 #include "kmc_encounter.h"

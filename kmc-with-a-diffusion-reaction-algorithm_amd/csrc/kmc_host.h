@@ -13,6 +13,7 @@ int save_state(const kmc_params* p, const kmc_state_view* v, const char* path, s
 int load_state(const kmc_params* p, const char* path, kmc_state_view* v, std::string* err);
 void derived_counts(const kmc_params* p, const kmc_state_view* v, int* rl, int* mono, int* cis);
 int dd_check(int32_t n, const int32_t* gid, const uint8_t* own, std::string* err);
+void set_error(const std::string& msg);  // what kmc_host_last_error returns next, on this thread
 }  // namespace kmch_host
 
 // host-only entry points (no device needed; also exported for tests)

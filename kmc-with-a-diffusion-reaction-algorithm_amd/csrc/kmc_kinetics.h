@@ -1,6 +1,6 @@
 // kmc_kinetics.h — the expressions of the bond kinetics recorder that the
 // device kernels (kmc_kinetics.hip) and the sequential host counterparts
-// (kmc_host_kin_*, kmc_io.cpp) must evaluate alike (include/kmc.h, DESIGN.md
+// (kmc_host_kin_*, kmc_host_observe.cpp) must evaluate alike (include/kmc.h, DESIGN.md
 // §15): the bin rule of every lifetime and waiting time, and one receptor's
 // transition at an update.  Integers only.
 #pragma once

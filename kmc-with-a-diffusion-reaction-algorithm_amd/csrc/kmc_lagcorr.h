@@ -1,6 +1,6 @@
 // kmc_lagcorr.h — the expressions of the multi-origin lag correlator that the
 // device kernels (kmc_lagcorr.hip) and the sequential host counterpart
-// (kmc_host_lag_*, kmc_io.cpp) must evaluate alike (include/kmc.h, DESIGN.md
+// (kmc_host_lag_*, kmc_host_observe.cpp) must evaluate alike (include/kmc.h, DESIGN.md
 // §18): the integer minimum image, the firing schedule with its slot and row
 // index, and the pair term.  Integers throughout; the only doubles are the
 // cosines of F_s, rounded to fixed point term by term (kmc_structure.h).

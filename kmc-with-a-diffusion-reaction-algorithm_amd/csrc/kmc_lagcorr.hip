@@ -15,7 +15,7 @@
 //
 // Included by kmc_engine.hip after kmc_rings.hip (one translation unit, the
 // library's flags); the expressions are kmc_lagcorr.h's, shared with
-// kmc_host_lag_* (kmc_io.cpp); the host side of the calls is kmc_observe.hip
+// kmc_host_lag_* (kmc_host_observe.cpp); the host side of the calls is kmc_observe.hip
 // §lag correlator.
 #include "kmc_device.h"
 #include "kmc_lagcorr.h"

@@ -1,6 +1,6 @@
 // kmc_orient.h — the expressions of the orientation layer that the device
 // kernels (kmc_orient.hip) and the sequential host counterparts
-// (kmc_host_rot_*, kmc_host_ligand_pose, kmc_io.cpp) must evaluate alike
+// (kmc_host_rot_*, kmc_host_ligand_pose, kmc_host_observe.cpp) must evaluate alike
 // (include/kmc.h): the quantised body vectors, their packing,
 // the handedness, the pair term and the pose bins.  Integers throughout.  The
 // firing schedule, the ring index and the five classes are kmc_lagcorr.h's.

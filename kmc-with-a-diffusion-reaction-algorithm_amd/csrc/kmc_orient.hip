@@ -17,7 +17,7 @@
 //
 // Included by kmc_engine.hip after kmc_lagcorr.hip (one translation unit, the
 // library's flags); the expressions are kmc_orient.h's, shared with
-// kmc_host_rot_* (kmc_io.cpp); the host side of the calls is kmc_observe.hip
+// kmc_host_rot_* (kmc_host_observe.cpp); the host side of the calls is kmc_observe.hip
 // §orientation.
 #include "kmc_device.h"
 #include "kmc_observe.h"

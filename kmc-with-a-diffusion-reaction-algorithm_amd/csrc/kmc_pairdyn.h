@@ -1,6 +1,6 @@
 // kmc_pairdyn.h — the expressions of the pair-dynamics layer that the device
 // kernels (kmc_pairdyn.hip) and the sequential host counterpart
-// (kmc_host_pd_*, kmc_io.cpp) must evaluate alike (include/kmc.h, DESIGN.md
+// (kmc_host_pd_*, kmc_host_observe.cpp) must evaluate alike (include/kmc.h, DESIGN.md
 // §20): the fold into the box, the search grid's cell, the bin of a squared
 // distance against the squared integer edges, the validity of a displacement
 // and the two terms of the displacement correlation.  Integers throughout: no

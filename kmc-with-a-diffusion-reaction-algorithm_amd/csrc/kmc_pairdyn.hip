@@ -18,7 +18,7 @@
 //
 // Included by kmc_engine.hip after kmc_orient.hip (one translation unit, the
 // library's flags); the expressions are kmc_pairdyn.h's, shared with
-// kmc_host_pd_* (kmc_io.cpp); the host side of the calls is kmc_observe.hip
+// kmc_host_pd_* (kmc_host_observe.cpp); the host side of the calls is kmc_observe.hip
 // §pair dynamics.
 #include "kmc_device.h"
 #include "kmc_observe.h"

@@ -1,6 +1,6 @@
 // kmc_proximity.h — the expressions of the proximity clustering that the device
 // kernels (kmc_proximity.hip) and the sequential host counterpart
-// (kmc_host_prox_clusters, kmc_io.cpp) must evaluate bit for bit alike
+// (kmc_host_prox_clusters, kmc_host_observe.cpp) must evaluate bit for bit alike
 // (include/kmc.h).  The integer coordinates, the periodic
 // displacement, the cell of the grid and the distance bins' edges are §14's
 // (kmc_bondorder.h); what is new here is decided by integers alone.

@@ -1,5 +1,5 @@
 // kmc_rings.h — what the device kernels (kmc_rings.hip) and the sequential
-// host counterparts (kmc_host_network / kmc_host_rings, kmc_io.cpp) of the
+// host counterparts (kmc_host_network / kmc_host_rings, kmc_host_observe.cpp) of the
 // ligand network's ring statistics must evaluate alike (include/kmc.h,
 // DESIGN.md §17): the hop over a ligand's three sites with its validity
 // checks, the order of the bridge ends, the site a ring leaves free and the

@@ -1,6 +1,6 @@
 // kmc_structure.h — the two expressions of the structure factor that the
 // device kernel (kmc_structure.hip) and the sequential host counterpart
-// (kmc_host_structure_factor, kmc_io.cpp) must evaluate bit for bit alike
+// (kmc_host_structure_factor, kmc_host_observe.cpp) must evaluate bit for bit alike
 // (include/kmc.h).  Doubles, no fused multiply-add
 // (-ffp-contract=off), round_ / sin / cos of kmc_math.h.
 #pragma once

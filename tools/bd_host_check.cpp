@@ -1,9 +1,10 @@
 // tools/bd_host_check.cpp — the host twin of the body dynamics
-// (kmc_host_bd_*, csrc/kmc_io.cpp) under AddressSanitizer + UBSan: a
+// (kmc_host_bd_*, csrc/kmc_host_observe.cpp) under AddressSanitizer + UBSan: a
 // stand-alone program on the CPU, run by hand.  From the repository root:
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -ffp-contract=off -o /tmp/bd_host_check tools/bd_host_check.cpp \
+//       kmc-with-a-diffusion-reaction-algorithm_amd/csrc/kmc_host_observe.cpp \
 //       kmc-with-a-diffusion-reaction-algorithm_amd/csrc/kmc_io.cpp && /tmp/bd_host_check
 //
 // It binds random cis dimers and ligand bonds (among them bonds that wrap the

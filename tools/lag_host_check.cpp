@@ -1,9 +1,10 @@
 // tools/lag_host_check.cpp — the host twin of the lag correlator
-// (kmc_host_lag_*, csrc/kmc_io.cpp) under AddressSanitizer + UBSan: a
+// (kmc_host_lag_*, csrc/kmc_host_observe.cpp) under AddressSanitizer + UBSan: a
 // stand-alone program on the CPU, run by hand.  From the repository root:
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -ffp-contract=off -o /tmp/lag_host_check tools/lag_host_check.cpp \
+//       kmc-with-a-diffusion-reaction-algorithm_amd/csrc/kmc_host_observe.cpp \
 //       kmc-with-a-diffusion-reaction-algorithm_amd/csrc/kmc_io.cpp && /tmp/lag_host_check
 //
 // It walks random walks with changing links through the shapes whose indexing

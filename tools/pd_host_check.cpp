@@ -1,9 +1,10 @@
 // tools/pd_host_check.cpp — the host twin of the pair dynamics
-// (kmc_host_pd_*, csrc/kmc_io.cpp) under AddressSanitizer + UBSan: a
+// (kmc_host_pd_*, csrc/kmc_host_observe.cpp) under AddressSanitizer + UBSan: a
 // stand-alone program on the CPU, run by hand.  From the repository root:
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -ffp-contract=off -o /tmp/pd_host_check tools/pd_host_check.cpp \
+//       kmc-with-a-diffusion-reaction-algorithm_amd/csrc/kmc_host_observe.cpp \
 //       kmc-with-a-diffusion-reaction-algorithm_amd/csrc/kmc_io.cpp && /tmp/pd_host_check
 //
 // It walks random walks through the shapes whose indexing differs — the

@@ -1,10 +1,11 @@
 // tools/rot_host_check.cpp — the host twins of the orientation layer
-// (kmc_host_rot_*, kmc_host_ligand_pose, csrc/kmc_io.cpp) under
+// (kmc_host_rot_*, kmc_host_ligand_pose, csrc/kmc_host_observe.cpp) under
 // AddressSanitizer + UBSan: a stand-alone program on the CPU, run by hand.
 // From the repository root:
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       -ffp-contract=off -o /tmp/rot_host_check tools/rot_host_check.cpp \
+//       kmc-with-a-diffusion-reaction-algorithm_amd/csrc/kmc_host_observe.cpp \
 //       kmc-with-a-diffusion-reaction-algorithm_amd/csrc/kmc_io.cpp && /tmp/rot_host_check
 //
 // It tumbles bodies with changing links, reflections and now and then a bad
